@@ -28,9 +28,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The step runs on ten HIP streams (points, tracking chain, four line and four plane streams).  The ROCm runtime maps streams onto 4 hardware queues by default and
-# launches that share a queue serialise; with 8 queues the step takes 105.7 instead of 115.0 ms (12 / 16 measure the same).  Must be set before the runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 ENV_OVERRIDES = []
@@ -58,6 +55,75 @@ def pick_device(args, torch):
             raise SystemExit(f"rank {local_rank} has no GPU ({ndev} visible): RCCL needs one device per rank (use --backend gloo to share devices)")
         local_rank %= ndev
     return local_rank
+
+
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes of all .npy files together
+DUMP_STREAMS = 16       # streams whose large per-frame outputs (keypoints, descriptors, label images, voxel clouds) are written
+
+
+def dump_streams(B, seed=0):
+    """The fixed, seeded sample of streams --dump-outputs writes the large per-frame outputs of (the same for every run with the same batch)."""
+    import numpy as np
+    return np.sort(np.random.default_rng(seed).choice(B, size=min(B, DUMP_STREAMS), replace=False))
+
+
+def upto(a, counts):
+    """a[b, j] for j < counts[b], zero beyond (what a buffer holds past a frame's count is no output)."""
+    import numpy as np
+    a = np.array(a)
+    a[np.arange(a.shape[1])[None, :] >= np.asarray(counts).reshape(-1, 1)] = 0
+    return a
+
+
+def keypoints(a):
+    """[..., S, 7] float32 key point records (x, y, size, angle, response as floats; octave, class_id as int32 bits) -> [..., S, 7] float64 values."""
+    import numpy as np
+    from numpy.lib.recfunctions import structured_to_unstructured
+    from planarslam_amd._lib import KP_DTYPE
+    a = np.ascontiguousarray(a)
+    return structured_to_unstructured(a.view(KP_DTYPE).reshape(a.shape[:-1]), np.float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy.  float64 stays float64, float32 and the integer types that float32 holds exactly become
+    float32, wider integers float64.  Refuses to write more than DUMP_BUDGET bytes in all."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        if a.dtype == np.float64 or (a.dtype.kind in "iu" and a.size and np.abs(a.astype(np.int64)).max() > (1 << 24)):
+            out[name] = np.ascontiguousarray(a, np.float64)
+        else:
+            out[name] = np.ascontiguousarray(a, np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_BUDGET})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def track_outputs(tp, k, B):
+    """What a caller of TrackPipeline receives for the step whose extraction buffers are set k, after its tracking chain (the last one run): the extractors'
+    outputs of the sampled streams (dump_streams) and every stream's counts, poses and match counts."""
+    import numpy as np
+    from numpy.lib.recfunctions import structured_to_unstructured
+    from planarslam_amd._lib import KEYLINE_DTYPE
+    s = dump_streams(B)
+    g = lambda x: x.cpu().numpy()
+    n, nl, npl, pc = g(tp.n[k]), g(tp.nl[k]), g(tp.npl[k]), tp.pc[k]
+    npc, off = g(pc["n"]), g(pc["off"])
+    kl = structured_to_unstructured(g(tp.kls[k]).view(KEYLINE_DTYPE).reshape(B, 40)[s], np.float64)
+    A0, A1 = tp.pb_arrays
+    return {"sample_streams": s,
+            "orb_count": n, "orb_keypoints": upto(keypoints(g(tp.kps[k])[s]), n[s]), "orb_descriptors": upto(g(tp.desc[k])[s], n[s]),
+            "line_count": nl, "line_keylines": upto(kl, nl[s]), "line_descriptors": upto(g(tp.ldesc[k])[s], nl[s]), "line_equations": upto(g(tp.leq[k])[s], nl[s]),
+            "plane_count": npl, "planes": upto(g(tp.pls[k])[s], npl[s]), "plane_labels": g(tp.lab[k])[s].reshape(len(s), tp.H, tp.W),
+            "plane_kept_count": npc, "plane_coefficients": upto(g(pc["coef"])[s], npc[s]), "plane_source": upto(g(pc["src"])[s], npc[s]),
+            "plane_point_offsets": upto(off[s], npc[s] + 1), "plane_points": upto(g(pc["pts"])[s], off[s, npc[s]]),
+            "point_matches_last_frame": tp.nm, "point_matches_local_map": tp.nmm, "line_matches": g(tp.lm)[s], "plane_matches": tp.nplm,
+            "translation_opt_Tcw": A0["Tcw_out"], "translation_opt_inliers": A0["n_inliers"], "pose_opt_Tcw": A1["Tcw_out"], "pose_opt_inliers": A1["n_inliers"],
+            "pose_opt_lm_iterations": A1["lm_iters"], "Tcw": tp.pose}
 
 
 def parity_sample(tp, frames, depths, k, B, cam, streams=None):
@@ -148,6 +214,8 @@ def main():
                          "launch, rendezvous, shard and print paths are exercised on a 1-GPU box")
     ap.add_argument("--gen-procs", type=int, default=0, help="worker processes that synthesise the canvases (0 = up to 32; 1 = in this process: rocprofv3 --pmc hangs in "
                                                              "forked children, profiles/README.md)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                                                          "rank 0; the large per-frame arrays for a fixed, seeded sample of %d streams)" % DUMP_STREAMS)
     args = ap.parse_args()
     # no timing / variant switch reaches the timed region through the environment: the product reads none (PLANAR_HIP_LIB, a developer build of the same library, is
     # reported in the line; stage skipping lives in tools/stage_skip.py, which relabels its output)
@@ -372,6 +440,13 @@ def main():
         tp.check()
         if PARITY_SAMPLE and rank_env == 0:
             parity = parity_sample(tp, frames, depths, (args.warmup + args.steps - 1) % NB, B, TUM3)
+    if args.dump_outputs and rank_env == 0:     # before the PCIe loop and the sub-benchmarks reuse the buffers
+        if full:
+            dump_outputs(args.dump_outputs, track_outputs(tp, (args.warmup + args.steps - 1) % NB, B))
+        else:
+            s = dump_streams(B); n = o_n.cpu().numpy()
+            dump_outputs(args.dump_outputs, {"sample_streams": s, "orb_count": n, "orb_keypoints": upto(keypoints(o_kps.cpu().numpy()[s]), n[s]),
+                                             "orb_descriptors": upto(o_desc.cpu().numpy()[s], n[s])})
 
     seg = lambda a, b: sum(e[a].elapsed_time(e[b]) for e in evsets) / args.steps
     stage_ms = {"orb_extract": seg("start", "orb")}
@@ -758,18 +833,19 @@ def main_ba(args):
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     ranks = Ranks(backend=args.backend, device=dev)
-    line = ba_line(args.steps, args.warmup, args.cpu_seconds, args.backend, ranks, local_rank, dev)
+    line = ba_line(args.steps, args.warmup, args.cpu_seconds, args.backend, ranks, local_rank, dev, dump=args.dump_outputs)
     if line is not None:
         print(json.dumps(line))
     ranks.close()
 
 
-def ba_line(steps, warmup, cpu_seconds, backend, ranks, local_rank, dev):
+def ba_line(steps, warmup, cpu_seconds, backend, ranks, local_rank, dev, dump=None):
     """BASELINE configs[4] (0-based: the fifth entry, "Local BA"; DESIGN.md and earlier rounds also called it "config 5" counting from one): local bundle adjustment
     of 10 free key frames (+ 2 fixed ones that only observe) x 3000 point / line / plane features.  ONE problem; its landmarks (with all
     their edges) are partitioned over the ranks, every rank linearises its part, and the reduced camera system is all-reduced over RCCL twice
     per LM trial (planarslam_amd/csrc/ba.hip).  A step = one complete solve (optimize(5), outlier levels, optimize(10), erase flags) through the
-    host-pointer entry point, so the upload of the graph is inside the timed region.  Total work is fixed: "scaling": "strong".  Returns the line on rank 0."""
+    host-pointer entry point, so the upload of the graph is inside the timed region.  Total work is fixed: "scaling": "strong".  Returns the line on rank 0.
+    dump: directory of --dump-outputs (rank 0 writes the last solve's result there)."""
     import types
 
     import numpy as np
@@ -803,6 +879,8 @@ def ba_line(steps, warmup, cpu_seconds, backend, ranks, local_rank, dev):
         res = local_bundle_adjustment(mine, TUM3, ctx=ctx, comm=comm)
     barrier()
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
+    if dump and rank == 0:
+        dump_outputs(dump, {"kf_Tcw": res["kf_Tcw"], "landmarks": res["lm"], "edge_outlier": res["e_outlier"], "lm_iterations": np.array([res["lm_iters"]])})
     K, L, E = len(prob["kf_fixed"]), len(prob["lm_type"]), len(prob["e_kf"])
     np_free = int((np.asarray(prob["kf_fixed"]) == 0).sum())
     K_pre, L_pre, E_pre, np_free_pre = K, L, E, np_free
@@ -868,17 +946,18 @@ def main_pose(args):
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     ranks = Ranks(backend=args.backend, device=dev)
-    line = pose_line(args.steps, args.warmup, args.cpu_seconds, args.batch, ranks, local_rank, dev)
+    line = pose_line(args.steps, args.warmup, args.cpu_seconds, args.batch, ranks, local_rank, dev, dump=args.dump_outputs)
     if line is not None:
         print(json.dumps(line))
     ranks.close()
 
 
-def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev):
+def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev, dump=None):
     """BASELINE configs[3]: pose-only Levenberg-Marquardt, 1000 point + 150 line (75 lines x 2 end points) + 12 plane (4 planes x plane / parallel / vertical)
     edges per frame, batch = 256 frames per GPU (synth.pose_batch(B = 256, seed = 7 + 1000 * rank)), resident in HBM.  A step = Optimizer::PoseOptimization
     (src/Optimizer.cc:550-1275: four rounds of optimize(10) with outlier reclassification) for every frame of the batch: one launch of pose_opt_kernel.  Frames are
-    independent: every rank has its own batch, no collective ("weak").  Returns the line on rank 0."""
+    independent: every rank has its own batch, no collective ("weak").  Returns the line on rank 0.  dump: directory of --dump-outputs (rank 0 writes the
+    last 4 x optimize(10) launch's outputs there)."""
     import ctypes as C
     import types
 
@@ -928,6 +1007,8 @@ def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev):
 
     el_1, k_1, it_1 = run(1, 10, args.steps, args.warmup)        # one optimize(10): the "10 iters" protocol of BASELINE.md
     el, k_ms, lm_it = run(4, 10, args.steps, args.warmup)         # the reference's PoseOptimization: 4 x optimize(10)
+    if dump and rank == 0:
+        dump_outputs(dump, {k: d[k] for k in ("Tcw_out", "n_inliers", "lm_iters", "pt_outlier", "ln_outlier", "pl_outlier")})
     if rank != 0:
         return None
     # parity of this very batch with the real optimiser is tests/test_pose_gpu.py::test_pose_hip_equals_reference_fixture (c4_b256)

@@ -1,4 +1,4 @@
-import sys, time; sys.path.insert(0,'/root/repo')
+import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, ctypes as C
 from planarslam_amd import Context, PlaneDetection, Optimizer, ORBextractor
 from planarslam_amd._lib import PoseBatch, lib, check
