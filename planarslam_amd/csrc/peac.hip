@@ -8,8 +8,8 @@
 //   peac_blocks   one THREAD per 10x10 block: depth -> XYZ in FP64, validity / depth-discontinuity tests, the nine moment sums
 //                 accumulated in the reference's raster order (bit-exact FP64 sums), PCA by the iterative 3x3 symmetric
 //                 eigen-solver (Eigen's algorithm, restated)                                                            (a13-a15)
-//   peac_ahc3     one WAVEFRONT (64 lanes) per frame, the order-dependent clustering (peac_ahc2.h: lazy adjacency, tournament queue; frames with
-//                 bit-equal keys are redone with libstdc++'s exact heap by the same workgroup)
+//   peac_ahc3     one WAVEFRONT (64 lanes) per frame, two per SIMD, the order-dependent clustering (peac_ahc2.h: lazy adjacency, tournament queue;
+//                 frames with bit-equal keys are redone with libstdc++'s exact heap by peac_ahc2's only_retry launch that follows)
 //   peac_order    ranks the frames by the clustering time of the previous call (longest first) for the next launch
 //   peac_refine   256 threads per frame: block erosion + seed queue (prefix sums) -> floodFill (512 queue entries x 4 neighbours per step;
 //                 all pairs of a step that meet at one pixel are folded IN THE REFERENCE'S ORDER by one thread: round 5) -> final
@@ -889,7 +889,7 @@ struct planar_peac {
     int W = 0, H = 0, max_batch = 0;
     peac::Layout L{};
     peac::Consts C{};
-    int smem2 = 0, smem_refine = 0;
+    int smem2 = 0, smem3 = 0, smem_refine = 0;
     // kernel variants, set only through planar_peac_set_variant (tools' A/B runs and tests; no environment switch reaches the product path)
     int wide_below = 64;                                      // batches up to this size refine with 1024 threads per frame (0 = never)
     bool exact_only = false;                                  // skip the fast clustering attempt: every frame through the exact heap
@@ -917,16 +917,19 @@ int planar_peac_create(planar_ctx* ctx, int width, int height, int max_batch, pl
     o->C = peac::make_consts();
     const peac::Layout& L = o->L;
     o->smem2 = peac::ahc2_smem_bytes(L);
-    // Frame sizes: node ids are 16 bits, and the clustering wavefront keeps the queue keys (8 B per block), the merge-parent table (4 B per block) and three bitmaps in LDS:
-    // up to ~10 900 blocks = 160 KB (1280x720 = 9 216 blocks: 114 KB, one frame per CU at a time; 640x480 = 3 072: 38 KB, four per CU)
+    o->smem3 = peac::ahc3_smem_bytes(L);
+    // Frame sizes: node ids are 16 bits.  The fast clustering kernel keeps the queue keys (4 B per block), the merge-parent table (2 B per block) and two
+    // bitmaps in LDS: 640x480 = 3 072 blocks: 19.4 KB (+ 0.8 KB static), eight frames per CU (two wavefronts per SIMD).  The exact kernel that redoes the
+    // frames the fast one gives up on keeps 8 + 4 B per block: up to ~10 900 blocks = 160 KB (1280x720 = 9 216 blocks: 114 KB; 640x480: 38 KB)
     o->smem_refine = (int)((L.NB + 15) / 16 * 16);
-    if (L.pool_cap > 65535 || L.NB2 > 65535 || o->smem2 > 160 * 1024 - 2048) {
+    if (L.pool_cap > 65535 || L.NB2 > 65535 || o->smem2 > 160 * 1024 - 2048 || o->smem3 > o->smem2) {
         delete o;
         set_error("planar_peac_create: %dx%d = %d blocks of 10x10 pixels: the clustering kernel's LDS-resident queue holds about 10 900 (1280x720 fits, 1920x1080 does not)", width, height, L.NB);
         return PLANAR_EINVAL;
     }
     if (o->smem2 > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)peac::peac_ahc3, hipFuncAttributeMaxDynamicSharedMemorySize, o->smem2);
+        hipError_t e = hipSuccess;
+        if (o->smem3 > 48 * 1024) e = hipFuncSetAttribute((const void*)peac::peac_ahc3, hipFuncAttributeMaxDynamicSharedMemorySize, o->smem3);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)peac::peac_ahc2, hipFuncAttributeMaxDynamicSharedMemorySize, o->smem2);
         if (e != hipSuccess) { (void)hipGetLastError(); delete o; set_error("planar_peac_create: %d bytes of LDS per workgroup are not available: %s", o->smem2, hipGetErrorString(e)); return PLANAR_EINVAL; }
     }
@@ -972,14 +975,16 @@ int planar_peac_segment_dev(planar_peac* p, const uint16_t* d_depth, int B, int 
     hipLaunchKernelGGL(peac::peac_blocks, dim3((p->L.NB + 63) / 64, B), dim3(64), 0, st, p->L, K, d_depth, pitch_px, frame_stride_px, p->d_ws.as<uint8_t>());
     mark();
     {
-        // the fast attempt (tournament queue), then the exact kernel for the frames it gave up on (bit-equal keys of two live nodes: degenerate input)
-        // (the workgroup that gave up redoes its frame itself: no second launch)
+        // the fast attempt (tournament queue), then the exact kernel for the frames it gave up on (bit-equal keys of two live nodes: degenerate input):
+        // a workgroup of the second launch whose frame has no ST_RETRY exits at once
         // (on the context's side stream when it has one: planar_ctx_set_seq_stream)
         hipStream_t sq = p->ctx->seq_begin();
-        if (!p->exact_only)
-            hipLaunchKernelGGL(peac::peac_ahc3, dim3(B), dim3(64), p->smem2, sq, p->L, p->C, p->d_ws.as<uint8_t>(), p->d_status.as<int32_t>(),
-                               p->d_timing.as<long long>(), p->d_next.as<int>(), p->order_B == B ? p->d_order.as<int>() : nullptr, 1);
-        else
+        if (!p->exact_only) {
+            hipLaunchKernelGGL(peac::peac_ahc3, dim3(B), dim3(64), p->smem3, sq, p->L, p->C, p->d_ws.as<uint8_t>(), p->d_status.as<int32_t>(),
+                               p->d_timing.as<long long>(), p->d_next.as<int>(), p->order_B == B ? p->d_order.as<int>() : nullptr, 0);
+            hipLaunchKernelGGL(peac::peac_ahc2, dim3(B), dim3(64), p->smem2, sq, p->L, p->C, p->d_ws.as<uint8_t>(), p->d_status.as<int32_t>(),
+                               p->d_timing.as<long long>(), p->d_next.as<int>(), nullptr, 1);
+        } else
             hipLaunchKernelGGL(peac::peac_ahc2, dim3(B), dim3(64), p->smem2, sq, p->L, p->C, p->d_ws.as<uint8_t>(), p->d_status.as<int32_t>(),
                                p->d_timing.as<long long>(), p->d_next.as<int>(), p->order_B == B ? p->d_order.as<int>() : nullptr, 0);
         p->ctx->seq_end();

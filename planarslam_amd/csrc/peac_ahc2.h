@@ -11,7 +11,7 @@
 // By induction over the merge sequence, { live end of the chain of x : x in bag(a) } is exactly the reference's nbs(a) for every live a:
 // a merge replaces its two nodes by m in every neighbour's set, which is what following mp does; a disconnect erases the node from every
 // set, which is what TOMB does.  Chains are shortened by path halving (only ever re-pointing a node to one of its ancestors: results do not
-// depend on it).  The union of a merge is a 6144-bit LDS bitmap: both bags' resolved entries set their bit, rank = prefix popcount, so the
+// depend on it).  The union of a merge is an LDS bitmap with a bit per node id: both bags' resolved entries set their bit, rank = prefix popcount, so the
 // new bag comes out deduplicated and in ascending node id (= the reference's std::set order) with no searches.
 //
 // Candidate merges of a node are a pure function of its live-neighbour set, so they are evaluated ahead of time (the popped node together
@@ -63,6 +63,11 @@ static inline int ahc2_smem_bytes(const Layout& L) {
     const int W32 = (L.NB2 + 31) / 32;
     return (int)((size_t)L.NB * 8 + al8((size_t)L.NB2 * 2) + (size_t)W32 * 4 * 2 + al8((size_t)W32 * 2));
 }
+// LDS bytes of peac_ahc3: the fast attempt names a merged node after one of its parts, so NB ids: queue keys (4 B), merge parents (2 B), two bitmaps
+static inline int ahc3_smem_bytes(const Layout& L) {
+    const int W32 = (L.NB + 31) / 32;
+    return (int)((size_t)L.NB * 4 + al8((size_t)L.NB * 2) + (size_t)W32 * 4 * 2 + al8((size_t)W32 * 2));
+}
 
 typedef unsigned long long u64;
 
@@ -85,29 +90,39 @@ constexpr unsigned K_EMPTY = 0xffffff80u;  // tournament queue: no node (above e
 //               a node clears its slot and recomputes one column (one LDS round trip).  Nodes that die are removed at once, so there are no pops
 //               of dead nodes (the reference pops and skips ~2600 of them per 640x480 frame).  Wherever equal proxies meet (inside a column when
 //               it is recomputed, across columns at the top, at a push) the FP64 keys are compared, and bit-equal FP64 keys of two live nodes
-//               end the attempt with ST_RETRY: the launch of peac_ahc2 that follows redoes exactly those frames with the exact heap.
+//               end the attempt with ST_RETRY: the exact heap redoes exactly those frames (peac_ahc3).
+struct AhcShared { int ext[MAX_PLANES]; unsigned mark[64]; };   // static LDS of a frame, declared by the kernel: its two ahc_frame forms share it
 template <bool FAST>
 __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8_t* __restrict__ ws, int32_t* __restrict__ status,
-                                          long long* __restrict__ timing, const int frame) {
+                                          long long* __restrict__ timing, const int frame, AhcShared& sh) {
     PLANAR_DYN_SMEM(smem);
-    __shared__ int s_ext[MAX_PLANES];
-    __shared__ unsigned s_mark[64];
+    int* s_ext = sh.ext;
+    unsigned* s_mark = sh.mark;
     const int lane = threadIdx.x;
     uint8_t* F = ws + (size_t)frame * L.frame_bytes;
-    double* g_stats = (double*)(F + L.off_stats);
-    double* g_geo = (double*)(F + L.off_geo);
-    int* g_N = (int*)(F + L.off_N);
+    // the nodes' moments / plane / N by creation id: blocks 0 .. NB-1, then merged nodes in merge order (what peac_refine and the retry read)
+    double* o_stats = (double*)(F + L.off_stats);
+    double* o_geo = (double*)(F + L.off_geo);
+    int* o_N = (int*)(F + L.off_N);
+    // ... and the copy the kernel works on, indexed by node id.  FAST: entries NB2 .. NB2 + NB - 1 of the same arrays (the blocks copied there first), so the
+    // blocks' entries stay as peac_blocks wrote them for the exact kernel that may redo the frame
+    double* g_stats = FAST ? o_stats + (size_t)L.NB2 * 9 : o_stats;
+    double* g_geo = FAST ? o_geo + (size_t)L.NB2 * 7 : o_geo;
+    int* g_N = FAST ? o_N + L.NB2 : o_N;
     const uint8_t* g_flags = F + L.off_flags;
     uint32_t* crec = (uint32_t*)(F + L.off_crec);
     u16* bpool = (u16*)(F + L.off_bpool);
     u16* h_dsp = (u16*)(F + L.off_h_dsp); u16* h_dss = (u16*)(F + L.off_h_dss); u16* h_rid = (u16*)(F + L.off_h_rid);
     int* g_hand = (int*)(F + L.off_h_hand);
-    const int NB = L.NB, NB2 = L.NB2, Nw = L.Nw, Nh = L.Nh, W32 = (NB2 + 31) / 32;
+    // Node ids.  Exact kernel: creation ids, NB2 of them.  FAST: a merge kills two nodes and makes one, so at most NB are alive: the merged node takes
+    // the id of its part p (mp[nb] = p, mp[p] stays p: an old bag entry resolves to the node it was merged into, as before).  Its creation id (what
+    // the reference's neighbour order and peac_refine go by) is kept in dword 2 of its record.
+    const int NB = L.NB, NB2 = L.NB2, Nw = L.Nw, Nh = L.Nh, NS = FAST ? NB : NB2, W32 = (NS + 31) / 32;
 
     // merge heap: one 64-bit word per entry = key rounded to float (bits 0..31) | node id (32..47) | bag size at creation, 255 = in the pool (48..55)
     u64* hp = (u64*)smem;
-    u16* mp = (u16*)(smem + (size_t)NB * 8);                                            // merge-parent pointers
-    unsigned* cval = (unsigned*)((uint8_t*)mp + al8((size_t)NB2 * 2));                  // bit per node: its candidate record is valid
+    u16* mp = (u16*)(smem + (size_t)NB * (FAST ? 4 : 8));                               // merge-parent pointers
+    unsigned* cval = (unsigned*)((uint8_t*)mp + al8((size_t)NS * 2));                   // bit per node: its candidate record is valid
     unsigned* bmp = cval + W32;                                                         // union bitmap (all zero between merges)
     u16* pre = (u16*)(bmp + W32);                                                       // exclusive popcount prefix of the bitmap words
 
@@ -133,7 +148,12 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
     // ---- init ----
     unsigned char* cnt8 = (unsigned char*)hp;                // bag sizes while the graph is built (the heap is built afterwards)
     for (int b = lane; b < NB; b += 64) { cnt8[b] = 0; h_dsp[b] = (u16)b; h_dss[b] = 1; h_rid[b] = (u16)b; }
-    for (int t = lane; t < NB2; t += 64) mp[t] = (u16)t;
+    for (int t = lane; t < NS; t += 64) mp[t] = (u16)t;
+    if constexpr (FAST) {
+        for (int t = lane; t < NB * 9; t += 64) g_stats[t] = o_stats[t];
+        for (int t = lane; t < NB * 7; t += 64) g_geo[t] = o_geo[t];
+        for (int t = lane; t < NB; t += 64) g_N[t] = o_N[t];
+    }
     for (int t = lane; t < W32; t += 64) { cval[t] = 0; bmp[t] = 0; }
     __syncthreads();
 
@@ -176,7 +196,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         uint32_t* r = rec(b);
         r[0] = (uint32_t)cnt8[b];
         r[1] = (uint32_t)(g_N[b] / (WIN * WIN)) << 16;
-        r[2] = (uint32_t)b;
+        r[2] = (uint32_t)b | (uint32_t)b << 16;                  // rid | creation id
         r[3] = 0;
     }
     __syncthreads();
@@ -255,7 +275,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
 
 
     // ---- FAST: the tournament queue ----
-    unsigned* K = (unsigned*)smem;                            // [NB2] (the heap's LDS)
+    unsigned* K = (unsigned*)smem;                            // [NS] (the heap's LDS)
     float top_key = 0.f, la_margin = 0.5f;                    // proxy key of the node being popped; lookahead margin (eval_phase)
     unsigned cm_v = K_EMPTY;                                  // this lane's column minimum: raw K value ...
     int cm_id = -1;                                           // ... and node id
@@ -274,23 +294,23 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
     // (frames of more than 4096 blocks - 8192 node ids, two per lane and column - take the general form: any number of ids per lane)
     auto col_recompute_large = [&](int Lc) {
         unsigned mn = K_EMPTY;
-        for (int i = Lc + 64 * lane; i < NB2; i += 4096) mn = min(mn, kproxy(K[i]));
+        for (int i = Lc + 64 * lane; i < NS; i += 4096) mn = min(mn, kproxy(K[i]));
         mn = wave_min_u32(mn);
         int id = -1; unsigned v = K_EMPTY;
         if (mn != K_EMPTY) {
             int nmatch = 0, first = -1;
-            for (int base = 0; base < NB2; base += 4096) {
+            for (int base = 0; base < NS; base += 4096) {
                 const int i = base + Lc + 64 * lane;
-                const u64 m = __ballot(i < NB2 && kproxy(K[min(i, NB2 - 1)]) == mn);
+                const u64 m = __ballot(i < NS && kproxy(K[min(i, NS - 1)]) == mn);
                 if (m) { if (first < 0) first = base + Lc + 64 * (__ffsll((long long)m) - 1); nmatch += __popcll(m); }
             }
             if (nmatch == 1) id = first;
             else {
                 GFENCE();
                 Pick P{-1, 0.0, false, false};
-                for (int base = 0; base < NB2; base += 4096) {
+                for (int base = 0; base < NS; base += 4096) {
                     const int i = base + Lc + 64 * lane;
-                    for (u64 m = __ballot(i < NB2 && kproxy(K[min(i, NB2 - 1)]) == mn); m; m &= m - 1) pick_add(P, base + Lc + 64 * (__ffsll((long long)m) - 1));
+                    for (u64 m = __ballot(i < NS && kproxy(K[min(i, NS - 1)]) == mn); m; m &= m - 1) pick_add(P, base + Lc + 64 * (__ffsll((long long)m) - 1));
                 }
                 if (P.tie) err = ST_RETRY;
                 id = P.id;
@@ -300,9 +320,9 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         if (lane == Lc) { cm_v = v; cm_id = id; }
     };
     auto col_recompute = [&](int Lc) {                        // Lc wave-uniform
-        if (NB2 > 8192) { col_recompute_large(Lc); return; }
+        if (NS > 8192) { col_recompute_large(Lc); return; }
         const int i1 = Lc + 64 * lane, i2 = i1 + 4096;
-        const unsigned v1 = i1 < NB2 ? K[i1] : K_EMPTY, v2 = i2 < NB2 ? K[i2] : K_EMPTY;
+        const unsigned v1 = i1 < NS ? K[i1] : K_EMPTY, v2 = i2 < NS ? K[i2] : K_EMPTY;
         const unsigned p1 = kproxy(v1), p2 = kproxy(v2);
         const unsigned mn = wave_min_u32(min(p1, p2));
         int id = -1; unsigned v = K_EMPTY;
@@ -564,18 +584,20 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         int w_nb = __shfl((int)r, win);
         const bool odd = active && ok && (mg.mse != mg.mse || (mg.mse == min_m && (int)r != w_nb));
         u64 oddm = __ballot(odd);
-        while (oddm) {   // exact ties or NaNs inside a segment: the reference's in-order rule over the DISTINCT neighbours in ascending id (rare)
+        int rk = 0;                                             // creation id of the neighbour: the reference's order
+        if (oddm) { GFENCE(); if (active && ok) rk = FAST ? (int)(rec((int)r)[2] >> 16) : (int)r; }
+        while (oddm) {   // exact ties or NaNs inside a segment: the reference's in-order rule over the DISTINCT neighbours in ascending creation id (rare)
             const int ol = __ffsll((long long)oddm) - 1;
             const int shp = wave_lane(hpos, ol), scnt = wave_lane(cnt, ol);
             const bool mine = active && lane >= shp && lane < shp + scnt;
             bool f_have = false; double f_mse = 0; int f_N = 0, f_lane = 0, last_id = -1;
             while (true) {
-                int cid = (mine && ok && (int)r > last_id) ? (int)r : 0x7fffffff;
+                int cid = (mine && ok && rk > last_id) ? rk : 0x7fffffff;
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) cid = min(cid, __shfl_xor(cid, o));
                 cid = wave_uni(cid);
                 if (cid == 0x7fffffff) break;
-                const u64 who = __ballot(mine && ok && (int)r == cid);
+                const u64 who = __ballot(mine && ok && rk == cid);
                 const int sl = __ffsll((long long)who) - 1;
                 const double c_mse = wave_lane(mg.mse, sl); const int c_N = wave_lane(mN, sl);
                 if (!f_have || f_mse > c_mse || (f_mse == c_mse && (double)f_N < c_mse)) { f_have = true; f_mse = c_mse; f_N = c_N; f_lane = sl; }   // quirk :1045
@@ -670,9 +692,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             for (int t = 0; t < 9; t++) ps[t] = sp[t];
             const double pn0 = gp[0], pn1 = gp[1], pn2 = gp[2];
             const int Na = g_N[p];
-            double b_ms[9], b_mse = INF; Geo b_g; unsigned b_r = TOMB; bool b_have = false, odd = false;
-#pragma unroll
-            for (int t = 0; t < 9; t++) b_ms[t] = 0;
+            double b_mse = INF; Geo b_g; unsigned b_r = TOMB; bool b_have = false, odd = false;
 #pragma unroll
             for (int t = 0; t < 3; t++) { b_g.center[t] = 0; b_g.normal[t] = 0; }
             b_g.mse = 0;
@@ -680,8 +700,8 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             // s_mov_b64 and a 64-bit literal, which gfx950 does not have - the register ends up 0 (tests/test_build_sanity.py scans for it).
             double bestm = BIG;
             // 256 bag entries at a time, four per lane.  In a batch the frame workspaces do not fit the caches: every dependent global access is an HBM
-            // round trip (2-4 k cycles), so each kind of load is issued for all four chunks before anything waits for it: entries, then the
-            // candidates' normals and N, then their moments.
+            // round trip (2-4 k cycles), so the entries of all four chunks are requested before anything waits for them.  Only a lower bound per chunk
+            // stays in registers (the kernel runs at two wavefronts per SIMD: 256 registers).
             for (int g0 = 0; g0 < cp; g0 += 256) {
                 unsigned cr[4];
 #pragma unroll
@@ -698,28 +718,21 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                     cr[c] = keep ? r : TOMB;                                                  // this lane's candidate of chunk c
                 }
                 PEAC_TICK(19);
-                double cms[4][9], clb[4], cn[4][3]; int cN[4];
+                // per lane and chunk only the candidate and the lower bound of its merged mse stay live; the merged moments are formed again
+                // (same additions, same result) for the candidate a solve round picks
+                double clb[4]; int cN[4];
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     const int idx = cr[c] == TOMB ? p : (int)cr[c];
                     const double* gn = geo_of(idx) + 3;
-                    cn[c][0] = gn[0]; cn[c][1] = gn[1]; cn[c][2] = gn[2];
-                    cN[c] = g_N[idx];
-                }
+                    const double* sb = g_stats + (size_t)idx * 9;
+                    double cms[9];
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const double* sb = g_stats + (size_t)(cr[c] == TOMB ? p : (int)cr[c]) * 9;
-#pragma unroll
-                    for (int t = 0; t < 9; t++) cms[c][t] = sb[t];
-                }
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const bool ok = cr[c] != TOMB && !(fabs(pn0 * cn[c][0] + pn1 * cn[c][1] + pn2 * cn[c][2]) < C.cos_merge);   // AHCPlaneFitter.hpp:1035
-#pragma unroll
-                    for (int t = 0; t < 9; t++) cms[c][t] = ps[t] + cms[c][t];
-                    cN[c] = Na + cN[c];
+                    for (int t = 0; t < 9; t++) cms[t] = ps[t] + sb[t];
+                    cN[c] = Na + g_N[idx];
+                    const bool ok = cr[c] != TOMB && !(fabs(pn0 * gn[0] + pn1 * gn[1] + pn2 * gn[2]) < C.cos_merge);   // AHCPlaneFitter.hpp:1035
                     if (!ok) cr[c] = TOMB;
-                    const double lb = merged_mse_lower_bound(cms[c], cN[c]);
+                    const double lb = merged_mse_lower_bound(cms, cN[c]);
                     clb[c] = ok ? lb : INF;
                 }
                 PEAC_TICK(20);
@@ -729,24 +742,19 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                     for (int c = 1; c < 4; c++) if (clb[c] < lbs) { lbs = clb[c]; sel = c; }
                     const bool go = lbs < INF && lbs <= bestm;
                     if (!__ballot(go)) break;
-                    double s2[9]; int N2 = 1; unsigned r2 = TOMB;
+                    int N2 = 1; unsigned r2 = TOMB;
 #pragma unroll
-                    for (int t = 0; t < 9; t++) s2[t] = t >= 3 && t < 6 ? 1.0 : 0.0;          // idle lanes solve a harmless diagonal matrix
+                    for (int c = 0; c < 4; c++) if (go && sel == c) { N2 = cN[c]; r2 = cr[c]; clb[c] = INF; }
+                    double s2[9];
+                    const double* sb = g_stats + (size_t)(go ? r2 : (unsigned)p) * 9;
 #pragma unroll
-                    for (int c = 0; c < 4; c++) if (go && sel == c) {
-#pragma unroll
-                        for (int t = 0; t < 9; t++) s2[t] = cms[c][t];
-                        N2 = cN[c]; r2 = cr[c]; clb[c] = INF;
-                    }
+                    for (int t = 0; t < 9; t++) { const double v = ps[t] + sb[t]; s2[t] = go ? v : (t >= 3 && t < 6 ? 1.0 : 0.0); }   // idle lanes solve a harmless diagonal matrix
                     Geo g2;
                     stats_compute_u(s2, N2, g2);
                     if (go) {
                         if (!(g2.mse < BIG)) odd = true;                            // NaN / infinite: the in-order path decides
-                        else if (!b_have || g2.mse < b_mse) {
-                            b_have = true; b_mse = g2.mse; b_g = g2; b_r = r2;
-#pragma unroll
-                            for (int t = 0; t < 9; t++) b_ms[t] = s2[t];
-                        } else if (g2.mse == b_mse) odd = true;
+                        else if (!b_have || g2.mse < b_mse) { b_have = true; b_mse = g2.mse; b_g = g2; b_r = r2; }
+                        else if (g2.mse == b_mse) odd = true;
                     }
                     bestm = wave_min_f64(b_have ? b_mse : BIG);
                     dbg_bigsolves++;
@@ -756,11 +764,21 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             for (int t = lane; t < W32; t += 64) bmp[t] = 0;
             GFENCE();
             const u64 eqm = __ballot(b_have && b_mse == bestm);
-            if (__ballot(odd) || __popcll(eqm) > 1) { fallback = true; dbg_prune_skip = 1; }
+            if (__ballot(odd) || __popcll(eqm) > 1) {
+                // the in-order path walks the bag in ascending node id; FAST ids are not in creation order: the exact kernel redoes the frame
+                if constexpr (FAST) err = ST_RETRY;
+                else { fallback = true; dbg_prune_skip = 1; }
+            }
             else {
                 const bool have = eqm != 0;
                 const int wl = have ? __ffsll((long long)eqm) - 1 : 0;
-                if (have && lane == wl) write_merged(p, b_ms, b_g);
+                if (have && lane == wl) {
+                    const double* sb = g_stats + (size_t)b_r * 9;
+                    double b_ms[9];
+#pragma unroll
+                    for (int t = 0; t < 9; t++) b_ms[t] = ps[t] + sb[t];
+                    write_merged(p, b_ms, b_g);
+                }
                 const double w_z = wave_lane(b_g.center[2], wl);
                 const unsigned w_nb = wave_lane(b_r, wl);
                 if (lane == 0) {
@@ -793,14 +811,14 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
 
     // ---- the queue of the initial blocks ----
     if constexpr (FAST) {
-        for (int b = lane; b < NB2; b += 64) {
+        for (int b = lane; b < NS; b += 64) {
             unsigned v = K_EMPTY;
             if (b < NB && (g_flags[b] & 1)) v = k_of(geo_of(b)[6], (int)(rec(b)[0] & 0x7fu));
             K[b] = v;
         }
         WFENCE();
         bool tie = false;
-        for (int i = lane; i < NB2; i += 64) {                 // every lane scans its own column
+        for (int i = lane; i < NS; i += 64) {                 // every lane scans its own column
             const unsigned v = K[i];
             const unsigned pv = kproxy(v), pc = kproxy(cm_v);
             if (pv < pc) { cm_v = v; cm_id = i; }
@@ -862,6 +880,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             PEAC_TICK(17);
         } else if (n > 0 && ((A.h.x >> 16) & 4u)) {
             eval_big(p, n, A.h.w);
+            if (err) break;
             GFENCE();
             A = load_rec(rp);
             n = (int)(A.h.x & 0xffffu);
@@ -886,8 +905,9 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             const int ridn = (int)(hB.z & 0xffffu);
             const unsigned offB = hB.w;
             PEAC_TICK(4);
-            const int m = n_nodes++;
-            if (m >= NB2) { err = 1; break; }
+            const int cm = n_nodes++;                               // creation id of the merged node
+            if (cm >= NB2) { err = 1; break; }
+            const int m = FAST ? p : cm;                            // its node id
             int nm;
             unsigned offM = 0;
             bool bigM = false;
@@ -986,21 +1006,28 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                 uint32_t* gg = (uint32_t*)(g_geo + (size_t)m * 7);
                 uint32_t* dstw = lane < 18 ? gs + lane : gg + (lane - 18);     // 18 dwords of moments, then centre and normal
                 if (lane < 30) *dstw = A.mw;
+                if constexpr (FAST) {                                          // ... and under its creation id
+                    uint32_t* os = (uint32_t*)(o_stats + (size_t)cm * 9);
+                    uint32_t* og = (uint32_t*)(o_geo + (size_t)cm * 7);
+                    uint32_t* dsto = lane < 18 ? os + lane : og + (lane - 18);
+                    if (lane < 30) *dsto = A.mw;
+                }
             }
             const int N100m = N100p + N100n;
             const int ridm = N100p >= N100n ? ridp : ridn;
             if (lane == 0) {
                 geo_of(m)[6] = A.mse;
                 g_N[m] = N100m * (WIN * WIN);
-                *(uint4*)rec(m) = make_uint4((uint32_t)nm | (bigM ? 4u << 16 : 0u), (uint32_t)N100m << 16, (uint32_t)ridm, offM);
-                h_rid[m] = (u16)ridm;
+                if constexpr (FAST) { o_geo[(size_t)cm * 7 + 6] = A.mse; o_N[cm] = N100m * (WIN * WIN); inval((unsigned)m); }   // (m is p: its record was valid)
+                *(uint4*)rec(m) = make_uint4((uint32_t)nm | (bigM ? 4u << 16 : 0u), (uint32_t)N100m << 16, (uint32_t)ridm | (uint32_t)cm << 16, offM);
+                h_rid[cm] = (u16)ridm;
                 // ds.Union(pa.rid, pb.rid) (DisjointSet.hpp:64-84): the rid of a live node is its set's root, so Find() returns its argument;
                 // union by size, size(root) * 100 == N of the live node whose rid it is
                 if (ridp != ridn) {
                     if (N100p < N100n) { h_dsp[ridp] = (u16)ridn; h_dss[ridn] = (u16)N100m; }
                     else { h_dsp[ridn] = (u16)ridp; h_dss[ridp] = (u16)N100m; }
                 }
-                mp[p] = (u16)m; mp[nb] = (u16)m;
+                mp[p] = (u16)m; mp[nb] = (u16)m;                        // (FAST: mp[p] stays p)
             }
             WFENCE();
             PEAC_TICK(9);
@@ -1043,13 +1070,27 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
     // ---- hand the clustering state over to peac_refine: set sizes / root ids / parents are in the workspace already; dead bits, extracted planes
     {
         unsigned* o_nouse = (unsigned*)(F + L.off_h_nouse); unsigned* o_cval = (unsigned*)(F + L.off_h_cval);
+        // dead bits by creation id
+        const int W32o = (NB2 + 31) / 32;
         for (int b0 = 0; b0 < NB2; b0 += 64) {
             const int id = b0 + lane;
-            const u64 dead = __ballot(id < NB2 && mp[id] != id);
-            if (lane == 0) { o_nouse[b0 >> 5] = (unsigned)dead; if ((b0 >> 5) + 1 < W32) o_nouse[(b0 >> 5) + 1] = (unsigned)(dead >> 32); }
+            bool dead;
+            if constexpr (FAST) {   // block b is alive when id b is and still names the block; merged nodes die below n_nodes (the live ones are revived next)
+                if (id < NB) dead = mp[id] != id || (rec(id)[2] >> 16) != (unsigned)id;
+                else dead = id < n_nodes;
+            } else dead = id < NB2 && mp[id] != id;
+            const u64 dm = __ballot(dead);
+            if (lane == 0) { o_nouse[b0 >> 5] = (unsigned)dm; if ((b0 >> 5) + 1 < W32o) o_nouse[(b0 >> 5) + 1] = (unsigned)(dm >> 32); }
         }
-        for (int t = lane; t < W32; t += 64) o_cval[t] = 0;
-        for (int t = lane; t < MAX_PLANES; t += 64) g_hand[4 + t] = t < n_ext ? s_ext[t] : 0;
+        if constexpr (FAST) {
+            GFENCE();
+            for (int id = lane; id < NB; id += 64) {
+                const unsigned c = rec(id)[2] >> 16;
+                if (mp[id] == id && c >= (unsigned)NB) atomicAnd(&o_nouse[c >> 5], ~(1u << (c & 31)));
+            }
+        }
+        for (int t = lane; t < (NB2 + 31) / 32; t += 64) o_cval[t] = 0;
+        for (int t = lane; t < MAX_PLANES; t += 64) g_hand[4 + t] = t < n_ext ? (FAST ? (int)(rec(s_ext[t])[2] >> 16) : s_ext[t]) : 0;
         if (lane == 0) {
             g_hand[0] = n_ext; g_hand[1] = err; g_hand[2] = n_nodes;
             status[frame] = err;
@@ -1067,20 +1108,22 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
 }
 
 // The fast attempt: every frame of the batch, taken from a start-order counter (longest first, see peac_order), not from the block index.
-// retry_inline: a frame the fast attempt gives up on (ST_RETRY) is redone with the exact heap by the same workgroup, which holds the LDS already - a separate
-// launch of the exact kernel over the batch would have to be granted 38 KB of LDS per workgroup just to find, almost always, nothing to do.
-__global__ __launch_bounds__(64) void peac_ahc3(Layout L, Consts C, uint8_t* __restrict__ ws, int32_t* __restrict__ status,
-                                                long long* __restrict__ timing, int* __restrict__ next_frame, const int* __restrict__ order, int retry_inline) {
+// A frame it gives up on (ST_RETRY) is redone with the exact heap: by the launch of peac_ahc2(only_retry = 1) that the library queues behind it on the
+// same stream (retry_inline = 0), or by the same workgroup (retry_inline != 0: the launch must then grant ahc2_smem_bytes of LDS, not ahc3_smem_bytes).
+// Two wavefronts per SIMD: the frame is a chain of dependent latencies (FP64 divide / sqrt, LDS round trips, readlane), which a second frame on the SIMD fills.
+__global__ __launch_bounds__(64, 2) void peac_ahc3(Layout L, Consts C, uint8_t* __restrict__ ws, int32_t* __restrict__ status,
+                                                   long long* __restrict__ timing, int* __restrict__ next_frame, const int* __restrict__ order, int retry_inline) {
     __shared__ int s_frame;
+    __shared__ AhcShared s_sh;
 #if defined(PLANAR_AHC_PRIO) && !defined(PLANAR_WAVE_EMUL)
     __builtin_amdgcn_s_setprio(PLANAR_AHC_PRIO);             // (experiment: issue priority of the clustering wavefront over the wide kernels' wavefronts on its SIMD)
 #endif
     if (threadIdx.x == 0) { const int k = atomicAdd(next_frame, 1); s_frame = order ? order[k] : k; }
     __syncthreads();
-    const int st = ahc_frame<true>(L, C, ws, status, timing, s_frame);
+    const int st = ahc_frame<true>(L, C, ws, status, timing, s_frame, s_sh);
     if (st == ST_RETRY && retry_inline) {
         __syncthreads();
-        ahc_frame<false>(L, C, ws, status, timing, s_frame);
+        ahc_frame<false>(L, C, ws, status, timing, s_frame, s_sh);
         if (timing && threadIdx.x == 0) timing[(size_t)s_frame * TSLOTS + 12] = 1;      // the frame went through both kernels
     }
 }
@@ -1088,13 +1131,14 @@ __global__ __launch_bounds__(64) void peac_ahc3(Layout L, Consts C, uint8_t* __r
 __global__ __launch_bounds__(64) void peac_ahc2(Layout L, Consts C, uint8_t* __restrict__ ws, int32_t* __restrict__ status,
                                                 long long* __restrict__ timing, int* __restrict__ next_frame, const int* __restrict__ order, int only_retry) {
     __shared__ int s_frame;
+    __shared__ AhcShared s_sh;
     if (threadIdx.x == 0) {
         if (only_retry) s_frame = status[blockIdx.x] == ST_RETRY ? (int)blockIdx.x : -1;
         else { const int k = atomicAdd(next_frame, 1); s_frame = order ? order[k] : k; }
     }
     __syncthreads();
     if (s_frame < 0) return;
-    ahc_frame<false>(L, C, ws, status, timing, s_frame);
+    ahc_frame<false>(L, C, ws, status, timing, s_frame, s_sh);
 }
 
 }  // namespace peac

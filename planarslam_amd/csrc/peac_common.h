@@ -151,7 +151,7 @@ __device__ void stats_compute(const double s[9], int N, Geo& g) {
 }
 
 struct Layout {   // per-frame workspace (element offsets), identical for every frame
-    int W, H, Nw, Nh, NB, NB2;   // NB2 = 2*NB: initial blocks + merged nodes
+    int W, H, Nw, Nh, NB, NB2;   // NB2 = 2*NB: initial blocks + merged nodes (creation ids)
     int pool_cap, q_cap;
     size_t off_stats, off_geo, off_N, off_flags, off_member, off_dist, off_queue, off_seedcnt, frame_bytes;
     // state the clustering kernel (peac_ahc) leaves for the refinement kernel (peac_refine): disjoint set, root ids, dead bits, extracted planes
@@ -234,7 +234,9 @@ static inline Layout make_layout(int width, int height) {
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o2 = off; off = (off + bytes + 255) / 256 * 256; return o2; };
     // (round 6: the regions only the round-2 clustering kernel used - its 32-bit lists and pool, its candidate cache, the 32-bit disjoint set: 1.26 MB per frame - are gone)
-    L.off_stats = carve((size_t)L.NB2 * 9 * 8); L.off_geo = carve((size_t)L.NB2 * 7 * 8); L.off_N = carve((size_t)L.NB2 * 4);
+    // moments / plane / N: NB2 nodes by creation id, then the NB node ids the fast clustering kernel works on (peac_ahc2.h)
+    const size_t NN = (size_t)L.NB2 + L.NB;
+    L.off_stats = carve(NN * 9 * 8); L.off_geo = carve(NN * 7 * 8); L.off_N = carve(NN * 4);
     L.off_flags = carve((size_t)L.NB2);
     L.off_member = carve((size_t)width * height + 4);
     L.off_dist = carve((size_t)width * height * 4); L.off_queue = carve((size_t)L.q_cap * 4);
