@@ -75,8 +75,12 @@ typedef unsigned long long u64;
 #ifdef PLANAR_WAVE_EMUL
 static int g_peac_check_prune = 0;
 #define PEAC_CHECK_PRUNE (g_peac_check_prune != 0)
+// and where the fast kernel gave up (ST_RETRY), bit s for site s: 0 bit-equal keys in the queue, 1 non-finite key, 2 tie inside a pooled bag, 3 MAX_STEP
+static unsigned g_peac_retry_sites = 0;
+#define PEAC_NOTE_RETRY(s) (g_peac_retry_sites |= 1u << (s))
 #else
 #define PEAC_CHECK_PRUNE false
+#define PEAC_NOTE_RETRY(s) ((void)0)
 #endif
 
 constexpr int ST_RETRY = 100;              // status of a frame the fast kernel gave up on (exact FP64 tie between live nodes): peac_ahc2 redoes it
@@ -312,7 +316,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                     const int i = base + Lc + 64 * lane;
                     for (u64 m = __ballot(i < NS && kproxy(K[min(i, NS - 1)]) == mn); m; m &= m - 1) pick_add(P, base + Lc + 64 * (__ffsll((long long)m) - 1));
                 }
-                if (P.tie) err = ST_RETRY;
+                if (P.tie) { err = ST_RETRY; PEAC_NOTE_RETRY(0); }
                 id = P.id;
             }
             v = K[id];
@@ -337,7 +341,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                 Pick P{-1, 0.0, false, false};
                 for (u64 m = e1; m; m &= m - 1) pick_add(P, Lc + 64 * (__ffsll((long long)m) - 1));
                 for (u64 m = e2; m; m &= m - 1) pick_add(P, Lc + 64 * (__ffsll((long long)m) - 1) + 4096);
-                if (P.tie) err = ST_RETRY;
+                if (P.tie) { err = ST_RETRY; PEAC_NOTE_RETRY(0); }
                 id = P.id; v = K[id];
             }
         }
@@ -353,7 +357,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         GFENCE();
         Pick P{-1, 0.0, false, false};
         for (u64 m = eq; m; m &= m - 1) pick_add(P, wave_lane(cm_id, __ffsll((long long)m) - 1));
-        if (P.tie) err = ST_RETRY;
+        if (P.tie) { err = ST_RETRY; PEAC_NOTE_RETRY(0); }
         return P.id;
     };
     auto pq_remove = [&](int id) {                            // id wave-uniform; its column is recomputed when it was the column's minimum
@@ -362,7 +366,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         if (wave_lane(cm_id, id & 63) == id) col_recompute(id & 63);
     };
     auto pq_push = [&](int id, double mse, int cnt) {
-        if (!(mse < 3.0e38) || !(mse > -3.0e38)) err = ST_RETRY;   // NaN / infinite key: leave it to the exact kernel
+        if (!(mse < 3.0e38) || !(mse > -3.0e38)) { err = ST_RETRY; PEAC_NOTE_RETRY(1); }   // NaN / infinite key: leave it to the exact kernel
         const unsigned v = k_of(mse, cnt);
         if (lane == 0) K[id] = v;
         WFENCE();
@@ -766,7 +770,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
             const u64 eqm = __ballot(b_have && b_mse == bestm);
             if (__ballot(odd) || __popcll(eqm) > 1) {
                 // the in-order path walks the bag in ascending node id; FAST ids are not in creation order: the exact kernel redoes the frame
-                if constexpr (FAST) err = ST_RETRY;
+                if constexpr (FAST) { err = ST_RETRY; PEAC_NOTE_RETRY(2); }
                 else { fallback = true; dbg_prune_skip = 1; }
             }
             else {
@@ -827,7 +831,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
                 if (a < b) { cm_v = v; cm_id = i; } else if (a == b) tie = true;
             }
         }
-        if (__ballot(tie)) err = ST_RETRY;
+        if (__ballot(tie)) { err = ST_RETRY; PEAC_NOTE_RETRY(0); }
     } else
     // heap of the initial blocks, in block order (:809)
     for (int b0 = 0; b0 < NB; b0 += 64) {
@@ -1048,7 +1052,7 @@ __device__ __forceinline__ int ahc_frame(const Layout& L, const Consts& C, uint8
         }
         ++step;
     }
-    if constexpr (FAST) { if (!err && step > MAX_STEP) err = ST_RETRY; }   // maxStep reached (never for NB <= 3072): the exact kernel knows what to do
+    if constexpr (FAST) { if (!err && step > MAX_STEP) { err = ST_RETRY; PEAC_NOTE_RETRY(3); } }   // maxStep reached (never for NB <= 3072): the exact kernel knows what to do
     while (!FAST && heap_n > 0 && !err) {                          // only after MAX_STEP: the reference extracts what is left without looking at nouse
         const int p = e_id(hp[0]);
         heap_pop();

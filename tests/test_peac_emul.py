@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import peac_cases as pc
 from planarslam_amd.synth import depth_image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,8 +35,8 @@ def libs():
     return E, O
 
 
-def _run(libs, d, mode=0):
-    E, O = libs
+def _cluster(E, d, mode):
+    """the emulated kernels on one frame, nothing checked but that the emulator ran: (nodes, hand, dsp, dss, nouse, stats) as peac_emul_cluster leaves them"""
     H, W = d.shape
     NB, NB2 = C.c_int(), C.c_int()
     E.peac_emul_dims(W, H, C.byref(NB), C.byref(NB2))
@@ -43,8 +44,17 @@ def _run(libs, d, mode=0):
     nodes = np.zeros((NB2, 18)); hand = np.zeros(132, np.int32); dsp = np.zeros(NB, np.uint16); dss = np.zeros(NB, np.uint16)
     nouse = np.zeros((NB2 + 31) // 32, np.uint32); st = np.zeros(8, np.int64)
     err = C.create_string_buffer(512)
+    d = np.ascontiguousarray(d, np.uint16)
     rc = E.peac_emul_cluster(d.ctypes.data, W, H, *K, mode, nodes.ctypes.data, hand.ctypes.data, dsp.ctypes.data, dss.ctypes.data, nouse.ctypes.data, st.ctypes.data, err, 512)
     assert rc == 0, err.value.decode()
+    return nodes, hand, dsp, dss, nouse, st
+
+
+def _run(libs, d, mode=0):
+    E, O = libs
+    H, W = d.shape
+    nodes, hand, dsp, dss, nouse, st = _cluster(E, d, mode)
+    NB, NB2 = len(dsp), len(nodes)
     onodes = np.zeros((NB2, 18)); oext = np.zeros(4096, np.int32); onext = C.c_int(); oroot = np.zeros(NB, np.int32); osize = np.zeros(NB, np.int32)
     n = O.orc_peac_cluster_state(d.ctypes.data, W, H, *K, onodes.ctypes.data, NB2, oext.ctypes.data, C.byref(onext), oroot.ctypes.data, osize.ctypes.data)
     assert st[0] == 0 and hand[1] == 0, f"kernel status {st[0]} / {hand[1]}"
@@ -62,7 +72,8 @@ def _run(libs, d, mode=0):
     assert np.array_equal(roots, oroot) and np.array_equal(dss[roots], osize), "DisjointSet partition differs"
     dead = np.array([(nouse[i >> 5] >> (i & 31)) & 1 for i in range(n)], bool)
     assert dead[live].all(), "a node of the graph is still marked alive after the clustering"
-    return dict(retried=bool(st[4]), phases=int(st[2] >> 40), evaluated=int((st[2] >> 20) & 0xFFFFF), hits=int(st[2] & 0xFFFFF), big=int(st[3]), big_solves=int(st[5]), nodes=int(n), planes=int(hand[0]))
+    return dict(retried=bool(st[4]), phases=int(st[2] >> 40), evaluated=int((st[2] >> 20) & 0xFFFFF), hits=int(st[2] & 0xFFFFF), big=int(st[3]), big_solves=int(st[5]), nodes=int(n), planes=int(hand[0]),
+                sites=int(st[6]))
 
 
 @pytest.mark.parametrize("w,h,seed,noise,holes", [(160, 120, 5, True, True), (320, 240, 77, True, True), (320, 240, 78, False, True), (640, 480, 4321, True, True),
@@ -120,3 +131,39 @@ def test_pruned_evaluation_of_big_bags_agrees_with_evaluating_everything(libs, s
     if noise:                                                         # the point of pruning: about one solve per node instead of one per 64 neighbours
         fast = _run(libs, depth_image(seed, 640, 480, noise=noise, holes=noise), mode=2)
         assert fast["big_solves"] < 1.5 * fast["big"], fast
+
+
+# where the fast kernel gave up (stats [6], bits of PEAC_NOTE_RETRY in peac_ahc2.h).  The non-finite-key site of pq_push is not reachable from a depth
+# image, so nothing here aims at it: a merged node is pushed only after its mse passed `mse < T_mse_merge(z)`, which NaN and +inf fail, and -inf would need
+# the moment sums (finite coordinates of at most W*H pixels) to overflow.
+SITE_QUEUE_TIE, SITE_POOLED_TIE = 1, 4
+
+
+@pytest.mark.parametrize("w,h", [(320, 240), (640, 480)])
+@pytest.mark.parametrize("name", sorted(pc.EDGE_RETRIED))
+def test_which_edge_frames_the_fast_kernel_hands_over(libs, name, w, h):
+    """the edge frames the GPU tests mix into their batches: the ones with bit-equal block mse (one wall, walls at constant depths) are handed to the
+    exact kernel, at the queue; the others are finished by the fast kernel (and all of them equal the oracle, _run)"""
+    info = _run(libs, pc.edge_frames(w, h)[name])
+    assert info["retried"] == pc.EDGE_RETRIED[name], info
+    assert info["sites"] == (SITE_QUEUE_TIE if pc.EDGE_RETRIED[name] else 0), info
+
+
+@pytest.mark.parametrize("i", range(len(pc.POOLED_TIE_320)))
+def test_a_tie_inside_a_pooled_bag_hands_the_frame_over(libs, i):
+    """eval_big: two candidates of a pooled bag with bit-equal merged mse; the fast kernel's bag order is not the reference's, so it gives the frame to
+    the exact kernel - there and nowhere else on these frames"""
+    info = _run(libs, pc.pooled_tie(i))
+    assert info["retried"] and info["big"] > 0 and info["sites"] == SITE_POOLED_TIE, info
+
+
+def test_more_than_max_planes_is_a_reported_status(libs):
+    """1280x720, 144 separated tilted patches of 3 600+ px: the reference extracts them all, the kernel holds MAX_PLANES = 128 and ends the clustering
+    with status 4 (planar_peac_check turns it into PLANAR_ECAPACITY)"""
+    import oracle_lib as ol
+    E, _ = libs
+    d = pc.many_planes()
+    op, _ = ol.peac_run(d, max_planes=256)
+    assert len(op) == 144
+    _, hand, _, _, _, st = _cluster(E, d, 0)
+    assert st[0] == 4 and hand[1] == 4 and hand[0] == 128 and not st[4], (st, hand[:4])

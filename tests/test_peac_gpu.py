@@ -130,3 +130,54 @@ def test_refinement_rare_paths_give_the_same_labels():
     for b in (len(GOLD) + 4, len(depths) - 1):                       # (and the product's are the oracle's on the SE3 frames too)
         op, olab = ol.peac_run(depths[b])
         assert np.array_equal(res[b][1], olab) and np.array_equal(res[b][0], op)
+
+
+def test_refinement_rare_paths_give_the_same_labels_in_peac_refine():
+    """The same check for peac_refine (256 threads per frame, 512 flood-fill entries per step: the kernel of batches above 64): the paranoid build's child
+    selects it with planar_peac_set_variant(wide_below = 0) and must take as many flood-fill steps as the product's peac_refine, which differ from the
+    wide kernel's on the larger frames (read_timing slot 7), and give the product's labels and planes (which equal the oracle's)."""
+    import subprocess
+    import sys
+    import tempfile
+    import peac_cases as pc
+    from planarslam_amd import PlaneDetection
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = os.path.join(root, "planarslam_amd", "libplanar_hip_paranoid.so")
+    if not os.path.exists(lib):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(root, "planarslam_amd", "csrc"), "paranoid"])
+    depths = [np.load(p)["depth"] for p in GOLD] + [depth_image(60 + i, noise=(i % 2 == 0), holes=(i % 3 != 0)) for i in range(4)]
+    depths += [pc.flat_wall(), pc.steps(), pc.ramp()]
+    depths = np.stack(depths)
+    B = len(depths)
+
+    def run(wide_below):
+        pd = PlaneDetection(640, 480, max_batch=B)
+        pc.set_variant(pd, 0, wide_below)
+        r = pd.run(depths)
+        t = np.zeros((B, 48), np.int64)
+        pd.L.planar_peac_read_timing(pd.h, B, t.ctypes.data)
+        return r, t[:, 7].copy()
+    res, steps = run(0)
+    _, steps_wide = run(1 << 30)
+    assert (steps != steps_wide).any()
+    for b in range(B):
+        op, olab = ol.peac_run(depths[b])
+        assert np.array_equal(res[b][1], olab) and np.array_equal(res[b][0], op), f"frame {b}"
+    with tempfile.TemporaryDirectory() as td:
+        np.save(os.path.join(td, "d.npy"), depths)
+        code = ("import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+                "from planarslam_amd import PlaneDetection\n"
+                "import peac_cases as pc\n"
+                "d = np.load(%r)\n"
+                "pd = PlaneDetection(640, 480, max_batch=len(d))\n"
+                "pc.set_variant(pd, 0, 0)\n"
+                "r = pd.run(d)\n"
+                "t = np.zeros((len(d), 48), np.int64); pd.L.planar_peac_read_timing(pd.h, len(d), t.ctypes.data)\n"
+                "np.savez(%r, labels=np.stack([x[1] for x in r]), n=np.array([len(x[0]) for x in r]), planes=np.concatenate([x[0] for x in r]), steps=t[:, 7])\n"
+                ) % (root, os.path.join(root, "tests"), os.path.join(td, "d.npy"), os.path.join(td, "o.npz"))
+        subprocess.check_call([sys.executable, "-W", "ignore", "-c", code], env=dict(os.environ, PLANAR_HIP_LIB=lib))
+        z = np.load(os.path.join(td, "o.npz"))
+    assert np.array_equal(z["steps"], steps), "the child did not run peac_refine"
+    assert np.array_equal(z["n"], [len(x[0]) for x in res])
+    assert np.array_equal(z["labels"], np.stack([x[1] for x in res]))
+    assert np.array_equal(z["planes"], np.concatenate([x[0] for x in res]))
