@@ -282,6 +282,36 @@ int planar_search_by_projection_map(planar_ctx* ctx, const planar_frame_view* fr
 int planar_search_by_projection_map_dev(planar_ctx* ctx, const planar_frame_view* d_frame, const planar_map_probes* d_probes, float th,
                                         float nn_ratio, int32_t* d_match, int32_t* d_nmatches);
 
+/* Key-frame side of ORBmatcher::SearchByProjection(Frame&, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+ * (src/ORBmatcher.cc:1537-1663), the relocalisation search.  Entry i is pKF->GetMapPointMatches()[i]. */
+typedef struct planar_keyframe_probes {
+    int32_t stride;
+    const int32_t* n;            /* [B]             vpMPs.size()                                             */
+    const uint8_t* usable;       /* [B][stride]     vpMPs[i] != NULL && !isBad()                             */
+    const uint8_t* found;        /* [B][stride]     sAlreadyFound.count(vpMPs[i]) (NULL = empty set)         */
+    const float* xw;             /* [B][stride][3]  GetWorldPos()                                            */
+    const float* min_dist;       /* [B][stride]     mfMinDistance (the 0.8 of GetMinDistanceInvariance is applied here) */
+    const float* max_dist;       /* [B][stride]     mfMaxDistance (1.2 of GetMaxDistanceInvariance; PredictScale reads it bare) */
+    const float* angle;          /* [B][stride]     pKF->mvKeysUn[i].angle                                   */
+    const uint8_t* desc;         /* [B][stride][32] GetDescriptor()                                          */
+} planar_keyframe_probes;
+
+/* ORBmatcher(nnratio, check_orientation)::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), batched over B (frame, key frame)
+ * pairs.  cur: keys_un, desc, Tcw, bounds, grid, fx fy cx cy, scale_factors are read; blocked[i2] = CurrentFrame.mvpMapPoints[i2] != NULL on
+ * entry (NULL = none); u_right is not read (this overload has no stereo gate).  log_scale_factor / n_levels = CurrentFrame.mfLogScaleFactor /
+ * mnScaleLevels (MapPoint::PredictScale, src/MapPoint.cc:419-434).  Kept as the reference has them: no depth test before the projection, no
+ * ratio test, bestDist starts at 256 and bestDist <= ORBdist decides; key-frame points are resolved in index order and a match is written into
+ * mvpMapPoints at once, so later points skip that keypoint; ComputeThreeMaxima's removal runs last.  orb_dist < 256 is required (the reference
+ * writes mvpMapPoints[-1] otherwise).
+ *   cur_match[b][i2] (in/out): key-frame index i of the map point the reference stores in CurrentFrame.mvpMapPoints[i2]; -1 where the rotation
+ *       check resets it to NULL; untouched otherwise.
+ *   nmatches[b]: the function's return value. */
+int planar_search_by_projection_keyframe(planar_ctx* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, float log_scale_factor,
+                                         int n_levels, float th, int orb_dist, int check_orientation, int32_t* cur_match, int32_t* nmatches);
+int planar_search_by_projection_keyframe_dev(planar_ctx* ctx, const planar_frame_view* d_cur, const planar_keyframe_probes* d_kf,
+                                             float log_scale_factor, int n_levels, float th, int orb_dist, int check_orientation,
+                                             int32_t* d_cur_match, int32_t* d_nmatches);
+
 /* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (src/ORBmatcher.cc:160-292).
  * The DBoW2 FeatureVectors (node id -> feature indices) are passed as one node id per feature (-1: feature
  * is in no node), which is what DBoW2's transform(..., levelsup) produces (each feature falls in one node).

@@ -77,6 +77,10 @@ class MapProbes(C.Structure):
                                                                    "observed")]
 
 
+class KeyframeProbes(C.Structure):
+    _fields_ = [("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "usable", "found", "xw", "min_dist", "max_dist", "angle", "desc")]
+
+
 class TrackMatches(C.Structure):
     _fields_ = [("B", C.c_int32), ("stride", C.c_int32), ("mp_stride", C.c_int32), ("n_levels", C.c_int32), ("n", C.c_void_p), ("keys_un", C.c_void_p),
                 ("u_right", C.c_void_p), ("pt_match", C.c_void_p), ("mp_xw", C.c_void_p), ("mp_valid", C.c_void_p), ("inv_level_sigma2", C.c_float * MAX_LEVELS),
@@ -129,6 +133,8 @@ _SIGS = {
     "planar_search_by_projection_frame_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(LastFrameView), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_projection_map": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(MapProbes), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "planar_search_by_projection_map_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(MapProbes), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "planar_search_by_projection_keyframe": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KeyframeProbes), C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_search_by_projection_keyframe_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KeyframeProbes), C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_fuse_search": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3),
     "planar_fuse_search_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3),
     "planar_lsd_fuse_search": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3),

@@ -2,6 +2,7 @@
 //
 //   planar_search_by_projection_frame   ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)  src/ORBmatcher.cc:1396-1535
 //   planar_search_by_projection_map     ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th)   src/ORBmatcher.cc:46-130
+//   planar_search_by_projection_keyframe ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)  src/ORBmatcher.cc:1537-1663
 //   planar_search_by_bow                ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...)                  src/ORBmatcher.cc:160-292
 //   planar_lsd_search_by_projection     LSDmatcher::SearchByProjection + Frame::GetLinesInArea           src/LSDmatcher.cpp:141-211, src/Frame.cc:491-524
 //   planar_plane_search_by_coefficients PlaneMatcher::SearchMapByCoefficients                           src/PlaneMatcher.cpp:10-79
@@ -31,7 +32,7 @@ constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
 constexpr int CAND_CAP = 8192;       // candidates of one chunk of probes; with it the workgroup needs 61 KB of LDS (two per CU)
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:38-40
 
-enum { MODE_FRAME = 0, MODE_MAP = 1, MODE_BOW = 2 };
+enum { MODE_FRAME = 0, MODE_MAP = 1, MODE_BOW = 2, MODE_KF = 3 };
 
 struct Lds {
     uint32_t cand[CAND_CAP];       // dist << 16 | octave << 12 | index ; doubles as scratch while the grid is built
@@ -133,8 +134,9 @@ __device__ void build_grid(L& s, const planar_frame_view& f, const planar_keypoi
 
 // Frame::GetFeaturesInArea (src/Frame.cc:440-489) + the per-candidate gates of the two SearchByProjection
 // loops that do not depend on the assignment state.  emit(idx, octave) is called in the reference's order.
-template <typename Emit>
-__device__ inline void walk_window(const Lds& s, const planar_frame_view& f, const planar_keypoint* keys, const float* uR, float x, float y,
+// STEREO = false: no mvuRight gate (the key-frame overload); uR / ur are then not read.
+template <bool STEREO = true, typename L, typename Emit>
+__device__ inline void walk_window(const L& s, const planar_frame_view& f, const planar_keypoint* keys, const float* uR, float x, float y,
                                    float r, int minLevel, int maxLevel, float ur, Emit emit) {
     const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.grid_w_inv));
     if (nMinCellX >= PLANAR_GRID_COLS) return;
@@ -158,10 +160,12 @@ __device__ inline void walk_window(const Lds& s, const planar_frame_view& f, con
             }
             const float distx = kp.x - x, disty = kp.y - y;
             if (!(fabsf(distx) < r && fabsf(disty) < r)) continue;
-            const float u2 = uR[idx];
-            if (u2 > 0) {
-                const float er = fabsf(ur - u2);
-                if (er > r) continue;
+            if (STEREO) {
+                const float u2 = uR[idx];
+                if (u2 > 0) {
+                    const float er = fabsf(ur - u2);
+                    if (er > r) continue;
+                }
             }
             emit(idx, kp.octave);
         }
@@ -182,6 +186,9 @@ struct Args {
     int mono, check_orientation;
     int32_t* match;
     int32_t* nmatches;
+    planar_keyframe_probes kf;     // MODE_KF
+    float lsf;
+    int n_levels, orb_dist;
 };
 
 // ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1666-1708) on bin counts
@@ -208,7 +215,8 @@ __device__ inline int rot_bin(float a_from, float a_to) {
 }
 
 // Order-bound part: wavefront 0 resolves probes [0, m) of the current chunk in order.
-//   MODE_FRAME: best only, TH_HIGH;  MODE_MAP: best + second with the same-level ratio test;  MODE_BOW: TH_LOW + ratio.
+//   MODE_FRAME: best only, TH_HIGH;  MODE_MAP: best + second with the same-level ratio test;  MODE_BOW: TH_LOW + ratio;
+//   MODE_KF: best only, ORBdist, and the match itself blocks the keypoint for later probes (src/ORBmatcher.cc:1609, :1623).
 template <int MODE>
 __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int b, const float* from_angle, const float* to_angle_f,
                               const planar_keypoint* keys, const uint8_t* observed) {
@@ -235,7 +243,7 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
         const uint32_t e1 = s.cand[off + bestK];
         const int bestIdx = e1 & 0xfff, bestLevel = (e1 >> 12) & 0xf;
         int bestDist2 = 256, bestLevel2 = -1;
-        if (MODE != MODE_FRAME) {
+        if (MODE != MODE_FRAME && MODE != MODE_KF) {
             uint32_t k2 = 0xffffffffu;
             for (int base = 0; base < cnt; base += 64) {
                 const int k = base + lane;
@@ -256,16 +264,17 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
         bool take;
         if (MODE == MODE_FRAME) take = bestDist <= TH_HIGH;
         else if (MODE == MODE_MAP) take = bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > a.nn_ratio * (float)bestDist2);
+        else if (MODE == MODE_KF) take = bestDist <= a.orb_dist;
         else take = bestDist <= TH_LOW && (float)bestDist < a.nn_ratio * (float)bestDist2;
         if (!take) continue;
         if (lane == 0) {
             match[bestIdx] = id;
-            const bool now_blocked = MODE == MODE_BOW ? true : (observed[id] != 0);
+            const bool now_blocked = (MODE == MODE_BOW || MODE == MODE_KF) ? true : (observed[id] != 0);
             const uint32_t w = blk[bestIdx >> 5], bit = 1u << (bestIdx & 31);
             blk[bestIdx >> 5] = now_blocked ? (w | bit) : (w & ~bit);
             s.nmatches++;
             if (MODE != MODE_MAP && a.check_orientation) {
-                const float to = MODE == MODE_FRAME ? keys[bestIdx].angle : to_angle_f[bestIdx];
+                const float to = MODE == MODE_BOW ? to_angle_f[bestIdx] : keys[bestIdx].angle;
                 const int n = s.n_ev++;
                 s.ev_idx[n] = (uint16_t)bestIdx;
                 s.ev_bin[n] = (uint8_t)rot_bin(from_angle[id], to);
@@ -300,6 +309,39 @@ __device__ void rotation_filter(Lds& s, int32_t* match) {
     }
 }
 
+// rotation_filter with ComputeThreeMaxima ranked on the lanes (MODE_KF).  Its strict-'>' insertion keeps the three largest non-empty bins in
+// stable order, which is rank < 3 under (count descending, bin ascending); the serial ind1..ind3 form lives in scratch.
+__device__ void rotation_filter_ranked(Lds& s, int32_t* match) {
+    const int tid = threadIdx.x;
+    if (tid < HISTO_LENGTH) s.hist[tid] = 0;
+    if (tid < 3) s.keep[tid] = -1;
+    __syncthreads();
+    const int n = s.n_ev;
+    for (int i = tid; i < n; i += NT) atomicAdd(&s.hist[s.ev_bin[i]], 1);
+    __syncthreads();
+    if (tid < HISTO_LENGTH && s.hist[tid] > 0) {
+        const int h = s.hist[tid];
+        int rank = 0;
+        for (int j = 0; j < HISTO_LENGTH; j++) { const int hj = s.hist[j]; rank += (hj > h || (hj == h && j < tid)) ? 1 : 0; }
+        if (rank < 3) s.keep[rank] = tid;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int i1 = s.keep[0], i2 = s.keep[1], i3 = s.keep[2];
+        const int max1 = i1 >= 0 ? s.hist[i1] : 0, max2 = i2 >= 0 ? s.hist[i2] : 0, max3 = i3 >= 0 ? s.hist[i3] : 0;
+        const bool k2 = !((float)max2 < 0.1f * (float)max1), k3 = k2 && !((float)max3 < 0.1f * (float)max1);
+        if (!k2) s.keep[1] = -1;
+        if (!k3) s.keep[2] = -1;
+        s.nmatches -= n - (max1 + (k2 ? max2 : 0) + (k3 ? max3 : 0));     // every event sits in one bin; max1..3 read 0 for a missing bin
+    }
+    __syncthreads();
+    const int k1 = s.keep[0], k2 = s.keep[1], k3 = s.keep[2];
+    for (int i = tid; i < n; i += NT) {
+        const int bin = s.ev_bin[i];
+        if (bin != k1 && bin != k2 && bin != k3) match[s.ev_idx[i]] = -1;
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
@@ -322,7 +364,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     }
 
     // per-frame constants of the frame-to-frame variant (src/ORBmatcher.cc:1408-1420)
-    float Rcw[9], tcw[3];
+    float Rcw[9], tcw[3], Ow[3];
     bool bForward = false, bBackward = false;
     size_t po;
     int NP;
@@ -344,6 +386,19 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
         NP = a.last.n[b];
         probe_desc = a.last.mp_desc + po * 32;
         observed = a.last.mp_observed + po;
+    } else if (MODE == MODE_KF) {
+        // Ow = -Rcw.t()*tcw (src/ORBmatcher.cc:1541-1543), the same product as the frame variant's twc
+        const float* Tc = f.Tcw + (size_t)b * 16;
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcw[3 * r + c] = Tc[4 * r + c]; tcw[r] = Tc[4 * r + 3]; }
+        for (int i = 0; i < 3; i++) {
+            double sum = 0;
+            for (int k = 0; k < 3; k++) sum += (double)Rcw[3 * k + i] * (double)tcw[k];
+            Ow[i] = (float)(sum * -1.0);
+        }
+        po = (size_t)b * a.kf.stride;
+        NP = a.kf.n[b];
+        probe_desc = a.kf.desc + po * 32;
+        observed = nullptr;
     } else {
         po = (size_t)b * a.mp.stride;
         NP = a.mp.n[b];
@@ -381,6 +436,29 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
                         }
                     }
                 }
+            } else if (MODE == MODE_KF) {
+                if (a.kf.usable[po + p] && !(a.kf.found && a.kf.found[po + p])) {                       // :1558
+                    const float* X = a.kf.xw + (po + p) * 3;
+                    const float xc = gemm3_row(Rcw[0], Rcw[1], Rcw[2], X, tcw[0]);
+                    const float yc = gemm3_row(Rcw[3], Rcw[4], Rcw[5], X, tcw[1]);
+                    const float zc = gemm3_row(Rcw[6], Rcw[7], Rcw[8], X, tcw[2]);
+                    const float invzc = (float)(1.0 / (double)zc);                                      // no depth test in this overload
+                    u = f.fx * xc * invzc + f.cx;
+                    v = f.fy * yc * invzc + f.cy;
+                    if (!(u < f.min_x || u > f.max_x) && !(v < f.min_y || v > f.max_y)) {
+                        const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
+                        const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);   // cv::norm
+                        const float maxDistance = 1.2f * a.kf.max_dist[po + p], minDistance = 0.8f * a.kf.min_dist[po + p];
+                        if (!(dist3D < minDistance || dist3D > maxDistance)) {
+                            const float ratio = a.kf.max_dist[po + p] / dist3D;                        // MapPoint::PredictScale (src/MapPoint.cc:419-434)
+                            int lvl = (int)ceilf((float)log((double)ratio) / a.lsf);
+                            if (lvl < 0) lvl = 0; else if (lvl >= a.n_levels) lvl = a.n_levels - 1;
+                            r = a.th * f.scale_factors[lvl];
+                            minL = lvl - 1; maxL = lvl + 1;
+                            valid = true;
+                        }
+                    }
+                }
             } else {
                 if (a.mp.in_view[po + p]) {
                     const int lvl = a.mp.level[po + p];
@@ -394,7 +472,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             }
         }
         int cnt = 0;
-        if (valid) walk_window(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
+        if (valid) walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
         int total;
         const int off = block_exscan(cnt, s.wsum, &total);
         if (tid == 0) s.m_fit = 0;
@@ -410,18 +488,20 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             uint32_t d[8];
             load_desc(d, probe_desc + (size_t)p * 32);
             int k = off;
-            walk_window(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int idx, int oct) {
+            walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int idx, int oct) {
                 const int dist = hamming256(d, desc + (size_t)idx * 32);
                 s.cand[k++] = ((uint32_t)dist << 16) | ((uint32_t)(oct & 0xf) << 12) | (uint32_t)idx;
             });
         }
         __syncthreads();
         // ---- order-bound
-        if (tid < 64) resolve_chunk<MODE>(s, m, a, match_b, b, MODE == MODE_FRAME ? a.last.angle + po : nullptr, nullptr, keys, observed);
+        const float* from_angle = MODE == MODE_FRAME ? a.last.angle + po : MODE == MODE_KF ? a.kf.angle + po : nullptr;
+        if (tid < 64) resolve_chunk<MODE>(s, m, a, match_b, b, from_angle, nullptr, keys, observed);
         __syncthreads();
         base += m;
     }
     if (MODE == MODE_FRAME && a.check_orientation) rotation_filter(s, match_b);
+    if (MODE == MODE_KF && a.check_orientation) rotation_filter_ranked(s, match_b);
     __syncthreads();
     if (tid == 0) a.nmatches[b] = s.nmatches;
 }
@@ -1073,6 +1153,54 @@ int planar_search_by_projection_map(planar_ctx* ctx, const planar_frame_view* fr
     dp.n = s.dev<int32_t>(p0); dp.in_view = s.dev<uint8_t>(p1); dp.proj_x = s.dev<float>(p2); dp.proj_y = s.dev<float>(p3); dp.proj_xr = s.dev<float>(p4);
     dp.level = s.dev<int32_t>(p5); dp.view_cos = s.dev<float>(p6); dp.desc = s.dev<uint8_t>(p7); dp.observed = s.dev<uint8_t>(p8);
     rc = planar_search_by_projection_map_dev(ctx, &df, &dp, th, nn_ratio, s.dev<int32_t>(om), s.dev<int32_t>(on));
+    if (rc) return rc;
+    return s.download(ctx->stream);
+}
+
+static int check_keyframe_args(const planar_frame_view* cur, const planar_keyframe_probes* kf, int n_levels, int orb_dist) {
+    int rc = guided::check_view(cur);
+    if (rc) return rc;
+    PLANAR_REQUIRE(cur->Tcw && kf->n && kf->usable && kf->xw && kf->min_dist && kf->max_dist && kf->angle && kf->desc, PLANAR_EINVAL, "null array in view");
+    PLANAR_REQUIRE(kf->stride >= 1, PLANAR_EINVAL, "key-frame stride out of range");
+    PLANAR_REQUIRE(n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL, "n_levels out of range");
+    PLANAR_REQUIRE(orb_dist < 256, PLANAR_EINVAL, "orb_dist >= 256 (the reference would write mvpMapPoints[-1])");
+    return PLANAR_OK;
+}
+
+int planar_search_by_projection_keyframe_dev(planar_ctx* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, float log_scale_factor,
+                                             int n_levels, float th, int orb_dist, int check_orientation, int32_t* d_cur_match, int32_t* d_nmatches) {
+    PLANAR_REQUIRE(ctx && cur && kf && d_cur_match && d_nmatches, PLANAR_EINVAL, "null argument");
+    int rc = check_keyframe_args(cur, kf, n_levels, orb_dist);
+    if (rc) return rc;
+    Args a{};
+    a.f = *cur; a.kf = *kf; a.lsf = log_scale_factor; a.th = th; a.n_levels = n_levels; a.orb_dist = orb_dist;
+    a.check_orientation = check_orientation; a.match = d_cur_match; a.nmatches = d_nmatches;
+    return guided::launch_projection<guided::MODE_KF>(ctx, a);
+}
+
+int planar_search_by_projection_keyframe(planar_ctx* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, float log_scale_factor,
+                                         int n_levels, float th, int orb_dist, int check_orientation, int32_t* cur_match, int32_t* nmatches) {
+    PLANAR_REQUIRE(ctx && cur && kf && cur_match && nmatches, PLANAR_EINVAL, "null argument");
+    int rc = check_keyframe_args(cur, kf, n_levels, orb_dist);
+    if (rc) return rc;
+    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
+    Stager s;
+    int ix[6];
+    stage_view(s, cur, true, ix);
+    const int B = cur->B;
+    const size_t np = (size_t)B * kf->stride;
+    const int k0 = s.in(kf->n, (size_t)B * 4), k1 = s.in(kf->usable, np), k2 = kf->found ? s.in(kf->found, np) : -1, k3 = s.in(kf->xw, np * 12),
+              k4 = s.in(kf->min_dist, np * 4), k5 = s.in(kf->max_dist, np * 4), k6 = s.in(kf->angle, np * 4), k7 = s.in(kf->desc, np * 32);
+    const int om = s.inout(cur_match, (size_t)B * cur->stride * 4), on = s.out(nmatches, (size_t)B * 4);
+    rc = s.upload(ctx->stream);
+    if (rc) return rc;
+    planar_frame_view dc = *cur;
+    patch_view(s, &dc, ix);
+    planar_keyframe_probes dk = *kf;
+    dk.n = s.dev<int32_t>(k0); dk.usable = s.dev<uint8_t>(k1); dk.found = k2 >= 0 ? s.dev<uint8_t>(k2) : nullptr; dk.xw = s.dev<float>(k3);
+    dk.min_dist = s.dev<float>(k4); dk.max_dist = s.dev<float>(k5); dk.angle = s.dev<float>(k6); dk.desc = s.dev<uint8_t>(k7);
+    rc = planar_search_by_projection_keyframe_dev(ctx, &dc, &dk, log_scale_factor, n_levels, th, orb_dist, check_orientation, s.dev<int32_t>(om),
+                                                  s.dev<int32_t>(on));
     if (rc) return rc;
     return s.download(ctx->stream);
 }

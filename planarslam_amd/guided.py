@@ -2,6 +2,7 @@
 
     ORBmatcher.SearchByProjection(CurrentFrame, LastFrame, th, bMono)   reference src/ORBmatcher.cc:1396 (include/ORBmatcher.h:45)
     ORBmatcher.SearchByProjection(F, vpMapPoints, th)                   reference src/ORBmatcher.cc:46   (include/ORBmatcher.h:41)
+    ORBmatcher.SearchByProjection(F, pKF, sAlreadyFound, th, ORBdist)    reference src/ORBmatcher.cc:1537 (include/ORBmatcher.h:57)
     ORBmatcher.SearchByBoW(pKF, F, vpMapPointMatches)                   reference src/ORBmatcher.cc:160  (include/ORBmatcher.h:59)
     ORBmatcher.Fuse(pKF, vpMapPoints, th), the search half              reference src/ORBmatcher.cc:829  (include/ORBmatcher.h:81)
     LSDmatcher.SearchByProjection(F, vpMapLines, th)                    reference src/LSDmatcher.cpp:141
@@ -16,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import KEYLINE_DTYPE, KP_DTYPE, MAX_LEVELS, Context, FrameView, LastFrameView, MapProbes, check, lib
+from ._lib import KEYLINE_DTYPE, KP_DTYPE, MAX_LEVELS, Context, FrameView, KeyframeProbes, LastFrameView, MapProbes, check, lib
 
 
 def _c(a, dt):
@@ -70,6 +71,25 @@ def map_probes(d: dict):
     return v, keep
 
 
+def keyframe_probes(d: dict):
+    """dict -> (planar_keyframe_probes, keepalive).  Keys: n[B], usable[B,S], optional found[B,S], xw[B,S,3], min_dist[B,S], max_dist[B,S]
+    (mfMinDistance / mfMaxDistance), angle[B,S] (pKF->mvKeysUn[i].angle), desc[B,S,32]."""
+    keep = dict(n=_c(d["n"], np.int32), usable=_c(d["usable"], np.uint8), xw=_c(d["xw"], np.float32), min_dist=_c(d["min_dist"], np.float32),
+                max_dist=_c(d["max_dist"], np.float32), angle=_c(d["angle"], np.float32), desc=_c(d["desc"], np.uint8))
+    if d.get("found") is not None:
+        keep["found"] = _c(d["found"], np.uint8)
+    v = KeyframeProbes()
+    v.stride = keep["usable"].shape[1]
+    for k, a in keep.items():
+        setattr(v, k, a.ctypes.data)
+    return v, keep
+
+
+def _log_scale_factor(frame: dict) -> float:
+    # Frame::mfLogScaleFactor = log(mfScaleFactor) (src/Frame.cc), float
+    return float(np.float32(np.log(np.float32(np.asarray(frame["scale_factors"], np.float32)[1]))))
+
+
 class ORBmatcher:
     """Guided half of ORBmatcher (the brute-force half lives in matcher.ORBmatcher)."""
 
@@ -95,6 +115,21 @@ class ORBmatcher:
         m = np.full((fv.B, fv.stride), -1, np.int32) if match is None else _c(match, np.int32).copy()
         nm = np.zeros(fv.B, np.int32)
         check(lib().planar_search_by_projection_map(self.ctx.h, C.byref(fv), C.byref(pv), th, self.mfNNratio, m.ctypes.data, nm.ctypes.data))
+        return m, nm
+
+    def SearchByProjectionKeyFrame(self, cur: dict, kf: dict, th: float, ORBdist: int, log_scale_factor: float | None = None,
+                                   n_levels: int | None = None, cur_match=None):
+        """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), the relocalisation search.  cur: a frame dict with Tcw and
+        blocked (CurrentFrame.mvpMapPoints[i2] != NULL on entry); kf: see keyframe_probes (found = membership in sAlreadyFound).
+        Returns (cur_match [B,S] = key-frame index per current keypoint / -1, nmatches [B])."""
+        fv, k1 = frame_view(cur)
+        kv, k2 = keyframe_probes(kf)
+        nl = n_levels or len(cur["scale_factors"])
+        lsf = _log_scale_factor(cur) if log_scale_factor is None else log_scale_factor
+        m = np.full((fv.B, fv.stride), -1, np.int32) if cur_match is None else _c(cur_match, np.int32).copy()
+        nm = np.zeros(fv.B, np.int32)
+        check(lib().planar_search_by_projection_keyframe(self.ctx.h, C.byref(fv), C.byref(kv), lsf, nl, th, int(ORBdist), int(self.mbCheckOrientation),
+                                                         m.ctypes.data, nm.ctypes.data))
         return m, nm
 
     def SearchByBoW(self, kf: dict, f: dict):
