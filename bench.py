@@ -16,10 +16,11 @@ Inputs: per rank 256 distinct synthetic RGB-D canvases (736 x 576), resident in 
 that pans a few pixels per step (consecutive frames of a stream overlap like video, every step shows every stream a NEW frame).  The window
 copy (a strided device-to-device copy) is inside the timed region.  Steps are software-pipelined `--depth` deep: the tracking chain of step
 i - depth runs behind the extraction launches of step i.  Every one of the K timed steps is complete before the closing barrier.
-Frames are independent, so ranks shard them with no data-path collective ("scaling": "weak").  Rank 0 prints ONE JSON line: whole-job frames/s,
-per-stage times, the roofline of the dominant stage (HIP events on the stream it runs on, inside the timed region), a CPU baseline (the
-oracle restatement of the same stages on all host cores, one thread and the reference's three extraction threads), the single-frame latency and the
-PCIe-inclusive rate.  --workload orb restricts the step to BASELINE config[1] (ORB only)."""
+Frames are independent, so ranks shard them with no data-path collective ("scaling": "weak").  Rank 0 prints ONE JSON line: whole-job frames/s and
+per-stage times.  A plain run does nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full the line
+also carries the roofline of the dominant kernel (HIP events on the stream it runs on, inside the timed region, and calibration launches of its own), the
+parity sample, a CPU baseline (the oracle restatement of the same stages on all host cores, one thread and the reference's three extraction threads),
+the single-frame latency, the PCIe-inclusive rate and the sub-benchmarks.  --workload orb restricts the step to BASELINE config[1] (ORB only)."""
 import argparse
 import json
 import os
@@ -110,17 +111,19 @@ def track_outputs(tp, k, B):
     from numpy.lib.recfunctions import structured_to_unstructured
     from planarslam_amd._lib import KEYLINE_DTYPE
     s = dump_streams(B)
+    si = tp.torch.as_tensor(s, device=tp.dev)
     g = lambda x: x.cpu().numpy()
+    gs = lambda x: x[si].cpu().numpy()          # the sampled streams only, picked on the device (every stream's label image alone is 1.2 MB)
     n, nl, npl, pc = g(tp.n[k]), g(tp.nl[k]), g(tp.npl[k]), tp.pc[k]
     npc, off = g(pc["n"]), g(pc["off"])
-    kl = structured_to_unstructured(g(tp.kls[k]).view(KEYLINE_DTYPE).reshape(B, 40)[s], np.float64)
+    kl = structured_to_unstructured(gs(tp.kls[k].view(B, -1)).view(KEYLINE_DTYPE).reshape(len(s), 40), np.float64)
     A0, A1 = tp.pb_arrays
     return {"sample_streams": s,
-            "orb_count": n, "orb_keypoints": upto(keypoints(g(tp.kps[k])[s]), n[s]), "orb_descriptors": upto(g(tp.desc[k])[s], n[s]),
-            "line_count": nl, "line_keylines": upto(kl, nl[s]), "line_descriptors": upto(g(tp.ldesc[k])[s], nl[s]), "line_equations": upto(g(tp.leq[k])[s], nl[s]),
-            "plane_count": npl, "planes": upto(g(tp.pls[k])[s], npl[s]), "plane_labels": g(tp.lab[k])[s].reshape(len(s), tp.H, tp.W),
-            "plane_kept_count": npc, "plane_coefficients": upto(g(pc["coef"])[s], npc[s]), "plane_source": upto(g(pc["src"])[s], npc[s]),
-            "plane_point_offsets": upto(off[s], npc[s] + 1), "plane_points": upto(g(pc["pts"])[s], off[s, npc[s]]),
+            "orb_count": n, "orb_keypoints": upto(keypoints(gs(tp.kps[k])), n[s]), "orb_descriptors": upto(gs(tp.desc[k]), n[s]),
+            "line_count": nl, "line_keylines": upto(kl, nl[s]), "line_descriptors": upto(gs(tp.ldesc[k]), nl[s]), "line_equations": upto(gs(tp.leq[k]), nl[s]),
+            "plane_count": npl, "planes": upto(gs(tp.pls[k]), npl[s]), "plane_labels": gs(tp.lab[k]).reshape(len(s), tp.H, tp.W),
+            "plane_kept_count": npc, "plane_coefficients": upto(gs(pc["coef"]), npc[s]), "plane_source": upto(gs(pc["src"]), npc[s]),
+            "plane_point_offsets": upto(off[s], npc[s] + 1), "plane_points": upto(gs(pc["pts"]), off[s, npc[s]]),
             "point_matches_last_frame": tp.nm, "point_matches_local_map": tp.nmm, "line_matches": g(tp.lm)[s], "plane_matches": tp.nplm,
             "translation_opt_Tcw": A0["Tcw_out"], "translation_opt_inliers": A0["n_inliers"], "pose_opt_Tcw": A1["Tcw_out"], "pose_opt_inliers": A1["n_inliers"],
             "pose_opt_lm_iterations": A1["lm_iters"], "Tcw": tp.pose}
@@ -197,11 +200,14 @@ def main():
                                                                 "CU-masked side stream (planar_ctx_set_seq_stream); 0 = no partition")
     ap.add_argument("--seq-which", type=int, default=SEQ_WHICH, help="which of them: 1 PEAC clustering, 2 LSD region growing (on the same stream when shared), 3 both, 4 LSD region growing on a masked stream per line context, 5 = 1 + 4")
     ap.add_argument("--seq-per-ctx", action="store_true", help="one masked stream per context instead of one shared by all sets")
-    ap.add_argument("--cpu-seconds", type=float, default=18.0, help="budget of the cpu_baseline leg, split over its three variants (0 = skip)")
-    ap.add_argument("--latency-reps", type=int, default=15, help="repetitions of the B = 1 pose-optimisation call (0 = skip the whole latency block)")
-    ap.add_argument("--latency-frames", type=int, default=200, help="distinct frames of the B = 1 latency block (4/5 se3 frames, 1/5 panned canvas windows)")
-    ap.add_argument("--sub-steps", type=int, default=20, help="steps of the BASELINE configs[1] / [3] / [4] sub-runs folded into the default line as sub_benchmarks (0 = skip)")
-    ap.add_argument("--pcie-steps", type=int, default=4, help="steps of the PCIe-inclusive loop (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the calibration launches and the roofline, "
+                                                         "the parity sample, the PCIe-inclusive loop, the CPU baseline, the B = 1 latency block and the sub-benchmarks "
+                                                         "(--workload pose: the 1 x 10 protocol and the CPU baseline; ba: the CPU baseline)")
+    ap.add_argument("--cpu-seconds", type=float, default=18.0, help="--full: budget of the cpu_baseline leg, split over its three variants (0 = skip)")
+    ap.add_argument("--latency-reps", type=int, default=15, help="--full: repetitions of the B = 1 pose-optimisation call (0 = skip the whole latency block)")
+    ap.add_argument("--latency-frames", type=int, default=200, help="--full: distinct frames of the B = 1 latency block (4/5 se3 frames, 1/5 panned canvas windows)")
+    ap.add_argument("--sub-steps", type=int, default=20, help="--full: steps of the BASELINE configs[1] / [3] / [4] sub-runs folded into the line as sub_benchmarks (0 = skip)")
+    ap.add_argument("--pcie-steps", type=int, default=4, help="--full: steps of the PCIe-inclusive loop (0 = skip)")
     ap.add_argument("--canvases", type=int, default=NCANVAS, help="distinct synthetic canvases (pan) / room scenes with their textures (se3) per GPU (the streams tile over them)")
     ap.add_argument("--streams", choices=["se3", "pan"], default="se3",
                     help="se3: every stream is a camera moving through a textured box room - gray and depth of every frame ray-cast from the same SE3 pose "
@@ -363,7 +369,7 @@ def main():
             step(i)
         if full: tp.drain()
         standalone = {}
-        if full:   # calibration: each sequential extractor alone on the device (not part of the timed region)
+        if full and args.full:   # calibration: each sequential extractor alone on the device (not part of the timed region)
             pd0, ls0 = tp.pds[0], tp.lss[0]
             for name, fn in (("peac_alone_ms", lambda: pd0.segment_dev(depths[0].data_ptr(), tp.lab[0].data_ptr(), tp.pls[0].data_ptr(), tp.npl[0].data_ptr(), B)),
                              ("lsd_lbd_alone_ms", lambda: check(L.planar_lsd_extract_dev(ls0.h, frames[0].data_ptr(), B, W, W * H, 40, tp.kls[0].data_ptr(),
@@ -438,7 +444,7 @@ def main():
     parity = None
     if full:
         tp.check()
-        if PARITY_SAMPLE and rank_env == 0:
+        if PARITY_SAMPLE and args.full and rank_env == 0:
             parity = parity_sample(tp, frames, depths, (args.warmup + args.steps - 1) % NB, B, TUM3)
     if args.dump_outputs and rank_env == 0:     # before the PCIe loop and the sub-benchmarks reuse the buffers
         if full:
@@ -467,32 +473,10 @@ def main():
 
     fps = whole_job_fps(world, B, args.steps, elapsed)
     avg_kp = n_kp / B
-    kernels = {k: {"ms_per_step": round(v[0] / max(1, calls), 4), "launches_per_step": v[1] // max(1, calls)} for k, v in prof.items()}
-    alg = orb_algorithmic_bytes(ex, avg_kp)
     quality = None
     t_pc_pts = lambda q: torch.gather(q.pc[0]["off"], 1, q.pc[0]["n"].long().unsqueeze(1)).float().mean().item()     # pt_off[b][n[b]] = voxel centroids kept
     if full:
-        # PEAC: read u16 depth + write int32 labels (1 843 200 B/frame); peac_blocks + peac_ahc + peac_order + peac_refine bracketed together
-        pk = "peac_blocks+peac_ahc+peac_refine"
-        pav = peac_ms / max(1, peac_calls)          # average duration of each launch, HIP events tight around it (co-run: other streams share the CUs)
-        kernels[pk] = {"ms_per_step": round(float(pav.sum()), 4), "launches_per_step": 4, "alone_ms": standalone["peac_alone_ms"],
-                       "avg_launch_ms": {"peac_blocks": round(float(pav[0]), 3), "peac_ahc": round(float(pav[1]), 3), "peac_order": round(float(pav[2]), 3),
-                                         "peac_refine": round(float(pav[3]), 3)},
-                       "stream_bracket_ms": round(stage_ms["peac(stream 2)"], 3),
-                       "note": "avg_launch_ms: HIP events right before / after each launch on the PEAC stream, inside the timed region (what rocprofv3's AverageNs measures); "
-                               "stream_bracket_ms also holds the surface-normal kernel and the queueing between launches with up to depth+2 launch sets in flight"}
-        # plane clouds (Frame::ComputePlanes head): read labels + depth (1 843 200 B / frame), write <= 4096 centroids; its launches bracketed one by one
-        ck = "plane_clouds(voxels+items+sort+tail)"
-        cav = pc_ms / max(1, pc_calls)
-        kernels[ck] = {"ms_per_step": round(float(cav.sum()), 4), "launches_per_step": 8, "alone_ms": standalone["plane_clouds_alone_ms"],
-                       "avg_launch_ms": dict(zip(PC_SLOTS, (round(float(x), 3) for x in cav))), "alone_launch_ms": standalone["plane_clouds_kernels_alone_ms"],
-                       "sort_stats_of_the_calibration_batch": standalone["plane_sort_stats"]}
-        lk = "lsd_detect(+7 small kernels)"
-        kernels[lk] = {"ms_per_step": round(stage_ms["lsd_lbd(stream 3)"], 4), "launches_per_step": 8, "alone_ms": standalone["lsd_lbd_alone_ms"]}
-        kernels["projection_kernel"] = {"ms_per_step": round(stage_ms["search_by_projection_last"], 4), "launches_per_step": 1}
         A1 = tp.pb_arrays[1]
-        lm_it = float(A1["lm_iters"].float().mean().item())
-        kernels["pose_opt_kernel"] = {"ms_per_step": round(stage_ms["assemble+pose_opt_4x10"], 4), "launches_per_step": 2, "avg_lm_iterations": round(lm_it, 2)}
         quality = {"avg_planes_per_frame": round(float(tp.npl[0].float().mean().item()), 2), "avg_planes_kept_per_frame": round(float(tp.pc[0]["n"].float().mean().item()), 2),
                    "avg_plane_cloud_points_per_frame": round(float(t_pc_pts(tp)), 1), "avg_lines_per_frame": round(float(tp.nl[0].float().mean().item()), 2),
                    "avg_projection_matches_per_frame": round(float(tp.nm.float().mean().item()), 1),
@@ -502,103 +486,128 @@ def main():
                    "avg_translation_opt_inliers": round(float(tp.pb_arrays[0]["n_inliers"].float().mean().item()), 1),
                    "avg_pose_opt_inliers": round(float(A1["n_inliers"].float().mean().item()), 1)}
     ms_per_step = elapsed / args.steps * 1e3
-    # ---- roofline: ONE KERNEL, the one with the most device time per step.  Durations: HIP events right before / after each launch on the stream the kernel runs on,
-    #      inside the timed region (co-run with the other streams: what rocprofv3's AverageNs of the same command measures), and the same launch alone on the device
-    #      (calibration launch before the timed region: rocprofv3's Min).  Bytes: SURVEY §8d's algorithmic figure of the kernel's stage x frames per launch. ----
-    per = {}
+    roofline = None
+    if args.full or not full:        # (the full workload picks its kernel by the times of the calibration launches: --full)
+        kernels = {k: {"ms_per_step": round(v[0] / max(1, calls), 4), "launches_per_step": v[1] // max(1, calls)} for k, v in prof.items()}
+        alg = orb_algorithmic_bytes(ex, avg_kp)
+        if full:
+            # PEAC: read u16 depth + write int32 labels (1 843 200 B/frame); peac_blocks + peac_ahc + peac_order + peac_refine bracketed together
+            pk = "peac_blocks+peac_ahc+peac_refine"
+            pav = peac_ms / max(1, peac_calls)          # average duration of each launch, HIP events tight around it (co-run: other streams share the CUs)
+            kernels[pk] = {"ms_per_step": round(float(pav.sum()), 4), "launches_per_step": 4, "alone_ms": standalone["peac_alone_ms"],
+                           "avg_launch_ms": {"peac_blocks": round(float(pav[0]), 3), "peac_ahc": round(float(pav[1]), 3), "peac_order": round(float(pav[2]), 3),
+                                             "peac_refine": round(float(pav[3]), 3)},
+                           "stream_bracket_ms": round(stage_ms["peac(stream 2)"], 3),
+                           "note": "avg_launch_ms: HIP events right before / after each launch on the PEAC stream, inside the timed region (what rocprofv3's AverageNs measures); "
+                                   "stream_bracket_ms also holds the surface-normal kernel and the queueing between launches with up to depth+2 launch sets in flight"}
+            # plane clouds (Frame::ComputePlanes head): read labels + depth (1 843 200 B / frame), write <= 4096 centroids; its launches bracketed one by one
+            ck = "plane_clouds(voxels+items+sort+tail)"
+            cav = pc_ms / max(1, pc_calls)
+            kernels[ck] = {"ms_per_step": round(float(cav.sum()), 4), "launches_per_step": 8, "alone_ms": standalone["plane_clouds_alone_ms"],
+                           "avg_launch_ms": dict(zip(PC_SLOTS, (round(float(x), 3) for x in cav))), "alone_launch_ms": standalone["plane_clouds_kernels_alone_ms"],
+                           "sort_stats_of_the_calibration_batch": standalone["plane_sort_stats"]}
+            lk = "lsd_detect(+7 small kernels)"
+            kernels[lk] = {"ms_per_step": round(stage_ms["lsd_lbd(stream 3)"], 4), "launches_per_step": 8, "alone_ms": standalone["lsd_lbd_alone_ms"]}
+            kernels["projection_kernel"] = {"ms_per_step": round(stage_ms["search_by_projection_last"], 4), "launches_per_step": 1}
+            lm_it = float(A1["lm_iters"].float().mean().item())
+            kernels["pose_opt_kernel"] = {"ms_per_step": round(stage_ms["assemble+pose_opt_4x10"], 4), "launches_per_step": 2, "avg_lm_iterations": round(lm_it, 2)}
+        # ---- roofline: ONE KERNEL, the one with the most device time per step.  Durations: HIP events right before / after each launch on the stream the kernel runs on,
+        #      inside the timed region (co-run with the other streams: what rocprofv3's AverageNs of the same command measures), and the same launch alone on the device
+        #      (calibration launch before the timed region: rocprofv3's Min).  Bytes: SURVEY §8d's algorithmic figure of the kernel's stage x frames per launch. ----
+        per = {}
 
-    def add_kernel(name, rocprof, corun, alone, nbytes, launches=1):
-        e = {"rocprof_name": rocprof, "alg_bytes_per_launch": int(nbytes), "corun_avg_ms": round(float(corun), 3), "alone_ms": None if alone is None else round(float(alone), 3),
-             "launches_per_step": launches}
-        if corun > 0: e["frac_corun"] = round(nbytes / (corun * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)
-        if alone: e["frac_alone"] = round(nbytes / (alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)
-        per[name] = e
-    for k, v in prof.items():                                  # the ORB kernels (per-launch events of the extractor): average over their launches
-        add_kernel(k, "planar::orb::" + k, v[0] / max(1, v[1]), None, alg.get(k, 0) * B, v[1] // max(1, calls))
-    if full:
-        lav = lsd_ms / max(1, lsd_calls)
-        ka, la, ca = standalone.get("peac_kernels_alone_ms", {}), standalone.get("lsd_kernels_alone_ms", {}), standalone["plane_clouds_kernels_alone_ms"]
-        add_kernel("peac_blocks", "planar::peac::peac_blocks", pav[0], ka.get("peac_blocks"), 614400 * B)
-        add_kernel("peac_ahc3", "planar::peac::peac_ahc3", pav[1], ka.get("peac_ahc"), 1843200 * B)
-        add_kernel("peac_refine", "planar::peac::peac_refine", pav[3], ka.get("peac_refine"), 1843200 * B)
-        add_kernel("lsd_sort(4 launches)", "planar::lsd::lsd_sort", lav[1], la.get("lsd_sort"), 312160 * B, 4)
-        add_kernel("lsd_detect", "planar::lsd::lsd_detect", lav[2], la.get("lsd_detect"), 312160 * B)
-        for i, nm in enumerate(PC_SLOTS):
-            add_kernel(nm, "planar::planepost::" + nm + ("" if nm.startswith("plane_sort") else "_kernel"), cav[i], ca.get(nm), 1843200 * B, 2 if nm == "plane_sort_heap" else 1)
-    # "most device time": the launch's duration ALONE on the device where the calibration measured it (the co-run brackets of the wide kernels mostly measure how long a
-    # launch queued for CUs behind the other streams - lsd_sort's four launches: 4.7 ms alone, 100 ms of brackets); the ORB-only workload has only the live averages
-    dev_time = lambda k: (per[k]["alone_ms"] if per[k]["alone_ms"] else 0.0) if full else per[k]["corun_avg_ms"] * per[k]["launches_per_step"]
-    dom = max(per, key=dev_time)
-    dom_ms, dom_bytes = per[dom]["corun_avg_ms"], per[dom]["alg_bytes_per_launch"]
-    if dom_ms > ms_per_step:
-        print(f"bench.py: WARNING: the HIP-event bracket of {dom} ({dom_ms:.1f} ms) exceeds the step ({ms_per_step:.1f} ms): launches of several steps overlap on its stream", file=sys.stderr)
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    # algorithmic bytes of the whole step per frame: ORB; + PEAC (depth in, labels out) + normals; + plane clouds (labels + depth in); + matchers + the two pose problems
-    # (65 130 B per LM evaluation x the MEASURED evaluations of both optimisers)
-    lm_both = (float(tp.pb_arrays[0]["lm_iters"].float().mean().item()) + float(tp.pb_arrays[1]["lm_iters"].float().mean().item())) if full else 0.0
-    per_frame = 1961064 + ((1843200 + 312160) + 1843200 + 72000 + 118000 + 65130 * lm_both if full else 0)
-    # HBM-side traffic of that kernel from the committed rocprofv3 PMC passes (separate --pmc FETCH_SIZE and --pmc WRITE_SIZE runs of this command, KB per launch;
-    # raw counter sums); a kernel without a row is reported as null with the reason, never as zero
-    traffic = None
-    pmc_csv = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_fetch_write_kb_per_launch.csv") for r in (6, 5, 4, 3, 2)) if os.path.exists(q)), "")
-    traffic_note = "null: no profiles/r0N_pmc_fetch_write_kb_per_launch.csv (tools/pmc_counters.py) found"
-    if os.path.exists(pmc_csv):
-        f_tot = w_tot = 0.0
-        for ln in open(pmc_csv).read().splitlines()[1:]:
-            k, _, f_kb, w_kb = ln.rsplit(",", 3)
-            if k.strip('"').replace("void ", "").startswith(per[dom]["rocprof_name"]):
-                f_tot += float(f_kb); w_tot += float(w_kb)
-        if f_tot + w_tot > 0:
-            traffic = int((f_tot + w_tot) * 1024 * B / 1024)                      # (the counter passes run B = 1024: scaled to this run's frames per launch)
-            traffic_note = (f"NOT measured in this run: read from the committed {os.path.relpath(pmc_csv, ROOT)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of "
-                            f"`bench.py --canvases 16 --gen-procs 1`, B=1024; counter collection hangs in forked children): {f_tot / 1024:.0f} MB read + {w_tot / 1024:.0f} MB written per launch")
-        else:
-            traffic_note = f"null: {os.path.relpath(pmc_csv, ROOT)} has no row for {per[dom]['rocprof_name']} (re-collect with tools/collect_profiles.sh)"
-            print(f"bench.py: WARNING: roofline.traffic not reported: {traffic_note}", file=sys.stderr)
-    # the lens that fits this path (no dense contraction, L2-resident working sets): instruction issue.  issue_frac = (4 x VALU + SALU wavefront-instructions) / (launch
-    # duration x 1024 SIMDs x 2.4 GHz), active / wait = share of the wavefronts' resident time with an instruction in flight / waiting for one; from the committed SQ
-    # counter passes (tools/pmc_counters.py: B = 1024, every launch alone on the device, no CU partition), like `traffic`
-    issue = None
-    sq_csv = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_sq_per_launch.csv") for r in (6, 5)) if os.path.exists(q)), "")
-    if os.path.exists(sq_csv):
-        import csv as _csv
-        rows = list(_csv.DictReader(open(sq_csv)))
-        def _issue(rn):
-            for r_ in rows:
-                if r_["kernel"].replace("void ", "").startswith(rn) and r_.get("issue_frac") not in (None, "", "nan"):
-                    return {"issue_frac": float(r_["issue_frac"]), "active": float(r_["active"]), "wait": float(r_["wait"]), "valu_winst_per_launch": int(float(r_["SQ_INSTS_VALU"])),
-                            "salu_winst_per_launch": int(float(r_["SQ_INSTS_SALU"])), "alone_us_per_launch_b1024": float(r_["avg_duration_us"])}
-            return None
-        issue = _issue(per[dom]["rocprof_name"])
-        if issue:
-            issue["source"] = os.path.relpath(sq_csv, ROOT)
-            issue["note"] = ("NOT measured in this run: committed rocprofv3 --pmc passes (SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVE_CYCLES / SQ_ACTIVE_INST_ANY / SQ_WAIT_INST_ANY, "
-                             "launches of 1024 frames alone on the device); issue_frac = (4 VALU + SALU) / (duration x 1024 SIMDs x 2.4 GHz)")
-        for k_, v_ in per.items():
-            q_ = _issue(v_["rocprof_name"])
-            if q_: v_["issue_frac"] = q_["issue_frac"]; v_["active"] = q_["active"]
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                "traffic": traffic, "traffic_source": os.path.relpath(pmc_csv, ROOT) if traffic is not None else None, "traffic_note": traffic_note,
-                "issue": issue,
-                "avg_launch_ms": round(dom_ms, 4), "alone_ms": per[dom]["alone_ms"], "frac_alone": per[dom].get("frac_alone"), "algorithmic_bytes_per_launch": int(dom_bytes),
-                "pipeline_algorithmic_GBps": round(per_frame * fps / 1e9, 2), "algorithmic_bytes_per_frame_of_the_step": int(per_frame),
-                "note": ("one kernel (the one with the most device time per step), not a stage: avg_launch_ms = HIP events right before / after each of its launches on its own stream "
-                         "inside the timed region (co-run with the other streams; rocprofv3's AverageNs of the same command), alone_ms = the same launch alone on the device "
-                         "(rocprofv3's Min).  peac_ahc3 / lsd_detect: one sequential wavefront per frame, latency-bound (DESIGN.md §4)"),
-                "per_kernel": per, "stages": kernels}
-    if full and args.seq_cus and (args.seq_which & 1) and dom == "peac_ahc3":
-        roofline["cu_partition"] = {"kernel_confined_to_cus": args.seq_cus, "of": 256,
-                                    "note": ("this kernel runs on a CU-masked side stream (planar_ctx_set_seq_stream): its launches take 256 / %d times longer than on the whole device - by "
-                                             "design, the other CUs run the wide kernels meanwhile - so `frac` (bytes / duration / 8 TB/s of the WHOLE device) is that much lower than "
-                                             "with --seq-cus 0; alone_ms is measured on the same mask") % args.seq_cus,
-                                    "frac_relative_to_its_share_of_hbm": round(achieved / HBM_PEAK_GBS * 256.0 / args.seq_cus, 6)}
-    if full:
-        roofline["per_kernel_note"] = ("co-run >> alone for the wide kernels: up to depth + 2 steps are in flight and every kernel waits for CUs behind the other streams' launches; "
-                                       "the single-wavefront kernels of the two side chains stretch when other wavefronts share their SIMDs (tools/corun_probe.py; DESIGN.md)")
+        def add_kernel(name, rocprof, corun, alone, nbytes, launches=1):
+            e = {"rocprof_name": rocprof, "alg_bytes_per_launch": int(nbytes), "corun_avg_ms": round(float(corun), 3), "alone_ms": None if alone is None else round(float(alone), 3),
+                 "launches_per_step": launches}
+            if corun > 0: e["frac_corun"] = round(nbytes / (corun * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)
+            if alone: e["frac_alone"] = round(nbytes / (alone * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)
+            per[name] = e
+        for k, v in prof.items():                                  # the ORB kernels (per-launch events of the extractor): average over their launches
+            add_kernel(k, "planar::orb::" + k, v[0] / max(1, v[1]), None, alg.get(k, 0) * B, v[1] // max(1, calls))
+        if full:
+            lav = lsd_ms / max(1, lsd_calls)
+            ka, la, ca = standalone.get("peac_kernels_alone_ms", {}), standalone.get("lsd_kernels_alone_ms", {}), standalone["plane_clouds_kernels_alone_ms"]
+            add_kernel("peac_blocks", "planar::peac::peac_blocks", pav[0], ka.get("peac_blocks"), 614400 * B)
+            add_kernel("peac_ahc3", "planar::peac::peac_ahc3", pav[1], ka.get("peac_ahc"), 1843200 * B)
+            add_kernel("peac_refine", "planar::peac::peac_refine", pav[3], ka.get("peac_refine"), 1843200 * B)
+            add_kernel("lsd_sort(4 launches)", "planar::lsd::lsd_sort", lav[1], la.get("lsd_sort"), 312160 * B, 4)
+            add_kernel("lsd_detect", "planar::lsd::lsd_detect", lav[2], la.get("lsd_detect"), 312160 * B)
+            for i, nm in enumerate(PC_SLOTS):
+                add_kernel(nm, "planar::planepost::" + nm + ("" if nm.startswith("plane_sort") else "_kernel"), cav[i], ca.get(nm), 1843200 * B, 2 if nm == "plane_sort_heap" else 1)
+        # "most device time": the launch's duration ALONE on the device where the calibration measured it (the co-run brackets of the wide kernels mostly measure how long a
+        # launch queued for CUs behind the other streams - lsd_sort's four launches: 4.7 ms alone, 100 ms of brackets); the ORB-only workload has only the live averages
+        dev_time = lambda k: (per[k]["alone_ms"] if per[k]["alone_ms"] else 0.0) if full else per[k]["corun_avg_ms"] * per[k]["launches_per_step"]
+        dom = max(per, key=dev_time)
+        dom_ms, dom_bytes = per[dom]["corun_avg_ms"], per[dom]["alg_bytes_per_launch"]
+        if dom_ms > ms_per_step:
+            print(f"bench.py: WARNING: the HIP-event bracket of {dom} ({dom_ms:.1f} ms) exceeds the step ({ms_per_step:.1f} ms): launches of several steps overlap on its stream", file=sys.stderr)
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        # algorithmic bytes of the whole step per frame: ORB; + PEAC (depth in, labels out) + normals; + plane clouds (labels + depth in); + matchers + the two pose problems
+        # (65 130 B per LM evaluation x the MEASURED evaluations of both optimisers)
+        lm_both = (float(tp.pb_arrays[0]["lm_iters"].float().mean().item()) + float(tp.pb_arrays[1]["lm_iters"].float().mean().item())) if full else 0.0
+        per_frame = 1961064 + ((1843200 + 312160) + 1843200 + 72000 + 118000 + 65130 * lm_both if full else 0)
+        # HBM-side traffic of that kernel from the committed rocprofv3 PMC passes (separate --pmc FETCH_SIZE and --pmc WRITE_SIZE runs of this command, KB per launch;
+        # raw counter sums); a kernel without a row is reported as null with the reason, never as zero
+        traffic = None
+        pmc_csv = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_fetch_write_kb_per_launch.csv") for r in (6, 5, 4, 3, 2)) if os.path.exists(q)), "")
+        traffic_note = "null: no profiles/r0N_pmc_fetch_write_kb_per_launch.csv (tools/pmc_counters.py) found"
+        if os.path.exists(pmc_csv):
+            f_tot = w_tot = 0.0
+            for ln in open(pmc_csv).read().splitlines()[1:]:
+                k, _, f_kb, w_kb = ln.rsplit(",", 3)
+                if k.strip('"').replace("void ", "").startswith(per[dom]["rocprof_name"]):
+                    f_tot += float(f_kb); w_tot += float(w_kb)
+            if f_tot + w_tot > 0:
+                traffic = int((f_tot + w_tot) * 1024 * B / 1024)                      # (the counter passes run B = 1024: scaled to this run's frames per launch)
+                traffic_note = (f"NOT measured in this run: read from the committed {os.path.relpath(pmc_csv, ROOT)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of "
+                                f"`bench.py --canvases 16 --gen-procs 1`, B=1024; counter collection hangs in forked children): {f_tot / 1024:.0f} MB read + {w_tot / 1024:.0f} MB written per launch")
+            else:
+                traffic_note = f"null: {os.path.relpath(pmc_csv, ROOT)} has no row for {per[dom]['rocprof_name']} (re-collect with tools/collect_profiles.sh)"
+                print(f"bench.py: WARNING: roofline.traffic not reported: {traffic_note}", file=sys.stderr)
+        # the lens that fits this path (no dense contraction, L2-resident working sets): instruction issue.  issue_frac = (4 x VALU + SALU wavefront-instructions) / (launch
+        # duration x 1024 SIMDs x 2.4 GHz), active / wait = share of the wavefronts' resident time with an instruction in flight / waiting for one; from the committed SQ
+        # counter passes (tools/pmc_counters.py: B = 1024, every launch alone on the device, no CU partition), like `traffic`
+        issue = None
+        sq_csv = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_sq_per_launch.csv") for r in (6, 5)) if os.path.exists(q)), "")
+        if os.path.exists(sq_csv):
+            import csv as _csv
+            rows = list(_csv.DictReader(open(sq_csv)))
+            def _issue(rn):
+                for r_ in rows:
+                    if r_["kernel"].replace("void ", "").startswith(rn) and r_.get("issue_frac") not in (None, "", "nan"):
+                        return {"issue_frac": float(r_["issue_frac"]), "active": float(r_["active"]), "wait": float(r_["wait"]), "valu_winst_per_launch": int(float(r_["SQ_INSTS_VALU"])),
+                                "salu_winst_per_launch": int(float(r_["SQ_INSTS_SALU"])), "alone_us_per_launch_b1024": float(r_["avg_duration_us"])}
+                return None
+            issue = _issue(per[dom]["rocprof_name"])
+            if issue:
+                issue["source"] = os.path.relpath(sq_csv, ROOT)
+                issue["note"] = ("NOT measured in this run: committed rocprofv3 --pmc passes (SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVE_CYCLES / SQ_ACTIVE_INST_ANY / SQ_WAIT_INST_ANY, "
+                                 "launches of 1024 frames alone on the device); issue_frac = (4 VALU + SALU) / (duration x 1024 SIMDs x 2.4 GHz)")
+            for k_, v_ in per.items():
+                q_ = _issue(v_["rocprof_name"])
+                if q_: v_["issue_frac"] = q_["issue_frac"]; v_["active"] = q_["active"]
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                    "traffic": traffic, "traffic_source": os.path.relpath(pmc_csv, ROOT) if traffic is not None else None, "traffic_note": traffic_note,
+                    "issue": issue,
+                    "avg_launch_ms": round(dom_ms, 4), "alone_ms": per[dom]["alone_ms"], "frac_alone": per[dom].get("frac_alone"), "algorithmic_bytes_per_launch": int(dom_bytes),
+                    "pipeline_algorithmic_GBps": round(per_frame * fps / 1e9, 2), "algorithmic_bytes_per_frame_of_the_step": int(per_frame),
+                    "note": ("one kernel (the one with the most device time per step), not a stage: avg_launch_ms = HIP events right before / after each of its launches on its own stream "
+                             "inside the timed region (co-run with the other streams; rocprofv3's AverageNs of the same command), alone_ms = the same launch alone on the device "
+                             "(rocprofv3's Min).  peac_ahc3 / lsd_detect: one sequential wavefront per frame, latency-bound (DESIGN.md §4)"),
+                    "per_kernel": per, "stages": kernels}
+        if full and args.seq_cus and (args.seq_which & 1) and dom == "peac_ahc3":
+            roofline["cu_partition"] = {"kernel_confined_to_cus": args.seq_cus, "of": 256,
+                                        "note": ("this kernel runs on a CU-masked side stream (planar_ctx_set_seq_stream): its launches take 256 / %d times longer than on the whole device - by "
+                                                 "design, the other CUs run the wide kernels meanwhile - so `frac` (bytes / duration / 8 TB/s of the WHOLE device) is that much lower than "
+                                                 "with --seq-cus 0; alone_ms is measured on the same mask") % args.seq_cus,
+                                        "frac_relative_to_its_share_of_hbm": round(achieved / HBM_PEAK_GBS * 256.0 / args.seq_cus, 6)}
+        if full:
+            roofline["per_kernel_note"] = ("co-run >> alone for the wide kernels: up to depth + 2 steps are in flight and every kernel waits for CUs behind the other streams' launches; "
+                                           "the single-wavefront kernels of the two side chains stretch when other wavefronts share their SIMDs (tools/corun_probe.py; DESIGN.md)")
 
     # ---- PCIe-inclusive rate: the same step fed from pinned host memory and drained to it (H2D / D2H on copy streams, overlapped) ----
     pcie = None
-    if full and world == 1 and args.pcie_steps > 0:
+    if args.full and full and world == 1 and args.pcie_steps > 0:
         h_g = [torch.empty((B, H, W), dtype=torch.uint8).pin_memory() for _ in range(NB)]
         h_d = [torch.empty((B, H, W), dtype=torch.int16).pin_memory() for _ in range(NB)]
         for k in range(NB):
@@ -650,7 +659,7 @@ def main():
 
     # ---- CPU baseline: the oracle restatement of the same stages on this box's host cores (tools/cpu_baseline.py) ----
     cpu = None
-    if args.cpu_seconds > 0 and world == 1:        # rank 0 at N = 1 only
+    if args.full and args.cpu_seconds > 0 and world == 1:        # rank 0 at N = 1 only
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import cpu_baseline as cb
         cb.use_fast_build()                          # -O3 -march=native, compiled on this box (the tests keep checking against the -O2 build)
@@ -673,7 +682,7 @@ def main():
     #      PoseOptimization; over `--latency-frames` DISTINCT frames (se3 frames of different streams, then panned canvas windows: the regime with heap-sort fallbacks),
     #      each frame timed once after an untimed pass of the first frames: p50 / p99 / max ----
     latency = None
-    if world == 1 and full and args.latency_reps > 0:
+    if args.full and world == 1 and full and args.latency_reps > 0:
         from planarslam_amd.lines import LineSegment as LS1
         from planarslam_amd.lines import is_line_good as ilg1
         from planarslam_amd.matcher import ORBmatcher as OM1
@@ -752,9 +761,9 @@ def main():
                                 "(src/Frame.cc:90-95): points | lines + isLineGood | PEAC + voxel clouds / refit + normals, each on its own host thread, context and stream"})
 
     # ---- sub_benchmarks: BASELINE configs[1] (ORB only), configs[3] (pose-only LM, B = 256) and configs[4] (local BA) as short sub-runs of THIS command, each with its
-    #      own roofline and cpu_baseline, so that the driver's default invocation carries a number for every BASELINE config that fits one GPU ----
+    #      own roofline and cpu_baseline, so that the --full line carries a number for every BASELINE config that fits one GPU ----
     sub = None
-    if full and world == 1 and args.sub_steps > 0:
+    if args.full and full and world == 1 and args.sub_steps > 0:
         sub = {}
         cpu_s = min(args.cpu_seconds, 6.0)
         # configs[1]: the pipeline's own extractor on the resident streams, window copy included (== `--workload orb`)
@@ -833,7 +842,7 @@ def main_ba(args):
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     ranks = Ranks(backend=args.backend, device=dev)
-    line = ba_line(args.steps, args.warmup, args.cpu_seconds, args.backend, ranks, local_rank, dev, dump=args.dump_outputs)
+    line = ba_line(args.steps, args.warmup, args.cpu_seconds if args.full else 0, args.backend, ranks, local_rank, dev, dump=args.dump_outputs)
     if line is not None:
         print(json.dumps(line))
     ranks.close()
@@ -946,18 +955,18 @@ def main_pose(args):
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     ranks = Ranks(backend=args.backend, device=dev)
-    line = pose_line(args.steps, args.warmup, args.cpu_seconds, args.batch, ranks, local_rank, dev, dump=args.dump_outputs)
+    line = pose_line(args.steps, args.warmup, args.cpu_seconds if args.full else 0, args.batch, ranks, local_rank, dev, dump=args.dump_outputs, protocol_1x10=args.full)
     if line is not None:
         print(json.dumps(line))
     ranks.close()
 
 
-def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev, dump=None):
+def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev, dump=None, protocol_1x10=True):
     """BASELINE configs[3]: pose-only Levenberg-Marquardt, 1000 point + 150 line (75 lines x 2 end points) + 12 plane (4 planes x plane / parallel / vertical)
     edges per frame, batch = 256 frames per GPU (synth.pose_batch(B = 256, seed = 7 + 1000 * rank)), resident in HBM.  A step = Optimizer::PoseOptimization
     (src/Optimizer.cc:550-1275: four rounds of optimize(10) with outlier reclassification) for every frame of the batch: one launch of pose_opt_kernel.  Frames are
     independent: every rank has its own batch, no collective ("weak").  Returns the line on rank 0.  dump: directory of --dump-outputs (rank 0 writes the
-    last 4 x optimize(10) launch's outputs there)."""
+    last 4 x optimize(10) launch's outputs there).  protocol_1x10: first time one optimize(10) per launch as well (config.protocol_1x10)."""
     import ctypes as C
     import types
 
@@ -1005,7 +1014,8 @@ def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev, dump=No
             barrier()
             return ranks.max_over_ranks(time.perf_counter() - t0), e0.elapsed_time(e1) / steps, float(d["lm_iters"].float().mean().item())
 
-    el_1, k_1, it_1 = run(1, 10, args.steps, args.warmup)        # one optimize(10): the "10 iters" protocol of BASELINE.md
+    if protocol_1x10:
+        el_1, k_1, it_1 = run(1, 10, args.steps, args.warmup)    # one optimize(10): the "10 iters" protocol of BASELINE.md
     el, k_ms, lm_it = run(4, 10, args.steps, args.warmup)         # the reference's PoseOptimization: 4 x optimize(10)
     if dump and rank == 0:
         dump_outputs(dump, {k: d[k] for k in ("Tcw_out", "n_inliers", "lm_iters", "pt_outlier", "ln_outlier", "pl_outlier")})
@@ -1019,7 +1029,8 @@ def pose_line(steps, warmup, cpu_seconds, batch, ranks, local_rank, dev, dump=No
             "config": {"workload": "BASELINE configs[3] (0-based): pose-only LM, synth.pose_batch(B=%d, n_points=1000, n_lines=75 (150 end-point edges), n_planes=4 (12 plane / parallel / "
                                    "vertical edges), seed=7), Optimizer::PoseOptimization = 4 rounds of optimize(10) with outlier reclassification; inputs resident in HBM" % B,
                        "frames_per_gpu_per_step": B, "avg_lm_iterations_per_frame": round(lm_it, 2),
-                       "protocol_1x10": {"problems_per_s": round(B * world * args.steps / el_1, 1), "ms_per_step": round(el_1 / args.steps * 1e3, 4), "avg_lm_iterations_per_frame": round(it_1, 2)}},
+                       "protocol_1x10": {"problems_per_s": round(B * world * args.steps / el_1, 1), "ms_per_step": round(el_1 / args.steps * 1e3, 4), "avg_lm_iterations_per_frame": round(it_1, 2)}
+                                        if protocol_1x10 else None},
             "roofline": {"bound": "hbm", "kernel": "pose_opt_kernel", "achieved": round(alg / (k_ms * 1e-3) / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6), "traffic": None, "avg_launch_ms": round(k_ms, 4), "algorithmic_bytes_per_launch": int(alg),
                          "note": "65 130 B per frame per LM evaluation (SURVEY §8d) x the measured LM iterations; HIP events on the kernel's stream around the timed launches.  One workgroup per "

@@ -1,5 +1,6 @@
 """`bench.py --dump-outputs DIR`: what the timed path computed in its last step, written as .npy files after the timed region.  Two runs with the same
-arguments write the same arrays; one more timed step changes them (the last step is a different frame of every stream)."""
+arguments write the same arrays; one more timed step changes them (the last step is a different frame of every stream); a plain run (no --full) writes
+what a --full run writes."""
 import json
 import os
 import subprocess
@@ -10,7 +11,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ("--batch", "32", "--canvases", "8", "--warmup", "1", "--cpu-seconds", "0", "--latency-reps", "0", "--pcie-steps", "0", "--sub-steps", "0")
+PLAIN = ("--batch", "32", "--canvases", "8", "--warmup", "1")
+SMALL = PLAIN + ("--full", "--cpu-seconds", "0", "--latency-reps", "0", "--pcie-steps", "0", "--sub-steps", "0")
 
 
 def _bench(out, *flags, timeout=600):
@@ -27,7 +29,7 @@ def _load(d):
 
 
 def test_full_workload_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
-    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    a, b, c, p = tmp_path / "a", tmp_path / "b", tmp_path / "c", tmp_path / "p"
     da = _bench(a, "--steps", "2", *SMALL)
     _bench(b, "--steps", "2", *SMALL)
     dc = _bench(c, "--steps", "3", *SMALL)
@@ -43,6 +45,12 @@ def test_full_workload_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
     assert len(s) == 16 and A["orb_keypoints"].shape[0] == 16 and A["plane_labels"].shape == (16, 480, 640)
     assert A.keys() == B_.keys() and all(np.array_equal(A[k], B_[k]) for k in A), [k for k in A if not np.array_equal(A[k], B_[k])]
     assert not np.array_equal(A["orb_keypoints"], C["orb_keypoints"]), "--steps 3 dumped the same last step as --steps 2"
+    # without --full: the same timed steps and outputs, none of the extra legs
+    dp = _bench(p, "--steps", "2", *PLAIN)
+    P = _load(p)
+    assert A.keys() == P.keys() and all(np.array_equal(A[k], P[k]) for k in A), [k for k in A if not np.array_equal(A[k], P[k])]
+    assert dp["steps"] == 2 and dp["value"] > 0 and dp["ms_per_step"] > 0
+    assert all(dp[k] is None for k in ("parity_sample", "roofline", "cpu_baseline", "latency_b1_ms", "sub_benchmarks", "value_pcie_inclusive"))
 
 
 def test_pose_workload_dumps_its_batch(tmp_path):

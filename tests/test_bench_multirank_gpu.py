@@ -26,8 +26,8 @@ def _bench(*flags, timeout=600):
 
 def test_two_ranks_shard_frames_and_print_one_line():
     B, K = 64, 2
-    d = _bench("--gpus", "2", "--backend", "gloo", "--steps", str(K), "--warmup", "1", "--batch", str(B), "--canvases", "16", "--cpu-seconds", "0", "--latency-reps", "0",
-               "--pcie-steps", "0")
+    d = _bench("--gpus", "2", "--backend", "gloo", "--steps", str(K), "--warmup", "1", "--batch", str(B), "--canvases", "16", "--full", "--cpu-seconds", "0",
+               "--latency-reps", "0", "--pcie-steps", "0")
     assert d["n_gpus"] == 2 and d["steps"] == K and d["scaling"] == "weak" and d["unit"] == "frames/s"
     assert d["config"]["frames_per_gpu_per_step"] == B and d["config"]["parallelism"].startswith("frame-sharded x2")
     # whole-job value: the frames of BOTH ranks over the slowest rank's time

@@ -4,7 +4,7 @@ tag=${1:-r06}
 cd $GRAFT_REPO_ROOT; O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
 timeout 240 python -c "import torch; print(torch.cuda.is_available())"
 timeout 300 python -m pytest tests/test_ba_gpu.py tests/test_ba_multirank_gpu.py -m gpu -q -x > $O/${tag}_ba_tests.log 2>&1; grep -a "passed\|failed\|Error" $O/${tag}_ba_tests.log | tail -5
-timeout 200 python bench.py --workload ba --steps 20 --warmup 3 > $O/${tag}_bench_ba.json 2> $O/ba.err
+timeout 200 python bench.py --workload ba --full --steps 20 --warmup 3 > $O/${tag}_bench_ba.json 2> $O/ba.err
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ba_prof
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ba_prof -- python $GRAFT_REPO_ROOT/bench.py --workload ba --steps 10 --warmup 2 > /dev/null 2>&1
 f=$(ls /tmp/ba_prof/*/*kernel_stats.csv | head -1); cp $f $O/${tag}_ba_kernel_stats.csv

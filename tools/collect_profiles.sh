@@ -10,11 +10,11 @@ tag=${1:-r06}; what=${2:-bench}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 240 python -c "import torch, numpy; print('warm', torch.cuda.is_available())" > $O/${tag}_warmup.log 2>&1
-FL="--steps 6 --warmup 3 --cpu-seconds 0 --latency-reps 0 --pcie-steps 0 --sub-steps 0"
+FL="--full --steps 6 --warmup 3 --cpu-seconds 0 --latency-reps 0 --pcie-steps 0 --sub-steps 0"
 # counter passes: the textures are synthesised in-process (--gen-procs 1, 16 rooms, 4-frame loops): rocprofv3 --pmc hangs when the profiled process forks workers (profiles/README.md)
-PF="--gen-procs 1 --canvases 16 --loop 4 --batch 1024 --seq-cus 0 --steps 3 --warmup 1 --cpu-seconds 0 --latency-reps 0 --pcie-steps 0 --sub-steps 0"   # B = 1024 as in every earlier round's counter files (bench.py scales traffic to its own batch)
+PF="--full --gen-procs 1 --canvases 16 --loop 4 --batch 1024 --seq-cus 0 --steps 3 --warmup 1 --cpu-seconds 0 --latency-reps 0 --pcie-steps 0 --sub-steps 0"   # B = 1024 as in every earlier round's counter files (bench.py scales traffic to its own batch)
 if [ $what = bench ]; then
-    timeout 400 python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err          # (configs[1] / [3] / [4] ride in its sub_benchmarks since round 5)
+    timeout 400 python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err          # (configs[1] / [3] / [4] ride in its sub_benchmarks since round 5)
     cd /tmp && export TMPDIR=/tmp
     timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_trace -- python $R/bench.py $FL > $O/${tag}_bench_under_rocprof.json 2>/dev/null
     cd $R
