@@ -473,7 +473,7 @@ int planar_lsd_detect_dev(planar_lsd* lsd, int B, int max_lines, planar_keyline*
 int planar_lsd_check(planar_lsd* lsd, int B);
 /* diagnostics (tests / profiling; stage 5 = cycle counters, see lsd.hip): stage 0 level-line angle float deg [w*h] (-1024 undefined), 1 squared gradient u32 [w*h],
  * 2 visiting order int32 (returns n), 3 raw segments 40 B each {x1,y1,x2,y2 float; width,p,nfa double} (returns count),
- * 4 number of grown regions int32[1] */
+ * 4 number of grown regions int32[1], 7 rare paths of the region kernel int32[2]: regions grown again by refine(), rounds of reduce_region_radius */
 int planar_lsd_read_stage(planar_lsd* lsd, int frame, int stage, void* out, int64_t out_bytes);
 /* Per-launch timing with HIP events on the context stream (bench.py's roofline leg), as planar_peac_set_profiling: get_profile synchronises and returns the
  * summed milliseconds of the recorded calls, total_ms[4] = preprocessing (blurs, gradient, Sobel), lsd_sort, lsd_detect, the rest, their number, and resets. */

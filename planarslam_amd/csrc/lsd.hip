@@ -54,7 +54,7 @@ struct Plan {
     double gaussCoefL[21], gaussCoefG[63];
 };
 
-struct Misc { uint32_t g2max; int n_ord; int n_seg; int n_kl; int status; int n_regions; int n_grown_px; int n_rect; long long t[8]; int sort_counts[2]; int heap_n; int sort_kv; int sort_prefix; int pad_; float imp_T; int imp_done; int imp_redo; int imp_full; };   // sort_counts: ranges, LDS-tier blocks; heap_n: ranges left to the heap-sort fallback; sort_kv: the largest sort key of a pixel with a defined angle, sort_prefix: words with a key <= that
+struct Misc { uint32_t g2max; int n_ord; int n_seg; int n_kl; int status; int n_regions; int n_grown_px; int n_rect; long long t[8]; int sort_counts[2]; int heap_n; int sort_kv; int sort_prefix; int n_refine; float imp_T; int imp_done; int imp_redo; int imp_full; };   // sort_counts: ranges, LDS-tier blocks; heap_n: ranges left to the heap-sort fallback; sort_kv: the largest sort key of a pixel with a defined angle, sort_prefix: words with a key <= that; n_refine: regions that refine() grew again + 65536 x rounds of reduce_region_radius
 
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     // cv::fastAtan2: 7th-order odd polynomial, degrees; plain mul/add (no FMA), see oracle/cvprim.cpp
@@ -62,16 +62,12 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     const float p1 = 0.9997878412794807f * scale, p3 = -0.3258083974640975f * scale;
     const float p5 = 0.1555786518463281f * scale, p7 = -0.04432655554792128f * scale;
     const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + 2.220446049250313e-16f);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + 2.220446049250313e-16f);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
+    // one division on selected operands (the same quotient as the reference's two branches): no branch in the wave-uniform chain of region_grow
+    const bool flat = ax >= ay;
+    const float c = (flat ? ay : ax) / ((flat ? ax : ay) + 2.220446049250313e-16f);
+    const float c2 = c * c;
+    const float t = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    float a = flat ? t : 90.f - t;
     if (x < 0) a = 180.f - a;
     if (y < 0) a = 360.f - a;
     return a;
@@ -527,6 +523,7 @@ struct Det {
     uint32_t* ring;
     double* stage;      // [64][3]
     int lane;
+    int* n_refine;      // Misc::n_refine of the frame (lsd_detect only)
 };
 
 // `used` flags, addressed by the compact index r of a defined pixel.  The global tail is only touched by images with more than
@@ -588,7 +585,7 @@ __device__ __forceinline__ GrowBatch grow_fetch(const Det& D, int head, int nb, 
     return g;
 }
 // seed_deg / seed_cs: ang[seed_pix] and seedcs[seed_pix] (the caller fetches them for 64 seed candidates at a time).  The region list in
-// global memory (D.reg) is written by lane 0 and read back by other lanes of this wavefront: callers that read it issue wave_sync() first.
+// global memory (D.reg) is written by the first lanes, a batch's accepts at a time, and read back by other lanes of this wavefront: callers that read it issue wave_sync() first.
 __device__ int region_grow(const Det& D, int seed_pix, uint32_t seed_rank, float seed_deg, float2 seed_cs, double prec, double& reg_angle) {
     const int lane = D.lane;
     reg_angle = (double)seed_deg * DEG_TO_RADS;
@@ -617,22 +614,33 @@ __device__ int region_grow(const Det& D, int seed_pix, uint32_t seed_rank, float
             bool ok = cur.ok && deg != NOTDEF_F;
             ok = ok && !used_get(D, rk);
             const double a = (double)deg * DEG_TO_RADS;
-            int cursor = 0;
-            while (true) {
-                const bool cand = ok && lane >= cursor && aligned_rad(a, reg_angle, prec);
-                const unsigned long long m = __ballot(cand);
-                if (!m) break;
-                const int f = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
-                const uint32_t axy = (uint32_t)__builtin_amdgcn_readlane((int)cur.nxy, f);
+            // The accept chain: nothing but the ballot -> lane select -> angle update -> alignment test that the visiting order demands.  `live` (an SGPR pair)
+            // holds the lanes that can still be accepted: unused, behind the last accepted lane, not a duplicate of an accepted pixel.  aligned_rad is
+            // evaluated on the reference's operands without branches: |d| and ||d| - 2 pi| both, the comparison selected by three ballots.  Accepts go up the
+            // lanes, so the accepted lanes' mask is all the loop records: the j-th set bit is the j-th accept, and each accepted lane stores its own pixel
+            // (region list, ring, `used`) once after the loop.  Nothing inside a batch reads them.
+            unsigned long long live = __ballot(ok), acc = 0ull;
+            auto aligned_live = [&]() {
+                const double ad = fabs(reg_angle - a), aw = fabs(ad - M_2__PI);
+                const unsigned long long wrap = __ballot(ad > M_3_2_PI);
+                return ((wrap & __ballot(aw <= prec)) | (~wrap & __ballot(ad <= prec))) & live;
+            };
+            for (unsigned long long m = aligned_live(); m != 0ull; m = aligned_live()) {      // (tested at the bottom: one scalar branch per accept)
+                const int f = __ffsll((long long)m) - 1;
                 const uint32_t ark = (uint32_t)__builtin_amdgcn_readlane((int)rk, f);
-                if (lane == 0) { used_set(D, ark); D.reg[reg_n] = axy; D.ring[reg_n & (RING - 1)] = axy; }
-                reg_n++;
+                acc |= 1ull << f;
                 sumdx += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), f));
                 sumdy += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn), f));
                 reg_angle = (double)fast_atan2_deg(sumdy, sumdx) * DEG_TO_RADS;
-                ok = ok && rk != ark;              // the same pixel as a neighbour of another entry of this batch: now used
-                cursor = f + 1;
+                // lanes up to f are passed; the same pixel as a neighbour of another entry of this batch is now used
+                live &= ~__ballot(rk == ark) & ~((2ull << f) - 1ull);
             }
+            if ((acc >> lane) & 1ull) {
+                const int at = reg_n + __popcll(acc & ((1ull << lane) - 1ull));
+                used_set(D, rk);
+                D.reg[at] = cur.nxy; D.ring[at & (RING - 1)] = cur.nxy;
+            }
+            reg_n += __popcll(acc);
         }
         lds_sync();                                // ring / used updates of this batch before the next batch reads them
         head = head_n;
@@ -686,18 +694,32 @@ __device__ inline int wave_sum_i(int v) { return planar::wave_sum_i32(v); }
 
 __device__ __forceinline__ double modgrad_of(const Det& D, uint32_t pxy) { return sqrt(D.g2[(pxy >> 16) * D.w + (pxy & 0xffff)] / 4.0); }
 
-__device__ void region2rect(const Det& D, int n, double reg_angle, double prec, double p, Rect& rec) {
+// region_point: point i of the region list.  `ring`: the whole region still sits in the LDS ring as region_grow left it (at most RING points, D.reg not rewritten
+// since): no global round trip, and the caller need not wait for the list's stores to land.  The LDS read is unconditional for the reason given in grow_fetch.
+__device__ __forceinline__ uint32_t region_point(const Det& D, int i, bool ring) {
+    uint32_t e = D.ring[i & (RING - 1)];
+    asm volatile("" : "+v"(e));
+    if (!ring) e = D.reg[i];
+    return e;
+}
+
+// Both moment passes and the extent loop read the same points and the first two the same weights (a gather, an FP64 square root and a division per point): a region
+// of at most 64 points - most of those that get here - keeps its lane's point and weight in registers for all three.
+__device__ void region2rect(const Det& D, int n, double reg_angle, double prec, double p, Rect& rec, bool ring) {
     double s3[3];
+    const bool one = n <= 64;
+    uint32_t e1 = 0; double w1 = 0;
     chains3(D, n, s3, false, [&](int i, double* v) {
-        const uint32_t e = D.reg[i];
+        const uint32_t e = region_point(D, i, ring);
         const double wgt = modgrad_of(D, e);
+        e1 = e; w1 = wgt;
         v[0] = double(e & 0xffff) * wgt; v[1] = double(e >> 16) * wgt; v[2] = wgt;
     });
     const double x = s3[0] / s3[2], y = s3[1] / s3[2];
     // get_theta
     chains3(D, n, s3, true, [&](int i, double* v) {
-        const uint32_t e = D.reg[i];
-        const double wgt = modgrad_of(D, e);
+        uint32_t e = e1; double wgt = w1;
+        if (!one) { e = region_point(D, i, ring); wgt = modgrad_of(D, e); }
         const double dx = double(e & 0xffff) - x, dy = double(e >> 16) - y;
         v[0] = dy * dy * wgt; v[1] = dx * dx * wgt; v[2] = dx * dy * wgt;
     });
@@ -709,7 +731,7 @@ __device__ void region2rect(const Det& D, int n, double reg_angle, double prec, 
     const double dx = cos(theta), dy = sin(theta);
     double l_min = 0, l_max = 0, w_min = 0, w_max = 0;
     for (int i = D.lane; i < n; i += 64) {
-        const uint32_t e = D.reg[i];
+        const uint32_t e = one ? e1 : region_point(D, i, ring);
         const double regdx = double(e & 0xffff) - x, regdy = double(e >> 16) - y;
         const double l = regdx * dx + regdy * dy;
         const double w = -regdx * dy + regdy * dx;
@@ -730,6 +752,7 @@ __device__ bool reduce_region_radius(const Det& D, int& n, double reg_angle, dou
     const double radSq1 = dist2(xc, yc, rec.x1, rec.y1), radSq2 = dist2(xc, yc, rec.x2, rec.y2);
     double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
     while (density < density_th) {
+        if (lane == 0) *D.n_refine += 65536;
         radSq *= 0.75 * 0.75;
         // the reference's swap-with-last removal == keep near points in place, fill each far slot below the new size with
         // the near points found scanning from the back (LSD)
@@ -764,7 +787,7 @@ __device__ bool reduce_region_radius(const Det& D, int& n, double reg_angle, dou
         wave_sync();
         n = n_near;
         if (n < 2) return false;
-        region2rect(D, n, reg_angle, prec, p, rec);
+        region2rect(D, n, reg_angle, prec, p, rec, false);       // (the list was compacted in global memory: the ring is stale)
         density = double(n) / (sqrt(dist2(rec.x1, rec.y1, rec.x2, rec.y2)) * rec.width);
     }
     return true;
@@ -773,6 +796,8 @@ __device__ bool reduce_region_radius(const Det& D, int& n, double reg_angle, dou
 __device__ bool refine(const Det& D, int& n, double& reg_angle, double prec, double p, Rect& rec, double density_th) {
     double density = double(n) / (sqrt(dist2(rec.x1, rec.y1, rec.x2, rec.y2)) * rec.width);
     if (density >= density_th) return true;
+    if (D.lane == 0) *D.n_refine += 1;
+    wave_sync();                                   // the region list in global memory is read from here on
     const uint32_t e0 = D.reg[0];
     const double xc = double(e0 & 0xffff), yc = double(e0 >> 16);
     const int seed_pix = (e0 >> 16) * D.w + (e0 & 0xffff);
@@ -800,7 +825,7 @@ __device__ bool refine(const Det& D, int& n, double& reg_angle, double prec, dou
     n = region_grow(D, seed_pix, rank_of(D, seed_pix), D.ang[seed_pix], seed_cos_sin(D.ang[seed_pix]), tau, reg_angle);
     wave_sync();
     if (n < 2) return false;
-    region2rect(D, n, reg_angle, prec, p, rec);
+    region2rect(D, n, reg_angle, prec, p, rec, n <= RING);
     density = double(n) / (sqrt(dist2(rec.x1, rec.y1, rec.x2, rec.y2)) * rec.width);
     if (density < density_th) return reduce_region_radius(D, n, reg_angle, prec, p, rec, density, density_th);
     return true;
@@ -1022,7 +1047,7 @@ __global__ __launch_bounds__(64) void lsd_detect(const Plan* __restrict__ plan, 
     D.ang = (const float*)(F + P.off_ang); D.g2 = (const uint32_t*)(F + P.off_g2);
     D.pix4 = (const float4*)(F + P.off_pix); D.plan = plan;
     D.reg = (uint32_t*)(F + P.off_reg); D.tmp = (uint32_t*)(F + P.off_tmp);
-    D.w = P.w; D.h = P.h; D.log_nt = P.log_nt; D.lane = lane;
+    D.w = P.w; D.h = P.h; D.log_nt = P.log_nt; D.lane = lane; D.n_refine = &misc->n_refine;
     const int used_words = USED_LDS_BITS / 32, gused_words = (P.w * P.h + 31) / 32;
     D.gused = (uint32_t*)(F + P.off_gused);
     uint8_t* q = lds_raw;
@@ -1039,12 +1064,22 @@ __global__ __launch_bounds__(64) void lsd_detect(const Plan* __restrict__ plan, 
     int n_rect = 0, n_regions = 0, n_px = 0;
     long long t_grow = 0, t_rect = 0, t_refine = 0, t_nfa = 0;
     const long long t_begin = __builtin_readcyclecounter();
-    for (int base = 0; base < n_ord; base += 64) {
-        const int pix = base + lane < n_ord ? (int)ord[base + lane] : -1;
-        const uint32_t prk = base + lane < n_ord ? ordr[base + lane] : 0u;
-        const float sdeg = pix >= 0 ? D.ang[pix] : 0.f;             // seed angle / (cos, sin) of the 64 candidates of this block
+    // The seed candidates are read two blocks of 64 ahead (pixel and compact index) and their angles one block ahead: the dependent pair of gathers of a block
+    // is in flight while the regions of the blocks before it grow, instead of being waited for at the head of every block.
+    auto seed_pix = [&](int i) { return i < n_ord ? (int)ord[i] : -1; };
+    auto seed_rank = [&](int i) { return i < n_ord ? ordr[i] : 0u; };
+    int pix = seed_pix(lane), pix_n = seed_pix(64 + lane);
+    uint32_t prk = seed_rank(lane), prk_n = seed_rank(64 + lane);
+    float sdeg = pix >= 0 ? D.ang[pix] : 0.f;                        // seed angle / (cos, sin) of the 64 candidates of this block
+    int pix_nn = -1;
+    uint32_t prk_nn = 0u;
+    for (int base = 0; base < n_ord; base += 64, pix = pix_n, prk = prk_n, pix_n = pix_nn, prk_n = prk_nn) {
+        const float sdeg_cur = sdeg;
+        sdeg = pix_n >= 0 ? D.ang[pix_n] : 0.f;
+        pix_nn = seed_pix(base + 128 + lane); prk_nn = seed_rank(base + 128 + lane);
         float2 scs = make_float2(0.f, 0.f);                           // (on the fly, 64 candidates at a time, and only for blocks that still hold an unused pixel: see seed_cos_sin)
-        if (__ballot(pix >= 0 && !used_get(D, prk)) != 0ull) scs = pix >= 0 && sdeg != NOTDEF_F ? seed_cos_sin(sdeg) : make_float2(0.f, 0.f);
+        if (__ballot(pix >= 0 && !used_get(D, prk)) == 0ull) continue;
+        scs = pix >= 0 && sdeg_cur != NOTDEF_F ? seed_cos_sin(sdeg_cur) : make_float2(0.f, 0.f);
         int cursor = 0;
         while (true) {
             const bool cand = pix >= 0 && lane >= cursor && !used_get(D, prk);
@@ -1054,7 +1089,7 @@ __global__ __launch_bounds__(64) void lsd_detect(const Plan* __restrict__ plan, 
             cursor = f + 1;
             const int seed = __builtin_amdgcn_readlane(pix, f);
             const uint32_t seed_rank = (uint32_t)__builtin_amdgcn_readlane((int)prk, f);
-            const float seed_deg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sdeg), f));
+            const float seed_deg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sdeg_cur), f));
             const float2 seed_cs = make_float2(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(scs.x), f)),
                                                __int_as_float(__builtin_amdgcn_readlane(__float_as_int(scs.y), f)));
             double reg_angle;
@@ -1064,9 +1099,10 @@ __global__ __launch_bounds__(64) void lsd_detect(const Plan* __restrict__ plan, 
             t_grow += c1 - c0;
             n_regions++; n_px += n;
             if (n < P.min_reg_size) continue;
-            wave_sync();                                            // region list written by lane 0, read by all lanes below
+            const bool ring = n <= RING;                            // the region is still whole in the LDS ring: region2rect reads it there
+            if (!ring) wave_sync();                                 // region list written per batch by its first lanes, read by all lanes below
             Rect rec;
-            region2rect(D, n, reg_angle, P.prec, P.p, rec);
+            region2rect(D, n, reg_angle, P.prec, P.p, rec, ring);
             c0 = __builtin_readcyclecounter(); t_rect += c0 - c1;
             const bool keep = refine(D, n, reg_angle, P.prec, P.p, rec, P.density_th);
             c1 = __builtin_readcyclecounter(); t_refine += c1 - c0;
@@ -1872,6 +1908,11 @@ int planar_lsd_read_stage(planar_lsd* o, int frame, int stage, void* out, int64_
             PLANAR_REQUIRE(out_bytes >= 32, PLANAR_EINVAL, "buffer too small");
             long long* o64 = (long long*)out;
             o64[0] = m.imp_done; o64[1] = m.imp_redo; o64[2] = m.imp_full; o64[3] = m.n_rect;
+            return PLANAR_OK;
+        }
+        case 7: {   // rare paths of lsd_detect: regions that failed the density test and were grown again by refine(), rounds of reduce_region_radius
+            PLANAR_REQUIRE(out_bytes >= 8, PLANAR_EINVAL, "buffer too small");
+            ((int32_t*)out)[0] = m.n_refine & 0xffff; ((int32_t*)out)[1] = m.n_refine >> 16;
             return PLANAR_OK;
         }
         default: set_error("planar_lsd_read_stage: unknown stage"); return PLANAR_EINVAL;

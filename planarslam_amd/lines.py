@@ -59,6 +59,8 @@ class LineSegment:
             out = np.zeros(10, np.int64)
         elif stage == 6:
             out = np.zeros(4, np.int64)
+        elif stage == 7:
+            out = np.zeros(2, np.int32)
         else:
             out = np.zeros(1, np.int32)
         r = check(lib().planar_lsd_read_stage(self.h, frame, stage, out.ctypes.data, out.nbytes))
