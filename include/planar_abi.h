@@ -58,7 +58,7 @@ int planar_ctx_set_stream(planar_ctx* ctx, void* hip_stream);
  * run only on the compute units whose bit is set in cu_mask (n_words x 32 bits, bit i = CU i in the driver's round-robin-over-XCDs numbering:
  * hipExtStreamCreateWithCUMask); planar_ctx_set_seq_stream(ctx, s) makes the context launch the PEAC clustering kernel and LSD's region-growing kernel on s
  * (forked from / joined into the context's stream by events, so results and ordering are unchanged); s = NULL restores the single-stream behaviour (default).
- * One such stream may be shared by several contexts.  The caller destroys it after the contexts. */
+ * One such stream may be shared by several contexts.  The caller destroys it after the contexts.  The context must be idle when planar_ctx_set_seq_stream is called. */
 int planar_cu_stream_create(int device, const uint32_t* cu_mask, int n_words, void** out_stream);
 void planar_cu_stream_destroy(void* stream);
 int planar_ctx_set_seq_stream(planar_ctx* ctx, void* stream);

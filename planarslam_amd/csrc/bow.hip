@@ -211,15 +211,15 @@ int planar_bow_transform(planar_vocab* v, const uint8_t* desc, const int32_t* n,
     PLANAR_HIP_CHECK(hipSetDevice(v->ctx->device));
     hipStream_t st = v->ctx->stream;
     const size_t bs = (size_t)B * stride;
-    Stager S;
-    const int i_desc = S.in(desc, bs * 32), i_n = S.in(n, (size_t)B * 4), i_word = S.out(word, bs * 4), i_w = S.out(weight, bs * 8), i_node = S.out(node, bs * 4),
-              i_bw = S.out(bow_word, bs * 4), i_bv = S.out(bow_value, bs * 8), i_bn = S.out(bow_n, (size_t)B * 4);
-    int rc = S.upload(st);
-    if (rc) return rc;
-    if ((rc = planar_bow_transform_dev(v, S.dev<uint8_t>(i_desc), S.dev<int32_t>(i_n), B, stride, levelsup, S.dev<int32_t>(i_word), S.dev<double>(i_w), S.dev<int32_t>(i_node),
-                                       S.dev<int32_t>(i_bw), S.dev<double>(i_bv), S.dev<int32_t>(i_bn))))
-        return rc;
-    return S.download(st);
+    Stager s;
+    const auto d_desc = s.in(desc, bs * 32);
+    const auto d_n = s.in(n, (size_t)B);
+    const auto d_word = s.out(word, bs);
+    const auto d_weight = s.out(weight, bs);
+    const auto d_node = s.out(node, bs), d_bow_word = s.out(bow_word, bs);
+    const auto d_bow_value = s.out(bow_value, bs);
+    const auto d_bow_n = s.out(bow_n, (size_t)B);
+    return s.run(st, [&] { return planar_bow_transform_dev(v, d_desc, d_n, B, stride, levelsup, d_word, d_weight, d_node, d_bow_word, d_bow_value, d_bow_n); });
 }
 
 }  // extern "C"

@@ -51,25 +51,39 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
-// Host<->device staging for the synchronous host-pointer entry points: one device block, inputs
-// copied in on the stream, outputs copied back after the launch.
+// Host<->device staging for the synchronous host-pointer entry points: one device block, inputs copied in on the stream, outputs copied back after the launch.
+// in() / out() / inout() take a host array and its length in ELEMENTS and return a handle that converts to the array's device address once upload() has run;
+// a null host array (an optional argument) is not staged and converts to a null device pointer.  Every array starts on a 256-byte boundary of the block.
 struct Stager {
-    struct Item { const void* h_in; void* h_out; size_t bytes; size_t off; };
+    struct Item { const void* h_in; void* h_out; size_t bytes; size_t off; void* field; };
+    template <typename T> struct Dev {
+        const Stager* s = nullptr; size_t off = 0;
+        operator T*() const { return s ? (T*)(s->buf.as<uint8_t>() + off) : nullptr; }
+    };
     std::vector<Item> items;
     size_t total = 0;
     DevBuf buf;
-    // returns the index of the item; call dev<T>(idx) after upload()
-    int in(const void* h, size_t bytes) { return add(h, nullptr, bytes); }
-    int out(void* h, size_t bytes) { return add(nullptr, h, bytes); }
-    int inout(void* h, size_t bytes) { return add(h, h, bytes); }
-    int add(const void* hin, void* hout, size_t bytes) {
-        items.push_back({hin, hout, bytes, total});
+    template <typename T> Dev<const T> in(const T* h, size_t count) { return h ? add<const T>(h, nullptr, count) : Dev<const T>{}; }
+    template <typename T> Dev<T> out(T* h, size_t count) { return h ? add<T>(nullptr, h, count) : Dev<T>{}; }
+    template <typename T> Dev<T> inout(T* h, size_t count) { return h ? add<T>(h, h, count) : Dev<T>{}; }
+    template <typename T> Dev<T> temp(size_t count) { return add<T>(nullptr, nullptr, count); }   // an array of the block that is not copied either way
+    // For the arrays of a view struct, on the caller's copy of the view: the host array `field` points to is staged, and upload() stores its device address in `field`.
+    // A null input stays null; an output without a host array (planar_pose_assemble's optional ones) still gets its device array.
+    template <typename T> void in_field(const T*& field, size_t count) { if (field) add<const T>(field, nullptr, count, &field); }
+    template <typename T> void out_field(const T*& field, size_t count) { add<T>(nullptr, const_cast<T*>(field), count, &field); }
+    template <typename T> Dev<T> add(const void* hin, void* hout, size_t count, void* field = nullptr) {
+        const size_t bytes = count * sizeof(T);
+        items.push_back({hin, hout, bytes, total, field});
         total += align_up(bytes ? bytes : (size_t)1, (size_t)256);
-        return (int)items.size() - 1;
+        return {this, items.back().off};
     }
     int upload(hipStream_t st) {
         int rc = buf.alloc(total);
         if (rc) return rc;
+        for (const Item& it : items) {
+            void* const d = buf.as<uint8_t>() + it.off;
+            if (it.field) memcpy(it.field, &d, sizeof d);
+        }
         for (const Item& it : items)
             if (it.h_in && it.bytes) {
                 hipError_t e = hipMemcpyAsync(buf.as<uint8_t>() + it.off, it.h_in, it.bytes, hipMemcpyHostToDevice, st);
@@ -77,7 +91,14 @@ struct Stager {
             }
         return PLANAR_OK;
     }
-    template <typename T> T* dev(int idx) const { return (T*)(buf.as<uint8_t>() + items[idx].off); }
+    // zeroes the staged block from `first` (an array of this call) to its end, on the stream: every array staged after `first` included
+    template <typename T> hipError_t zero_from(const Dev<T>& first, hipStream_t st) { return hipMemsetAsync((T*)first, 0, total - first.off, st); }
+    // the body of a host-pointer entry point once its arrays are staged: copy in, enqueue (launch() returns a PLANAR_* code), copy out, wait
+    template <typename F> int run(hipStream_t st, F&& launch) {
+        int rc = upload(st);
+        if (!rc) rc = launch();
+        return rc ? rc : download(st);
+    }
     int download(hipStream_t st) {
         for (const Item& it : items)
             if (it.h_out && it.bytes) {
@@ -86,6 +107,66 @@ struct Stager {
             }
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) { set_error("stream sync failed: %s", hipGetErrorString(e)); return PLANAR_EDEVICE; }
+        return PLANAR_OK;
+    }
+};
+
+// Optional HIP-event timing of the launches behind one entry point (planar_*_set_profiling / planar_*_get_profile; bench.py's roofline leg reads the slots).
+// A recorded call owns one set of slots + 1 events: begin() hands the set out, every mark() records its next event, and slot i is the time between events
+// i and i + 1.  A set stays open until its last event is recorded, so a later call can continue it (LSD: planar_lsd_preprocess_dev records events 0-2,
+// planar_lsd_detect_dev 3-4); a set that never got its last event is left out of sum().  With profiling off, begin() and mark() are one branch and no HIP call.
+struct LaunchProfile {
+    const int slots;
+    bool on = false;
+    bool open = false;                // the newest set still waits for events
+    std::vector<hipEvent_t> ev;       // the sets, slots + 1 events each, back to back
+    std::vector<int> marked;          // events recorded so far, per set
+    size_t used = 0;                  // sets handed out since the last reset()
+    explicit LaunchProfile(int nslots) : slots(nslots) {}
+    LaunchProfile(const LaunchProfile&) = delete;
+    ~LaunchProfile() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void reset() { used = 0; open = false; }
+    int begin() {
+        open = false;                 // a set left open by the previous call stays incomplete
+        if (!on) return PLANAR_OK;
+        if (used == marked.size()) {
+            for (int i = 0; i <= slots; i++) {
+                hipEvent_t e;
+                const hipError_t err = hipEventCreate(&e);
+                if (err != hipSuccess) {
+                    for (; i > 0; i--) { (void)hipEventDestroy(ev.back()); ev.pop_back(); }
+                    set_error("hipEventCreate failed: %s", hipGetErrorString(err));
+                    return err == hipErrorOutOfMemory ? PLANAR_ENOMEM : PLANAR_EDEVICE;
+                }
+                ev.push_back(e);
+            }
+            marked.push_back(0);
+        }
+        marked[used++] = 0;
+        open = true;
+        return PLANAR_OK;
+    }
+    void mark(hipStream_t st) {
+        if (!open) return;
+        int& k = marked[used - 1];
+        (void)hipEventRecord(ev[(used - 1) * (slots + 1) + k], st);
+        open = ++k <= slots;
+    }
+    // total_ms[slots]: elapsed time per slot, summed over the complete sets; *calls: how many there were.  The stream must be idle.  Resets.
+    int sum(double* total_ms, int64_t* calls) {
+        for (int i = 0; i < slots; i++) total_ms[i] = 0;
+        int64_t counted = 0;
+        for (size_t c = 0; c < used; c++) {
+            if (marked[c] != slots + 1) continue;
+            for (int i = 0; i < slots; i++) {
+                float ms = 0;
+                PLANAR_HIP_CHECK(hipEventElapsedTime(&ms, ev[c * (slots + 1) + i], ev[c * (slots + 1) + i + 1]));
+                total_ms[i] += ms;
+            }
+            counted++;
+        }
+        *calls = counted;
+        reset();
         return PLANAR_OK;
     }
 };
@@ -115,16 +196,21 @@ struct planar_ctx {
     // CUs while the wide kernels of `stream` keep the rest.  seq_begin() / seq_end() bracket the launch: fork by event from `stream`, join back into it.
     hipStream_t seq_stream = nullptr;
     hipEvent_t seq_fork = nullptr, seq_join = nullptr;
+    // A failed fork leaves the launch on `stream` itself (ordered, only without the overlap) and says so through planar_last_error.
     hipStream_t seq_begin() {
         if (!seq_stream) return stream;
-        (void)hipEventRecord(seq_fork, stream);
-        (void)hipStreamWaitEvent(seq_stream, seq_fork, 0);
-        return seq_stream;
+        hipError_t e = hipEventRecord(seq_fork, stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(seq_stream, seq_fork, 0);
+        if (e == hipSuccess) return seq_stream;
+        planar::set_error("planar_ctx: the fork to the side stream failed (%s): launching on the context's stream", hipGetErrorString(e));
+        return stream;
     }
-    void seq_end() {
-        if (!seq_stream) return;
-        (void)hipEventRecord(seq_join, seq_stream);
-        (void)hipStreamWaitEvent(stream, seq_join, 0);
+    // sq: what seq_begin() returned.  After a failed join `stream` is not ordered behind the side stream's kernel: the caller returns the error.
+    int seq_end(hipStream_t sq) {
+        if (!seq_stream || sq != seq_stream) return PLANAR_OK;
+        PLANAR_HIP_CHECK(hipEventRecord(seq_join, sq));
+        PLANAR_HIP_CHECK(hipStreamWaitEvent(stream, seq_join, 0));
+        return PLANAR_OK;
     }
     int ensure_scratch(size_t bytes) {
         if (scratch.bytes >= bytes) return PLANAR_OK;

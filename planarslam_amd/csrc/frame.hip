@@ -361,12 +361,14 @@ int planar_undistort_keypoints(planar_ctx* ctx, int B, const planar_keypoint* ke
     PLANAR_REQUIRE(B >= 1 && stride >= 1, PLANAR_EINVAL, "bad size");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int i_k = s.in(keys, (size_t)B * stride * sizeof(planar_keypoint)), i_n = s.in(n, (size_t)B * 4), o_k = s.out(keys_un, (size_t)B * stride * sizeof(planar_keypoint));
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    PLANAR_HIP_CHECK(hipMemsetAsync(s.dev<uint8_t>(o_k), 0, (size_t)B * stride * sizeof(planar_keypoint), ctx->stream));
-    if ((rc = planar_undistort_keypoints_dev(ctx, B, s.dev<planar_keypoint>(i_k), s.dev<int32_t>(i_n), stride, fx, fy, cx, cy, dist_coef, s.dev<planar_keypoint>(o_k)))) return rc;
-    return s.download(ctx->stream);
+    const size_t ns = (size_t)B * stride;
+    const auto d_keys = s.in(keys, ns);
+    const auto d_n = s.in(n, (size_t)B);
+    const auto d_keys_un = s.out(keys_un, ns);
+    return s.run(ctx->stream, [&]() -> int {
+        PLANAR_HIP_CHECK(hipMemsetAsync(d_keys_un, 0, ns * sizeof(planar_keypoint), ctx->stream));
+        return planar_undistort_keypoints_dev(ctx, B, d_keys, d_n, stride, fx, fy, cx, cy, dist_coef, d_keys_un);
+    });
 }
 int planar_keypoint_fields_dev(planar_ctx* ctx, const planar_keypoint* d_keys, int64_t n, int32_t* d_octave, float* d_angle) {
     PLANAR_REQUIRE(ctx && d_keys && d_octave && d_angle && n >= 1, PLANAR_EINVAL, "bad argument");
@@ -396,16 +398,15 @@ int planar_stereo_from_rgbd(planar_ctx* ctx, int B, const planar_keypoint* keys,
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
     const size_t ns = (size_t)B * stride;
-    const int i0 = s.in(keys, ns * sizeof(planar_keypoint)), i1 = keys_un == keys ? i0 : s.in(keys_un, ns * sizeof(planar_keypoint)), i2 = s.in(n, (size_t)B * 4);
-    const int i3 = s.in(depth, (size_t)B * frame_stride_px * 2), i4 = s.in(Tcw, (size_t)B * 64);
-    const int o0 = s.out(u_right, ns * 4), o1 = s.out(depth_out, ns * 4), o2 = s.out(xw, ns * 12), o3 = s.out(valid, ns);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_stereo_from_rgbd_dev(ctx, B, s.dev<planar_keypoint>(i0), s.dev<planar_keypoint>(i1), s.dev<int32_t>(i2), stride, s.dev<uint16_t>(i3), pitch_px,
-                                     frame_stride_px, depth_factor, fx, fy, cx, cy, bf, s.dev<float>(i4), s.dev<float>(o0), s.dev<float>(o1), s.dev<float>(o2),
-                                     s.dev<uint8_t>(o3));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const auto d_keys = s.in(keys, ns), d_keys_un = keys_un == keys ? d_keys : s.in(keys_un, ns);
+    const auto d_n = s.in(n, (size_t)B);
+    const auto d_depth = s.in(depth, (size_t)B * frame_stride_px);
+    const auto d_Tcw = s.in(Tcw, (size_t)B * 16);
+    const auto d_ur = s.out(u_right, ns), d_z = s.out(depth_out, ns), d_xw = s.out(xw, ns * 3);
+    const auto d_valid = s.out(valid, ns);
+    return s.run(ctx->stream, [&] {
+        return planar_stereo_from_rgbd_dev(ctx, B, d_keys, d_keys_un, d_n, stride, d_depth, pitch_px, frame_stride_px, depth_factor, fx, fy, cx, cy, bf, d_Tcw, d_ur, d_z, d_xw, d_valid);
+    });
 }
 
 int planar_pose_assemble(planar_ctx* ctx, const planar_track_matches* m, const planar_pose_batch* out) {
@@ -417,33 +418,20 @@ int planar_pose_assemble(planar_ctx* ctx, const planar_track_matches* m, const p
     const size_t B = (size_t)m->B;
     planar_track_matches d = *m;
     planar_pose_batch o = *out;
-    const int a0 = s.in(m->n, B * 4), a1 = s.in(m->keys_un, B * m->stride * sizeof(planar_keypoint)), a2 = s.in(m->u_right, B * m->stride * 4);
-    const int a3 = s.in(m->pt_match, B * m->stride * 4), a4 = s.in(m->mp_xw, B * m->mp_stride * 12), a5 = m->mp_valid ? s.in(m->mp_valid, B * m->mp_stride) : -1;
-    const bool ln = m->n_lines != nullptr && out->max_lines > 0, pl = m->n_planes != nullptr && out->max_planes > 0;
-    int b0 = -1, b1 = -1, b2 = -1, b3 = -1, c0 = -1, c1 = -1, c2 = -1, c3 = -1;
-    if (ln) { b0 = s.in(m->n_lines, B * 4); b1 = s.in(m->line_eq, B * m->ln_stride * 24); b2 = s.in(m->ln_match, B * m->ln_stride * 4); b3 = s.in(m->ml_xw6, B * m->ml_stride * 48); }
-    if (pl) { c0 = s.in(m->n_planes, B * 4); c1 = s.in(m->pl_coef, B * m->pl_stride * 16); c2 = s.in(m->pl_match, 3 * B * m->pl_stride * 4);
-              c3 = s.in(m->mpl_coef, (m->mpl_shared ? 1 : B) * (size_t)m->mpl_stride * 16); }
-    const int t0 = s.in(m->Tcw, B * 64);
-    const size_t MP = out->max_points, ML = std::max(out->max_lines, 1), MM = std::max(out->max_planes, 1);
-    const int o0 = s.out((void*)out->n_points, B * 4), o1 = s.out((void*)out->n_lines, B * 4), o2 = s.out((void*)out->n_planes, B * 4);
-    const int o3 = s.out((void*)out->pt_valid, B * MP), o4 = s.out((void*)out->pt_xw, B * MP * 12), o5 = s.out((void*)out->pt_obs, B * MP * 12), o6 = s.out((void*)out->pt_inv_sigma2, B * MP * 4);
-    const int o7 = s.out((void*)out->ln_valid, out->max_lines ? B * ML : 0), o8 = s.out((void*)out->ln_obs, out->max_lines ? B * ML * 24 : 0), o9 = s.out((void*)out->ln_xw, out->max_lines ? B * ML * 48 : 0);
-    const int p0 = s.out((void*)out->pl_meas, out->max_planes ? B * MM * 16 : 0), p1 = s.out((void*)out->pl_valid, out->max_planes ? B * MM * 3 : 0), p2 = s.out((void*)out->pl_world, out->max_planes ? B * MM * 48 : 0);
-    const int p3 = s.out((void*)out->Tcw_in, B * 64);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    d.n = s.dev<int32_t>(a0); d.keys_un = s.dev<planar_keypoint>(a1); d.u_right = s.dev<float>(a2); d.pt_match = s.dev<int32_t>(a3); d.mp_xw = s.dev<float>(a4);
-    d.mp_valid = a5 >= 0 ? s.dev<uint8_t>(a5) : nullptr;
-    d.n_lines = ln ? s.dev<int32_t>(b0) : nullptr; d.line_eq = ln ? s.dev<double>(b1) : nullptr; d.ln_match = ln ? s.dev<int32_t>(b2) : nullptr; d.ml_xw6 = ln ? s.dev<double>(b3) : nullptr;
-    d.n_planes = pl ? s.dev<int32_t>(c0) : nullptr; d.pl_coef = pl ? s.dev<float>(c1) : nullptr; d.pl_match = pl ? s.dev<int32_t>(c2) : nullptr; d.mpl_coef = pl ? s.dev<float>(c3) : nullptr;
-    d.Tcw = s.dev<float>(t0);
-    o.n_points = s.dev<int32_t>(o0); o.n_lines = s.dev<int32_t>(o1); o.n_planes = s.dev<int32_t>(o2); o.pt_valid = s.dev<uint8_t>(o3); o.pt_xw = s.dev<float>(o4);
-    o.pt_obs = s.dev<float>(o5); o.pt_inv_sigma2 = s.dev<float>(o6); o.ln_valid = s.dev<uint8_t>(o7); o.ln_obs = s.dev<double>(o8); o.ln_xw = s.dev<double>(o9);
-    o.pl_meas = s.dev<float>(p0); o.pl_valid = s.dev<uint8_t>(p1); o.pl_world = s.dev<float>(p2); o.Tcw_in = s.dev<float>(p3);
-    rc = planar_pose_assemble_dev(ctx, &d, &o);
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    // (planar_pose_batch declares the arrays this call writes as const: they are planar_pose_optimize's inputs)
+    s.in_field(d.n, B); s.in_field(d.keys_un, B * m->stride); s.in_field(d.u_right, B * m->stride); s.in_field(d.pt_match, B * m->stride); s.in_field(d.mp_xw, B * m->mp_stride * 3); s.in_field(d.mp_valid, B * m->mp_stride);
+    if (!(m->n_lines != nullptr && out->max_lines > 0)) d.n_lines = nullptr, d.line_eq = nullptr, d.ln_match = nullptr, d.ml_xw6 = nullptr;
+    if (!(m->n_planes != nullptr && out->max_planes > 0)) d.n_planes = nullptr, d.pl_coef = nullptr, d.pl_match = nullptr, d.mpl_coef = nullptr;
+    s.in_field(d.n_lines, B); s.in_field(d.line_eq, B * m->ln_stride * 3); s.in_field(d.ln_match, B * m->ln_stride); s.in_field(d.ml_xw6, B * m->ml_stride * 6);
+    s.in_field(d.n_planes, B); s.in_field(d.pl_coef, B * m->pl_stride * 4); s.in_field(d.pl_match, 3 * B * m->pl_stride); s.in_field(d.mpl_coef, (m->mpl_shared ? 1 : B) * (size_t)m->mpl_stride * 4);
+    s.in_field(d.Tcw, B * 16);
+    const size_t MP = out->max_points, ML = out->max_lines > 0 ? out->max_lines : 0, MM = out->max_planes > 0 ? out->max_planes : 0;
+    s.out_field(o.n_points, B); s.out_field(o.n_lines, B); s.out_field(o.n_planes, B);
+    s.out_field(o.pt_valid, B * MP); s.out_field(o.pt_xw, B * MP * 3); s.out_field(o.pt_obs, B * MP * 3); s.out_field(o.pt_inv_sigma2, B * MP);
+    s.out_field(o.ln_valid, B * ML); s.out_field(o.ln_obs, B * ML * 3); s.out_field(o.ln_xw, B * ML * 6);
+    s.out_field(o.pl_meas, B * MM * 4); s.out_field(o.pl_valid, B * MM * 3); s.out_field(o.pl_world, B * MM * 12);
+    s.out_field(o.Tcw_in, B * 16);
+    return s.run(ctx->stream, [&] { return planar_pose_assemble_dev(ctx, &d, &o); });
 }
 
 int planar_discard_outliers(planar_ctx* ctx, int B, const int32_t* n, int stride, int flag_stride, int32_t* match, uint8_t* outlier, int32_t* kept) {
@@ -451,13 +439,11 @@ int planar_discard_outliers(planar_ctx* ctx, int B, const int32_t* n, int stride
     PLANAR_REQUIRE(B >= 1 && stride >= 1 && flag_stride >= 1, PLANAR_EINVAL, "bad size");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int i0 = s.in(n, (size_t)B * 4), i1 = s.inout(match, (size_t)B * stride * 4), i2 = s.inout(outlier, (size_t)B * flag_stride);
-    const int o0 = kept ? s.out(kept, (size_t)B * 4) : s.add(nullptr, nullptr, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_discard_outliers_dev(ctx, B, s.dev<int32_t>(i0), stride, flag_stride, s.dev<int32_t>(i1), s.dev<uint8_t>(i2), s.dev<int32_t>(o0));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const auto d_n = s.in(n, (size_t)B);
+    const auto d_match = s.inout(match, (size_t)B * stride);
+    const auto d_outlier = s.inout(outlier, (size_t)B * flag_stride);
+    const auto d_kept = kept ? s.out(kept, (size_t)B) : s.temp<int32_t>((size_t)B);
+    return s.run(ctx->stream, [&] { return planar_discard_outliers_dev(ctx, B, d_n, stride, flag_stride, d_match, d_outlier, d_kept); });
 }
 
 int planar_update_normal_and_depth_dev(planar_ctx* ctx, int G, const int32_t* d_n, int stride, const float* d_xw, const uint8_t* d_valid, const float* d_ref_Tcw,
@@ -484,16 +470,17 @@ int planar_update_normal_and_depth(planar_ctx* ctx, int G, const int32_t* n, int
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t N = (size_t)G * stride;
     Stager s;
-    const int i_n = s.in(n, (size_t)G * 4), i_x = s.in(xw, N * 12), i_v = valid ? s.in(valid, N) : -1, i_T = s.in(ref_Tcw, (size_t)G * 64), i_k = s.in(keys_un, N * sizeof(planar_keypoint));
-    const int i_oo = obs_off ? s.in(obs_off, (N + 1) * 4) : -1, i_ow = obs_off ? s.in(obs_ow, (size_t)obs_off[N] * 12) : -1;
-    const int io_nr = s.inout(normal, N * 12), io_mn = s.inout(min_dist, N * 4), io_mx = s.inout(max_dist, N * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    if ((rc = planar_update_normal_and_depth_dev(ctx, G, s.dev<int32_t>(i_n), stride, s.dev<float>(i_x), valid ? s.dev<uint8_t>(i_v) : nullptr, s.dev<float>(i_T),
-                                                 s.dev<planar_keypoint>(i_k), obs_off ? s.dev<int32_t>(i_oo) : nullptr, obs_off ? s.dev<float>(i_ow) : nullptr, scale_factors,
-                                                 n_levels, s.dev<float>(io_nr), s.dev<float>(io_mn), s.dev<float>(io_mx))))
-        return rc;
-    return s.download(ctx->stream);
+    const auto d_n = s.in(n, (size_t)G);
+    const auto d_xw = s.in(xw, N * 3);
+    const auto d_valid = s.in(valid, N);
+    const auto d_T = s.in(ref_Tcw, (size_t)G * 16);
+    const auto d_keys = s.in(keys_un, N);
+    const auto d_obs_off = s.in(obs_off, N + 1);
+    const auto d_obs_ow = s.in(obs_ow, obs_off ? (size_t)obs_off[N] * 3 : 0);
+    const auto d_normal = s.inout(normal, N * 3), d_min = s.inout(min_dist, N), d_max = s.inout(max_dist, N);
+    return s.run(ctx->stream, [&] {
+        return planar_update_normal_and_depth_dev(ctx, G, d_n, stride, d_xw, d_valid, d_T, d_keys, d_obs_off, d_obs_ow, scale_factors, n_levels, d_normal, d_min, d_max);
+    });
 }
 
 }  // extern "C"

@@ -1053,125 +1053,140 @@ static int launch_projection(planar_ctx* ctx, const Args& a) {
 using namespace planar;
 using guided::Args;
 
+// ---- one argument check per entry-point pair: the host-pointer form calls it before it touches the device, the _dev form before it launches ----
+static bool n_levels_ok(int n) { return n >= 1 && n <= PLANAR_MAX_LEVELS; }
+
+static int check_frame_args(const void* ctx, const planar_frame_view* cur, const planar_last_frame_view* last, const void* match, const void* nmatches) {
+    PLANAR_REQUIRE(ctx && cur && last && match && nmatches, PLANAR_EINVAL, "null argument");
+    if (int rc = guided::check_view(cur)) return rc;
+    PLANAR_REQUIRE(cur->Tcw && last->n && last->Tcw && last->usable && last->xw && last->octave && last->angle && last->mp_desc && last->mp_observed,
+                   PLANAR_EINVAL, "null array in view");
+    PLANAR_REQUIRE(last->stride >= 1 && last->stride <= guided::MAXN, PLANAR_EINVAL, "last-frame stride out of range");
+    return PLANAR_OK;
+}
+static int check_map_args(const void* ctx, const planar_frame_view* frame, const planar_map_probes* probes, const void* match, const void* nmatches) {
+    PLANAR_REQUIRE(ctx && frame && probes && match && nmatches, PLANAR_EINVAL, "null argument");
+    if (int rc = guided::check_view(frame)) return rc;
+    PLANAR_REQUIRE(probes->n && probes->in_view && probes->proj_x && probes->proj_y && probes->proj_xr && probes->level && probes->view_cos &&
+                       probes->desc && probes->observed, PLANAR_EINVAL, "null array in probes");
+    PLANAR_REQUIRE(probes->stride >= 1, PLANAR_EINVAL, "probe stride out of range");
+    return PLANAR_OK;
+}
+static int check_keyframe_args(const void* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, int n_levels, int orb_dist, const void* match, const void* nmatches) {
+    PLANAR_REQUIRE(ctx && cur && kf && match && nmatches, PLANAR_EINVAL, "null argument");
+    if (int rc = guided::check_view(cur)) return rc;
+    PLANAR_REQUIRE(cur->Tcw && kf->n && kf->usable && kf->xw && kf->min_dist && kf->max_dist && kf->angle && kf->desc, PLANAR_EINVAL, "null array in view");
+    PLANAR_REQUIRE(kf->stride >= 1, PLANAR_EINVAL, "key-frame stride out of range");
+    PLANAR_REQUIRE(n_levels_ok(n_levels), PLANAR_EINVAL, "n_levels out of range");
+    PLANAR_REQUIRE(orb_dist < 256, PLANAR_EINVAL, "orb_dist >= 256 (the reference would write mvpMapPoints[-1])");
+    return PLANAR_OK;
+}
+static int check_fuse_args(const void* ctx, const planar_frame_view* kf, int n_levels, int stride, bool arrays) {
+    PLANAR_REQUIRE(ctx && kf && arrays, PLANAR_EINVAL, "null argument");
+    if (int rc = guided::check_view(kf)) return rc;
+    PLANAR_REQUIRE(kf->Tcw != nullptr, PLANAR_EINVAL, "key-frame view: Tcw required");
+    PLANAR_REQUIRE(stride >= 1 && n_levels_ok(n_levels), PLANAR_EINVAL, "stride >= 1 and 1 <= n_levels <= PLANAR_MAX_LEVELS required");
+    return PLANAR_OK;
+}
+static int check_lsd_fuse_args(const void* ctx, const planar_frame_view* kf, int n_levels, int line_stride, int ml_stride, bool arrays) {
+    PLANAR_REQUIRE(ctx && kf && kf->Tcw && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(kf->B >= 1 && line_stride >= 1 && ml_stride >= 1 && n_levels_ok(n_levels), PLANAR_EINVAL, "B, strides >= 1 and 1 <= n_levels <= PLANAR_MAX_LEVELS required");
+    return PLANAR_OK;
+}
+// planar_is_in_frustum_points (with n_levels) and planar_is_in_frustum_lines (without: pass 1)
+static int check_frustum_args(const void* ctx, const planar_frame_view* f, int n_levels, int stride, bool arrays) {
+    PLANAR_REQUIRE(ctx && f && f->Tcw && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(f->B >= 1 && stride >= 1 && n_levels_ok(n_levels), PLANAR_EINVAL, "bad sizes");
+    return PLANAR_OK;
+}
+static int check_bow_args(const void* ctx, int B, int kf_stride, int f_stride, bool arrays) {
+    PLANAR_REQUIRE(ctx && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(B >= 1 && kf_stride >= 1 && kf_stride <= guided::MAXN && f_stride >= 1 && f_stride <= guided::MAXN, PLANAR_EINVAL,
+                   "1 <= stride <= PLANAR_MAX_FRAME_KEYS required");
+    return PLANAR_OK;
+}
+static int check_lsd_projection_args(const void* ctx, int B, int line_stride, int ml_stride, int n_levels, bool arrays) {
+    PLANAR_REQUIRE(ctx && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(B >= 1 && line_stride >= 1 && line_stride <= guided::MAX_LINES && ml_stride >= 1, PLANAR_EINVAL, "bad sizes (line_stride <= 1024)");
+    PLANAR_REQUIRE(n_levels_ok(n_levels), PLANAR_EINVAL, "n_levels out of range");
+    return PLANAR_OK;
+}
+static int check_plane_search_args(const void* ctx, int B, int pl_stride, int mp_stride, int pts_stride, bool arrays) {
+    PLANAR_REQUIRE(ctx && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(B >= 1 && pl_stride >= 1 && mp_stride >= 1 && pts_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    return PLANAR_OK;
+}
+
+// ---- one staging helper per view struct, on the host-pointer form's COPY of the view: Stager::upload() turns the copy's host pointers into device addresses ----
+static void stage_view(Stager& s, planar_frame_view& d, bool with_pose) {
+    const size_t B = (size_t)d.B, n = B * d.stride;
+    if (!with_pose) d.Tcw = nullptr;
+    s.in_field(d.n, B); s.in_field(d.keys_un, n); s.in_field(d.u_right, n); s.in_field(d.desc, n * 32); s.in_field(d.blocked, n); s.in_field(d.Tcw, B * 16);
+}
+static void stage_view(Stager& s, planar_last_frame_view& d, size_t B) {
+    const size_t n = B * d.stride;
+    s.in_field(d.n, B); s.in_field(d.Tcw, B * 16); s.in_field(d.usable, n); s.in_field(d.xw, n * 3); s.in_field(d.octave, n); s.in_field(d.angle, n);
+    s.in_field(d.mp_desc, n * 32); s.in_field(d.mp_observed, n);
+}
+static void stage_view(Stager& s, planar_map_probes& d, size_t B) {
+    const size_t n = B * d.stride;
+    s.in_field(d.n, B); s.in_field(d.in_view, n); s.in_field(d.proj_x, n); s.in_field(d.proj_y, n); s.in_field(d.proj_xr, n); s.in_field(d.level, n);
+    s.in_field(d.view_cos, n); s.in_field(d.desc, n * 32); s.in_field(d.observed, n);
+}
+static void stage_view(Stager& s, planar_keyframe_probes& d, size_t B) {
+    const size_t n = B * d.stride;
+    s.in_field(d.n, B); s.in_field(d.usable, n); s.in_field(d.found, n); s.in_field(d.xw, n * 3); s.in_field(d.min_dist, n); s.in_field(d.max_dist, n);
+    s.in_field(d.angle, n); s.in_field(d.desc, n * 32);
+}
+
 extern "C" {
 
 int planar_search_by_projection_frame_dev(planar_ctx* ctx, const planar_frame_view* cur, const planar_last_frame_view* last, float th,
                                           int mono, int check_orientation, int32_t* d_cur_match, int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && cur && last && d_cur_match && d_nmatches, PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(cur);
-    if (rc) return rc;
-    PLANAR_REQUIRE(cur->Tcw && last->n && last->Tcw && last->usable && last->xw && last->octave && last->angle && last->mp_desc && last->mp_observed,
-                   PLANAR_EINVAL, "null array in view");
-    PLANAR_REQUIRE(last->stride >= 1 && last->stride <= guided::MAXN, PLANAR_EINVAL, "last-frame stride out of range");
+    if (int rc = check_frame_args(ctx, cur, last, d_cur_match, d_nmatches)) return rc;
     Args a{};
     a.f = *cur; a.last = *last; a.th = th; a.mono = mono; a.check_orientation = check_orientation; a.nn_ratio = 0;
     a.match = d_cur_match; a.nmatches = d_nmatches;
     return guided::launch_projection<guided::MODE_FRAME>(ctx, a);
 }
 
+int planar_search_by_projection_frame(planar_ctx* ctx, const planar_frame_view* cur, const planar_last_frame_view* last, float th, int mono,
+                                      int check_orientation, int32_t* cur_match, int32_t* nmatches) {
+    if (int rc = check_frame_args(ctx, cur, last, cur_match, nmatches)) return rc;
+    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
+    Stager s;
+    planar_frame_view dc = *cur;
+    planar_last_frame_view dl = *last;
+    stage_view(s, dc, true);
+    stage_view(s, dl, (size_t)cur->B);
+    const auto d_match = s.inout(cur_match, (size_t)cur->B * cur->stride), d_n = s.out(nmatches, (size_t)cur->B);
+    return s.run(ctx->stream, [&] { return planar_search_by_projection_frame_dev(ctx, &dc, &dl, th, mono, check_orientation, d_match, d_n); });
+}
+
 int planar_search_by_projection_map_dev(planar_ctx* ctx, const planar_frame_view* frame, const planar_map_probes* probes, float th,
                                         float nn_ratio, int32_t* d_match, int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && frame && probes && d_match && d_nmatches, PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(frame);
-    if (rc) return rc;
-    PLANAR_REQUIRE(probes->n && probes->in_view && probes->proj_x && probes->proj_y && probes->proj_xr && probes->level && probes->view_cos &&
-                       probes->desc && probes->observed, PLANAR_EINVAL, "null array in probes");
-    PLANAR_REQUIRE(probes->stride >= 1, PLANAR_EINVAL, "probe stride out of range");
+    if (int rc = check_map_args(ctx, frame, probes, d_match, d_nmatches)) return rc;
     Args a{};
     a.f = *frame; a.mp = *probes; a.th = th; a.nn_ratio = nn_ratio; a.match = d_match; a.nmatches = d_nmatches;
     return guided::launch_projection<guided::MODE_MAP>(ctx, a);
 }
 
-static int stage_view(Stager& s, const planar_frame_view* f, bool with_pose, int* ix) {
-    const size_t n = (size_t)f->B * f->stride;
-    ix[0] = s.in(f->n, (size_t)f->B * 4);
-    ix[1] = s.in(f->keys_un, n * sizeof(planar_keypoint));
-    ix[2] = s.in(f->u_right, n * 4);
-    ix[3] = s.in(f->desc, n * 32);
-    ix[4] = f->blocked ? s.in(f->blocked, n) : -1;
-    ix[5] = with_pose ? s.in(f->Tcw, (size_t)f->B * 64) : -1;
-    return 0;
-}
-static void patch_view(const Stager& s, planar_frame_view* d, const int* ix) {
-    d->n = s.dev<int32_t>(ix[0]); d->keys_un = s.dev<planar_keypoint>(ix[1]); d->u_right = s.dev<float>(ix[2]); d->desc = s.dev<uint8_t>(ix[3]);
-    d->blocked = ix[4] >= 0 ? s.dev<uint8_t>(ix[4]) : nullptr;
-    d->Tcw = ix[5] >= 0 ? s.dev<float>(ix[5]) : nullptr;
-}
-
-int planar_search_by_projection_frame(planar_ctx* ctx, const planar_frame_view* cur, const planar_last_frame_view* last, float th, int mono,
-                                      int check_orientation, int32_t* cur_match, int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && cur && last && cur_match && nmatches, PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(cur);
-    if (rc) return rc;
-    PLANAR_REQUIRE(cur->Tcw && last->n && last->Tcw && last->usable && last->xw && last->octave && last->angle && last->mp_desc && last->mp_observed,
-                   PLANAR_EINVAL, "null array in view");
-    PLANAR_REQUIRE(last->stride >= 1 && last->stride <= guided::MAXN, PLANAR_EINVAL, "last-frame stride out of range");
-    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
-    Stager s;
-    int ix[6];
-    stage_view(s, cur, true, ix);
-    const int B = cur->B;
-    const size_t nl = (size_t)B * last->stride;
-    const int l0 = s.in(last->n, (size_t)B * 4), l1 = s.in(last->Tcw, (size_t)B * 64), l2 = s.in(last->usable, nl), l3 = s.in(last->xw, nl * 12),
-              l4 = s.in(last->octave, nl * 4), l5 = s.in(last->angle, nl * 4), l6 = s.in(last->mp_desc, nl * 32), l7 = s.in(last->mp_observed, nl);
-    const int om = s.inout(cur_match, (size_t)B * cur->stride * 4), on = s.out(nmatches, (size_t)B * 4);
-    rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    planar_frame_view dc = *cur;
-    patch_view(s, &dc, ix);
-    planar_last_frame_view dl = *last;
-    dl.n = s.dev<int32_t>(l0); dl.Tcw = s.dev<float>(l1); dl.usable = s.dev<uint8_t>(l2); dl.xw = s.dev<float>(l3); dl.octave = s.dev<int32_t>(l4);
-    dl.angle = s.dev<float>(l5); dl.mp_desc = s.dev<uint8_t>(l6); dl.mp_observed = s.dev<uint8_t>(l7);
-    rc = planar_search_by_projection_frame_dev(ctx, &dc, &dl, th, mono, check_orientation, s.dev<int32_t>(om), s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
-}
-
 int planar_search_by_projection_map(planar_ctx* ctx, const planar_frame_view* frame, const planar_map_probes* probes, float th, float nn_ratio,
                                     int32_t* match, int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && frame && probes && match && nmatches, PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(frame);
-    if (rc) return rc;
-    PLANAR_REQUIRE(probes->n && probes->in_view && probes->proj_x && probes->proj_y && probes->proj_xr && probes->level && probes->view_cos &&
-                       probes->desc && probes->observed, PLANAR_EINVAL, "null array in probes");
-    PLANAR_REQUIRE(probes->stride >= 1, PLANAR_EINVAL, "probe stride out of range");
+    if (int rc = check_map_args(ctx, frame, probes, match, nmatches)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    int ix[6];
-    stage_view(s, frame, false, ix);
-    const int B = frame->B;
-    const size_t np = (size_t)B * probes->stride;
-    const int p0 = s.in(probes->n, (size_t)B * 4), p1 = s.in(probes->in_view, np), p2 = s.in(probes->proj_x, np * 4), p3 = s.in(probes->proj_y, np * 4),
-              p4 = s.in(probes->proj_xr, np * 4), p5 = s.in(probes->level, np * 4), p6 = s.in(probes->view_cos, np * 4), p7 = s.in(probes->desc, np * 32),
-              p8 = s.in(probes->observed, np);
-    const int om = s.inout(match, (size_t)B * frame->stride * 4), on = s.out(nmatches, (size_t)B * 4);
-    rc = s.upload(ctx->stream);
-    if (rc) return rc;
     planar_frame_view df = *frame;
-    patch_view(s, &df, ix);
     planar_map_probes dp = *probes;
-    dp.n = s.dev<int32_t>(p0); dp.in_view = s.dev<uint8_t>(p1); dp.proj_x = s.dev<float>(p2); dp.proj_y = s.dev<float>(p3); dp.proj_xr = s.dev<float>(p4);
-    dp.level = s.dev<int32_t>(p5); dp.view_cos = s.dev<float>(p6); dp.desc = s.dev<uint8_t>(p7); dp.observed = s.dev<uint8_t>(p8);
-    rc = planar_search_by_projection_map_dev(ctx, &df, &dp, th, nn_ratio, s.dev<int32_t>(om), s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
-}
-
-static int check_keyframe_args(const planar_frame_view* cur, const planar_keyframe_probes* kf, int n_levels, int orb_dist) {
-    int rc = guided::check_view(cur);
-    if (rc) return rc;
-    PLANAR_REQUIRE(cur->Tcw && kf->n && kf->usable && kf->xw && kf->min_dist && kf->max_dist && kf->angle && kf->desc, PLANAR_EINVAL, "null array in view");
-    PLANAR_REQUIRE(kf->stride >= 1, PLANAR_EINVAL, "key-frame stride out of range");
-    PLANAR_REQUIRE(n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL, "n_levels out of range");
-    PLANAR_REQUIRE(orb_dist < 256, PLANAR_EINVAL, "orb_dist >= 256 (the reference would write mvpMapPoints[-1])");
-    return PLANAR_OK;
+    stage_view(s, df, false);
+    stage_view(s, dp, (size_t)frame->B);
+    const auto d_match = s.inout(match, (size_t)frame->B * frame->stride), d_n = s.out(nmatches, (size_t)frame->B);
+    return s.run(ctx->stream, [&] { return planar_search_by_projection_map_dev(ctx, &df, &dp, th, nn_ratio, d_match, d_n); });
 }
 
 int planar_search_by_projection_keyframe_dev(planar_ctx* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, float log_scale_factor,
                                              int n_levels, float th, int orb_dist, int check_orientation, int32_t* d_cur_match, int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && cur && kf && d_cur_match && d_nmatches, PLANAR_EINVAL, "null argument");
-    int rc = check_keyframe_args(cur, kf, n_levels, orb_dist);
-    if (rc) return rc;
+    if (int rc = check_keyframe_args(ctx, cur, kf, n_levels, orb_dist, d_cur_match, d_nmatches)) return rc;
     Args a{};
     a.f = *cur; a.kf = *kf; a.lsf = log_scale_factor; a.th = th; a.n_levels = n_levels; a.orb_dist = orb_dist;
     a.check_orientation = check_orientation; a.match = d_cur_match; a.nmatches = d_nmatches;
@@ -1180,40 +1195,24 @@ int planar_search_by_projection_keyframe_dev(planar_ctx* ctx, const planar_frame
 
 int planar_search_by_projection_keyframe(planar_ctx* ctx, const planar_frame_view* cur, const planar_keyframe_probes* kf, float log_scale_factor,
                                          int n_levels, float th, int orb_dist, int check_orientation, int32_t* cur_match, int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && cur && kf && cur_match && nmatches, PLANAR_EINVAL, "null argument");
-    int rc = check_keyframe_args(cur, kf, n_levels, orb_dist);
-    if (rc) return rc;
+    if (int rc = check_keyframe_args(ctx, cur, kf, n_levels, orb_dist, cur_match, nmatches)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    int ix[6];
-    stage_view(s, cur, true, ix);
-    const int B = cur->B;
-    const size_t np = (size_t)B * kf->stride;
-    const int k0 = s.in(kf->n, (size_t)B * 4), k1 = s.in(kf->usable, np), k2 = kf->found ? s.in(kf->found, np) : -1, k3 = s.in(kf->xw, np * 12),
-              k4 = s.in(kf->min_dist, np * 4), k5 = s.in(kf->max_dist, np * 4), k6 = s.in(kf->angle, np * 4), k7 = s.in(kf->desc, np * 32);
-    const int om = s.inout(cur_match, (size_t)B * cur->stride * 4), on = s.out(nmatches, (size_t)B * 4);
-    rc = s.upload(ctx->stream);
-    if (rc) return rc;
     planar_frame_view dc = *cur;
-    patch_view(s, &dc, ix);
     planar_keyframe_probes dk = *kf;
-    dk.n = s.dev<int32_t>(k0); dk.usable = s.dev<uint8_t>(k1); dk.found = k2 >= 0 ? s.dev<uint8_t>(k2) : nullptr; dk.xw = s.dev<float>(k3);
-    dk.min_dist = s.dev<float>(k4); dk.max_dist = s.dev<float>(k5); dk.angle = s.dev<float>(k6); dk.desc = s.dev<uint8_t>(k7);
-    rc = planar_search_by_projection_keyframe_dev(ctx, &dc, &dk, log_scale_factor, n_levels, th, orb_dist, check_orientation, s.dev<int32_t>(om),
-                                                  s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    stage_view(s, dc, true);
+    stage_view(s, dk, (size_t)cur->B);
+    const auto d_match = s.inout(cur_match, (size_t)cur->B * cur->stride), d_n = s.out(nmatches, (size_t)cur->B);
+    return s.run(ctx->stream, [&] {
+        return planar_search_by_projection_keyframe_dev(ctx, &dc, &dk, log_scale_factor, n_levels, th, orb_dist, check_orientation, d_match, d_n);
+    });
 }
 
 int planar_fuse_search_dev(planar_ctx* ctx, const planar_frame_view* kf, const float* inv_level_sigma2, float log_scale_factor, int n_levels, const int32_t* d_n,
                            int stride, int points_shared, const uint8_t* d_usable, const float* d_xw, const float* d_normal, const float* d_min_dist,
                            const float* d_max_dist, const uint8_t* d_desc, float th, int32_t* d_fuse_idx, int32_t* d_fuse_dist, int32_t* d_n_fused) {
-    PLANAR_REQUIRE(ctx && kf && inv_level_sigma2 && d_n && d_usable && d_xw && d_normal && d_min_dist && d_max_dist && d_desc && d_fuse_idx && d_n_fused,
-                   PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(kf);
-    if (rc) return rc;
-    PLANAR_REQUIRE(kf->Tcw != nullptr, PLANAR_EINVAL, "key-frame view: Tcw required");
-    PLANAR_REQUIRE(stride >= 1 && n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL, "stride >= 1 and 1 <= n_levels <= PLANAR_MAX_LEVELS required");
+    if (int rc = check_fuse_args(ctx, kf, n_levels, stride, inv_level_sigma2 && d_n && d_usable && d_xw && d_normal && d_min_dist && d_max_dist && d_desc && d_fuse_idx && d_n_fused))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     guided::FuseArgs a{};
     a.f = *kf;
@@ -1229,38 +1228,30 @@ int planar_fuse_search_dev(planar_ctx* ctx, const planar_frame_view* kf, const f
 int planar_fuse_search(planar_ctx* ctx, const planar_frame_view* kf, const float* inv_level_sigma2, float log_scale_factor, int n_levels, const int32_t* n,
                        int stride, int points_shared, const uint8_t* usable, const float* xw, const float* normal, const float* min_dist,
                        const float* max_dist, const uint8_t* desc, float th, int32_t* fuse_idx, int32_t* fuse_dist, int32_t* n_fused) {
-    PLANAR_REQUIRE(ctx && kf && inv_level_sigma2 && n && usable && xw && normal && min_dist && max_dist && desc && fuse_idx && n_fused, PLANAR_EINVAL, "null argument");
-    int rc = guided::check_view(kf);
-    if (rc) return rc;
-    PLANAR_REQUIRE(kf->Tcw != nullptr && stride >= 1, PLANAR_EINVAL, "key-frame view: Tcw required, stride >= 1");
+    if (int rc = check_fuse_args(ctx, kf, n_levels, stride, inv_level_sigma2 && n && usable && xw && normal && min_dist && max_dist && desc && fuse_idx && n_fused)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    int ix[6];
-    stage_view(s, kf, true, ix);
-    const int B = kf->B;
-    const size_t np = (size_t)(points_shared ? 1 : B) * stride, no = (size_t)B * stride;
-    const int p0 = s.in(n, (size_t)(points_shared ? 1 : B) * 4), p1 = s.in(usable, np), p2 = s.in(xw, np * 12), p3 = s.in(normal, np * 12), p4 = s.in(min_dist, np * 4),
-              p5 = s.in(max_dist, np * 4), p6 = s.in(desc, np * 32);
-    const int o0 = s.out(fuse_idx, no * 4), o1 = fuse_dist ? s.out(fuse_dist, no * 4) : -1, o2 = s.out(n_fused, (size_t)B * 4);
-    rc = s.upload(ctx->stream);
-    if (rc) return rc;
     planar_frame_view d = *kf;
-    patch_view(s, &d, ix);
-    rc = planar_fuse_search_dev(ctx, &d, inv_level_sigma2, log_scale_factor, n_levels, s.dev<int32_t>(p0), stride, points_shared, s.dev<uint8_t>(p1), s.dev<float>(p2),
-                                s.dev<float>(p3), s.dev<float>(p4), s.dev<float>(p5), s.dev<uint8_t>(p6), th, s.dev<int32_t>(o0),
-                                o1 >= 0 ? s.dev<int32_t>(o1) : nullptr, s.dev<int32_t>(o2));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    stage_view(s, d, true);
+    const size_t B = (size_t)kf->B, PB = points_shared ? 1 : B, np = PB * stride, no = B * stride;
+    const auto d_n = s.in(n, PB);
+    const auto d_usable = s.in(usable, np);
+    const auto d_xw = s.in(xw, np * 3), d_normal = s.in(normal, np * 3), d_min = s.in(min_dist, np), d_max = s.in(max_dist, np);
+    const auto d_desc = s.in(desc, np * 32);
+    const auto d_idx = s.out(fuse_idx, no), d_dist = s.out(fuse_dist, no), d_fused = s.out(n_fused, B);
+    return s.run(ctx->stream, [&] {
+        return planar_fuse_search_dev(ctx, &d, inv_level_sigma2, log_scale_factor, n_levels, d_n, stride, points_shared, d_usable, d_xw, d_normal, d_min, d_max, d_desc, th, d_idx,
+                                      d_dist, d_fused);
+    });
 }
 
 int planar_lsd_fuse_search_dev(planar_ctx* ctx, const planar_frame_view* kf, float log_scale_factor, int n_levels, const int32_t* d_n_lines, int line_stride,
                                const planar_keyline* d_keylines, const uint8_t* d_ldesc, const int32_t* d_n_ml, int ml_stride, int lines_shared,
                                const uint8_t* d_usable, const double* d_xw6, const double* d_normal, const float* d_min_dist, const float* d_max_dist,
                                const uint8_t* d_ml_desc, float th, int32_t* d_fuse_idx, int32_t* d_fuse_dist, int32_t* d_n_fused) {
-    PLANAR_REQUIRE(ctx && kf && kf->Tcw && d_n_lines && d_keylines && d_ldesc && d_n_ml && d_usable && d_xw6 && d_normal && d_min_dist && d_max_dist && d_ml_desc &&
-                       d_fuse_idx && d_n_fused, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(kf->B >= 1 && line_stride >= 1 && ml_stride >= 1 && n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL,
-                   "B, strides >= 1 and 1 <= n_levels <= PLANAR_MAX_LEVELS required");
+    if (int rc = check_lsd_fuse_args(ctx, kf, n_levels, line_stride, ml_stride, d_n_lines && d_keylines && d_ldesc && d_n_ml && d_usable && d_xw6 && d_normal && d_min_dist &&
+                                                                                    d_max_dist && d_ml_desc && d_fuse_idx && d_n_fused))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     guided::LineFuseArgs a{};
     a.f = *kf; a.lsf = log_scale_factor; a.th = th; a.n_levels = n_levels; a.line_stride = line_stride; a.ml_stride = ml_stride; a.shared = lines_shared ? 1 : 0;
@@ -1275,35 +1266,36 @@ int planar_lsd_fuse_search(planar_ctx* ctx, const planar_frame_view* kf, float l
                            const planar_keyline* keylines, const uint8_t* ldesc, const int32_t* n_ml, int ml_stride, int lines_shared, const uint8_t* usable,
                            const double* xw6, const double* normal, const float* min_dist, const float* max_dist, const uint8_t* ml_desc, float th,
                            int32_t* fuse_idx, int32_t* fuse_dist, int32_t* n_fused) {
-    PLANAR_REQUIRE(ctx && kf && kf->Tcw && n_lines && keylines && ldesc && n_ml && usable && xw6 && normal && min_dist && max_dist && ml_desc && fuse_idx && n_fused,
-                   PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(kf->B >= 1 && line_stride >= 1 && ml_stride >= 1, PLANAR_EINVAL, "B, strides >= 1 required");
+    if (int rc = check_lsd_fuse_args(ctx, kf, n_levels, line_stride, ml_stride, n_lines && keylines && ldesc && n_ml && usable && xw6 && normal && min_dist && max_dist && ml_desc &&
+                                                                                    fuse_idx && n_fused))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int B = kf->B;
-    const size_t nl = (size_t)B * line_stride, nm = (size_t)(lines_shared ? 1 : B) * ml_stride, no = (size_t)B * ml_stride;
-    const int t = s.in(kf->Tcw, (size_t)B * 64), l0 = s.in(n_lines, (size_t)B * 4), l1 = s.in(keylines, nl * sizeof(planar_keyline)), l2 = s.in(ldesc, nl * 32);
-    const int m0 = s.in(n_ml, (size_t)(lines_shared ? 1 : B) * 4), m1 = s.in(usable, nm), m2 = s.in(xw6, nm * 48), m3 = s.in(normal, nm * 24), m4 = s.in(min_dist, nm * 4),
-              m5 = s.in(max_dist, nm * 4), m6 = s.in(ml_desc, nm * 32);
-    const int o0 = s.out(fuse_idx, no * 4), o1 = fuse_dist ? s.out(fuse_dist, no * 4) : -1, o2 = s.out(n_fused, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    planar_frame_view d = *kf;
-    d.Tcw = s.dev<float>(t);
-    rc = planar_lsd_fuse_search_dev(ctx, &d, log_scale_factor, n_levels, s.dev<int32_t>(l0), line_stride, s.dev<planar_keyline>(l1), s.dev<uint8_t>(l2), s.dev<int32_t>(m0),
-                                    ml_stride, lines_shared, s.dev<uint8_t>(m1), s.dev<double>(m2), s.dev<double>(m3), s.dev<float>(m4), s.dev<float>(m5),
-                                    s.dev<uint8_t>(m6), th, s.dev<int32_t>(o0), o1 >= 0 ? s.dev<int32_t>(o1) : nullptr, s.dev<int32_t>(o2));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    planar_frame_view d = *kf;                               // only the pose of the view is read
+    const size_t B = (size_t)kf->B, MB = lines_shared ? 1 : B, nl = B * line_stride, nm = MB * ml_stride, no = B * ml_stride;
+    s.in_field(d.Tcw, B * 16);
+    const auto d_n_lines = s.in(n_lines, B);
+    const auto d_keylines = s.in(keylines, nl);
+    const auto d_ldesc = s.in(ldesc, nl * 32);
+    const auto d_n_ml = s.in(n_ml, MB);
+    const auto d_usable = s.in(usable, nm);
+    const auto d_xw6 = s.in(xw6, nm * 6), d_normal = s.in(normal, nm * 3);
+    const auto d_min = s.in(min_dist, nm), d_max = s.in(max_dist, nm);
+    const auto d_ml_desc = s.in(ml_desc, nm * 32);
+    const auto d_idx = s.out(fuse_idx, no), d_dist = s.out(fuse_dist, no), d_fused = s.out(n_fused, B);
+    return s.run(ctx->stream, [&] {
+        return planar_lsd_fuse_search_dev(ctx, &d, log_scale_factor, n_levels, d_n_lines, line_stride, d_keylines, d_ldesc, d_n_ml, ml_stride, lines_shared, d_usable, d_xw6, d_normal,
+                                          d_min, d_max, d_ml_desc, th, d_idx, d_dist, d_fused);
+    });
 }
 
 int planar_is_in_frustum_points_dev(planar_ctx* ctx, const planar_frame_view* f, float log_scale_factor, int n_levels, const int32_t* d_n, int stride,
                                     const uint8_t* d_valid, const float* d_xw, const float* d_normal, const float* d_min_dist, const float* d_max_dist,
                                     float viewing_cos_limit, uint8_t* d_in_view, float* d_proj_x, float* d_proj_y, float* d_proj_xr, int32_t* d_level,
                                     float* d_view_cos) {
-    PLANAR_REQUIRE(ctx && f && f->Tcw && d_n && d_valid && d_xw && d_normal && d_min_dist && d_max_dist && d_in_view && d_proj_x && d_proj_y && d_proj_xr &&
-                       d_level && d_view_cos, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(f->B >= 1 && stride >= 1 && n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_frustum_args(ctx, f, n_levels, stride, d_n && d_valid && d_xw && d_normal && d_min_dist && d_max_dist && d_in_view && d_proj_x && d_proj_y && d_proj_xr &&
+                                                                  d_level && d_view_cos))
+        return rc;
     hipLaunchKernelGGL(guided::frustum_points_kernel, dim3((stride + 255) / 256, f->B), dim3(256), 0, ctx->stream, *f, log_scale_factor, n_levels, d_n, stride,
                        d_valid, d_xw, d_normal, d_min_dist, d_max_dist, viewing_cos_limit, d_in_view, d_proj_x, d_proj_y, d_proj_xr, d_level, d_view_cos);
     PLANAR_HIP_CHECK(hipGetLastError());
@@ -1313,33 +1305,30 @@ int planar_is_in_frustum_points_dev(planar_ctx* ctx, const planar_frame_view* f,
 int planar_is_in_frustum_points(planar_ctx* ctx, const planar_frame_view* f, float log_scale_factor, int n_levels, const int32_t* n, int stride,
                                 const uint8_t* valid, const float* xw, const float* normal, const float* min_dist, const float* max_dist,
                                 float viewing_cos_limit, uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr, int32_t* level, float* view_cos) {
-    PLANAR_REQUIRE(ctx && f && f->Tcw && n && valid && xw && normal && min_dist && max_dist && in_view && proj_x && proj_y && proj_xr && level && view_cos,
-                   PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(f->B >= 1 && stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_frustum_args(ctx, f, n_levels, stride, n && valid && xw && normal && min_dist && max_dist && in_view && proj_x && proj_y && proj_xr && level && view_cos))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const size_t N = (size_t)f->B * stride;
-    const int t = s.in(f->Tcw, (size_t)f->B * 64), a0 = s.in(n, (size_t)f->B * 4), a1 = s.in(valid, N), a2 = s.in(xw, N * 12), a3 = s.in(normal, N * 12),
-              a4 = s.in(min_dist, N * 4), a5 = s.in(max_dist, N * 4);
-    const int o0 = s.inout(in_view, N), o1 = s.inout(proj_x, N * 4), o2 = s.inout(proj_y, N * 4), o3 = s.inout(proj_xr, N * 4), o4 = s.inout(level, N * 4),
-              o5 = s.inout(view_cos, N * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    planar_frame_view d = *f;
-    d.Tcw = s.dev<float>(t);
-    rc = planar_is_in_frustum_points_dev(ctx, &d, log_scale_factor, n_levels, s.dev<int32_t>(a0), stride, s.dev<uint8_t>(a1), s.dev<float>(a2), s.dev<float>(a3),
-                                         s.dev<float>(a4), s.dev<float>(a5), viewing_cos_limit, s.dev<uint8_t>(o0), s.dev<float>(o1), s.dev<float>(o2),
-                                         s.dev<float>(o3), s.dev<int32_t>(o4), s.dev<float>(o5));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    planar_frame_view d = *f;                                // only the pose and the intrinsics of the view are read
+    const size_t B = (size_t)f->B, N = B * stride;
+    s.in_field(d.Tcw, B * 16);
+    const auto d_n = s.in(n, B);
+    const auto d_valid = s.in(valid, N);
+    const auto d_xw = s.in(xw, N * 3), d_normal = s.in(normal, N * 3), d_min = s.in(min_dist, N), d_max = s.in(max_dist, N);
+    const auto d_in_view = s.inout(in_view, N);
+    const auto d_px = s.inout(proj_x, N), d_py = s.inout(proj_y, N), d_pxr = s.inout(proj_xr, N);
+    const auto d_level = s.inout(level, N);
+    const auto d_cos = s.inout(view_cos, N);
+    return s.run(ctx->stream, [&] {
+        return planar_is_in_frustum_points_dev(ctx, &d, log_scale_factor, n_levels, d_n, stride, d_valid, d_xw, d_normal, d_min, d_max, viewing_cos_limit, d_in_view, d_px, d_py, d_pxr,
+                                               d_level, d_cos);
+    });
 }
 
 int planar_is_in_frustum_lines_dev(planar_ctx* ctx, const planar_frame_view* f, float log_scale_factor, const int32_t* d_n, int stride, const uint8_t* d_valid,
                                    const double* d_xw6, const double* d_normal, const float* d_min_dist, const float* d_max_dist, float viewing_cos_limit,
                                    uint8_t* d_in_view, float* d_proj, int32_t* d_level, float* d_view_cos) {
-    PLANAR_REQUIRE(ctx && f && f->Tcw && d_n && d_valid && d_xw6 && d_normal && d_min_dist && d_max_dist && d_in_view && d_proj && d_level && d_view_cos,
-                   PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(f->B >= 1 && stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_frustum_args(ctx, f, 1, stride, d_n && d_valid && d_xw6 && d_normal && d_min_dist && d_max_dist && d_in_view && d_proj && d_level && d_view_cos)) return rc;
     hipLaunchKernelGGL(guided::frustum_lines_kernel, dim3((stride + 255) / 256, f->B), dim3(256), 0, ctx->stream, *f, log_scale_factor, d_n, stride, d_valid, d_xw6,
                        d_normal, d_min_dist, d_max_dist, viewing_cos_limit, d_in_view, d_proj, d_level, d_view_cos);
     PLANAR_HIP_CHECK(hipGetLastError());
@@ -1349,34 +1338,32 @@ int planar_is_in_frustum_lines_dev(planar_ctx* ctx, const planar_frame_view* f, 
 int planar_is_in_frustum_lines(planar_ctx* ctx, const planar_frame_view* f, float log_scale_factor, const int32_t* n, int stride, const uint8_t* valid,
                                const double* xw6, const double* normal, const float* min_dist, const float* max_dist, float viewing_cos_limit, uint8_t* in_view,
                                float* proj, int32_t* level, float* view_cos) {
-    PLANAR_REQUIRE(ctx && f && f->Tcw && n && valid && xw6 && normal && min_dist && max_dist && in_view && proj && level && view_cos, PLANAR_EINVAL,
-                   "null argument");
-    PLANAR_REQUIRE(f->B >= 1 && stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_frustum_args(ctx, f, 1, stride, n && valid && xw6 && normal && min_dist && max_dist && in_view && proj && level && view_cos)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const size_t N = (size_t)f->B * stride;
-    const int t = s.in(f->Tcw, (size_t)f->B * 64), a0 = s.in(n, (size_t)f->B * 4), a1 = s.in(valid, N), a2 = s.in(xw6, N * 48), a3 = s.in(normal, N * 24),
-              a4 = s.in(min_dist, N * 4), a5 = s.in(max_dist, N * 4);
-    const int o0 = s.inout(in_view, N), o1 = s.inout(proj, N * 16), o2 = s.inout(level, N * 4), o3 = s.inout(view_cos, N * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    planar_frame_view d = *f;
-    d.Tcw = s.dev<float>(t);
-    rc = planar_is_in_frustum_lines_dev(ctx, &d, log_scale_factor, s.dev<int32_t>(a0), stride, s.dev<uint8_t>(a1), s.dev<double>(a2), s.dev<double>(a3),
-                                        s.dev<float>(a4), s.dev<float>(a5), viewing_cos_limit, s.dev<uint8_t>(o0), s.dev<float>(o1), s.dev<int32_t>(o2),
-                                        s.dev<float>(o3));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    planar_frame_view d = *f;                                // only the pose and the intrinsics of the view are read
+    const size_t B = (size_t)f->B, N = B * stride;
+    s.in_field(d.Tcw, B * 16);
+    const auto d_n = s.in(n, B);
+    const auto d_valid = s.in(valid, N);
+    const auto d_xw6 = s.in(xw6, N * 6), d_normal = s.in(normal, N * 3);
+    const auto d_min = s.in(min_dist, N), d_max = s.in(max_dist, N);
+    const auto d_in_view = s.inout(in_view, N);
+    const auto d_proj = s.inout(proj, N * 4);
+    const auto d_level = s.inout(level, N);
+    const auto d_cos = s.inout(view_cos, N);
+    return s.run(ctx->stream, [&] {
+        return planar_is_in_frustum_lines_dev(ctx, &d, log_scale_factor, d_n, stride, d_valid, d_xw6, d_normal, d_min, d_max, viewing_cos_limit, d_in_view, d_proj, d_level, d_cos);
+    });
 }
 
 int planar_search_by_bow_dev(planar_ctx* ctx, int B, const int32_t* d_n_kf, int kf_stride, const int32_t* d_kf_node, const uint8_t* d_kf_usable,
                              const float* d_kf_angle, const uint8_t* d_kf_desc, const int32_t* d_n_f, int f_stride, const int32_t* d_f_node,
                              const float* d_f_angle, const uint8_t* d_f_desc, float nn_ratio, int check_orientation, int32_t* d_match,
                              int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && d_n_kf && d_kf_node && d_kf_usable && d_kf_angle && d_kf_desc && d_n_f && d_f_node && d_f_angle && d_f_desc && d_match && d_nmatches,
-                   PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && kf_stride >= 1 && kf_stride <= guided::MAXN && f_stride >= 1 && f_stride <= guided::MAXN, PLANAR_EINVAL,
-                   "1 <= stride <= PLANAR_MAX_FRAME_KEYS required");
+    if (int rc = check_bow_args(ctx, B, kf_stride, f_stride, d_n_kf && d_kf_node && d_kf_usable && d_kf_angle && d_kf_desc && d_n_f && d_f_node && d_f_angle && d_f_desc && d_match &&
+                                                                 d_nmatches))
+        return rc;
     static bool attr_set = false;
     if (!attr_set) {
         PLANAR_HIP_CHECK(hipFuncSetAttribute((const void*)guided::bow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(guided::BowLds)));
@@ -1393,22 +1380,22 @@ int planar_search_by_bow_dev(planar_ctx* ctx, int B, const int32_t* d_n_kf, int 
 int planar_search_by_bow(planar_ctx* ctx, int B, const int32_t* n_kf, int kf_stride, const int32_t* kf_node, const uint8_t* kf_usable,
                          const float* kf_angle, const uint8_t* kf_desc, const int32_t* n_f, int f_stride, const int32_t* f_node,
                          const float* f_angle, const uint8_t* f_desc, float nn_ratio, int check_orientation, int32_t* match, int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && n_kf && kf_node && kf_usable && kf_angle && kf_desc && n_f && f_node && f_angle && f_desc && match && nmatches, PLANAR_EINVAL,
-                   "null argument");
-    PLANAR_REQUIRE(B >= 1 && kf_stride >= 1 && f_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_bow_args(ctx, B, kf_stride, f_stride, n_kf && kf_node && kf_usable && kf_angle && kf_desc && n_f && f_node && f_angle && f_desc && match && nmatches)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const size_t nk = (size_t)B * kf_stride, nf = (size_t)B * f_stride;
-    const int a0 = s.in(n_kf, (size_t)B * 4), a1 = s.in(kf_node, nk * 4), a2 = s.in(kf_usable, nk), a3 = s.in(kf_angle, nk * 4), a4 = s.in(kf_desc, nk * 32),
-              b0 = s.in(n_f, (size_t)B * 4), b1 = s.in(f_node, nf * 4), b2 = s.in(f_angle, nf * 4), b3 = s.in(f_desc, nf * 32);
-    const int om = s.inout(match, nf * 4), on = s.out(nmatches, (size_t)B * 4);   // rows >= n_f[b] keep their value
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_search_by_bow_dev(ctx, B, s.dev<int32_t>(a0), kf_stride, s.dev<int32_t>(a1), s.dev<uint8_t>(a2), s.dev<float>(a3), s.dev<uint8_t>(a4),
-                                  s.dev<int32_t>(b0), f_stride, s.dev<int32_t>(b1), s.dev<float>(b2), s.dev<uint8_t>(b3), nn_ratio, check_orientation,
-                                  s.dev<int32_t>(om), s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B, nk = nb * kf_stride, nf = nb * f_stride;
+    const auto d_n_kf = s.in(n_kf, nb), d_kf_node = s.in(kf_node, nk);
+    const auto d_kf_usable = s.in(kf_usable, nk);
+    const auto d_kf_angle = s.in(kf_angle, nk);
+    const auto d_kf_desc = s.in(kf_desc, nk * 32);
+    const auto d_n_f = s.in(n_f, nb), d_f_node = s.in(f_node, nf);
+    const auto d_f_angle = s.in(f_angle, nf);
+    const auto d_f_desc = s.in(f_desc, nf * 32);
+    const auto d_match = s.inout(match, nf), d_n = s.out(nmatches, nb);   // rows >= n_f[b] keep their value
+    return s.run(ctx->stream, [&] {
+        return planar_search_by_bow_dev(ctx, B, d_n_kf, kf_stride, d_kf_node, d_kf_usable, d_kf_angle, d_kf_desc, d_n_f, f_stride, d_f_node, d_f_angle, d_f_desc, nn_ratio,
+                                        check_orientation, d_match, d_n);
+    });
 }
 
 int planar_lsd_search_by_projection_dev(planar_ctx* ctx, int B, const int32_t* d_n_lines, int line_stride, const planar_keyline* d_keylines,
@@ -1416,10 +1403,9 @@ int planar_lsd_search_by_projection_dev(planar_ctx* ctx, int B, const int32_t* d
                                         const uint8_t* d_ml_in_view, const float* d_ml_proj, const int32_t* d_ml_level, const float* d_ml_view_cos,
                                         const uint8_t* d_ml_desc, const uint8_t* d_ml_observed, const float* scale_factors, int n_levels, float th,
                                         float nn_ratio, int32_t* d_match, int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && d_n_lines && d_keylines && d_ldesc && d_n_ml && d_ml_in_view && d_ml_proj && d_ml_level && d_ml_view_cos && d_ml_desc &&
-                       d_ml_observed && scale_factors && d_match && d_nmatches, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && line_stride >= 1 && line_stride <= guided::MAX_LINES && ml_stride >= 1, PLANAR_EINVAL, "bad sizes (line_stride <= 1024)");
-    PLANAR_REQUIRE(n_levels >= 1 && n_levels <= PLANAR_MAX_LEVELS, PLANAR_EINVAL, "n_levels out of range");
+    if (int rc = check_lsd_projection_args(ctx, B, line_stride, ml_stride, n_levels, d_n_lines && d_keylines && d_ldesc && d_n_ml && d_ml_in_view && d_ml_proj && d_ml_level &&
+                                                                                         d_ml_view_cos && d_ml_desc && d_ml_observed && scale_factors && d_match && d_nmatches))
+        return rc;
     guided::LineArgs a{};
     a.n_lines = d_n_lines; a.n_ml = d_n_ml; a.ml_level = d_ml_level; a.keylines = d_keylines; a.ldesc = d_ldesc; a.blocked = d_blocked;
     a.ml_in_view = d_ml_in_view; a.ml_desc = d_ml_desc; a.ml_observed = d_ml_observed; a.ml_proj = d_ml_proj; a.ml_view_cos = d_ml_view_cos;
@@ -1435,33 +1421,35 @@ int planar_lsd_search_by_projection(planar_ctx* ctx, int B, const int32_t* n_lin
                                     const float* ml_proj, const int32_t* ml_level, const float* ml_view_cos, const uint8_t* ml_desc,
                                     const uint8_t* ml_observed, const float* scale_factors, int n_levels, float th, float nn_ratio, int32_t* match,
                                     int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && n_lines && keylines && ldesc && n_ml && ml_in_view && ml_proj && ml_level && ml_view_cos && ml_desc && ml_observed &&
-                       scale_factors && match && nmatches, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && line_stride >= 1 && ml_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_lsd_projection_args(ctx, B, line_stride, ml_stride, n_levels, n_lines && keylines && ldesc && n_ml && ml_in_view && ml_proj && ml_level && ml_view_cos &&
+                                                                                         ml_desc && ml_observed && scale_factors && match && nmatches))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const size_t nl = (size_t)B * line_stride, nm = (size_t)B * ml_stride;
-    const int a0 = s.in(n_lines, (size_t)B * 4), a1 = s.in(keylines, nl * sizeof(planar_keyline)), a2 = s.in(ldesc, nl * 32),
-              a3 = blocked ? s.in(blocked, nl) : -1, b0 = s.in(n_ml, (size_t)B * 4), b1 = s.in(ml_in_view, nm), b2 = s.in(ml_proj, nm * 16),
-              b3 = s.in(ml_level, nm * 4), b4 = s.in(ml_view_cos, nm * 4), b5 = s.in(ml_desc, nm * 32), b6 = s.in(ml_observed, nm);
-    const int om = s.inout(match, nl * 4), on = s.out(nmatches, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_lsd_search_by_projection_dev(ctx, B, s.dev<int32_t>(a0), line_stride, s.dev<planar_keyline>(a1), s.dev<uint8_t>(a2),
-                                             a3 >= 0 ? s.dev<uint8_t>(a3) : nullptr, s.dev<int32_t>(b0), ml_stride, s.dev<uint8_t>(b1), s.dev<float>(b2),
-                                             s.dev<int32_t>(b3), s.dev<float>(b4), s.dev<uint8_t>(b5), s.dev<uint8_t>(b6), scale_factors, n_levels, th,
-                                             nn_ratio, s.dev<int32_t>(om), s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B, nl = nb * line_stride, nm = nb * ml_stride;
+    const auto d_n_lines = s.in(n_lines, nb);
+    const auto d_keylines = s.in(keylines, nl);
+    const auto d_ldesc = s.in(ldesc, nl * 32), d_blocked = s.in(blocked, nl);
+    const auto d_n_ml = s.in(n_ml, nb);
+    const auto d_in_view = s.in(ml_in_view, nm);
+    const auto d_proj = s.in(ml_proj, nm * 4);
+    const auto d_level = s.in(ml_level, nm);
+    const auto d_cos = s.in(ml_view_cos, nm);
+    const auto d_desc = s.in(ml_desc, nm * 32), d_observed = s.in(ml_observed, nm);
+    const auto d_match = s.inout(match, nl), d_n = s.out(nmatches, nb);
+    return s.run(ctx->stream, [&] {
+        return planar_lsd_search_by_projection_dev(ctx, B, d_n_lines, line_stride, d_keylines, d_ldesc, d_blocked, d_n_ml, ml_stride, d_in_view, d_proj, d_level, d_cos, d_desc,
+                                                   d_observed, scale_factors, n_levels, th, nn_ratio, d_match, d_n);
+    });
 }
 
 int planar_plane_search_by_coefficients_dev(planar_ctx* ctx, int B, const int32_t* d_n_planes, int pl_stride, const float* d_pl_coef,
                                             const float* d_Tcw, int map_shared, const int32_t* d_n_mp, int mp_stride, const uint8_t* d_mp_valid,
                                             const float* d_mp_coef, const int32_t* d_mp_npts, int pts_stride, const float* d_mp_pts, const float* th,
                                             int32_t* d_match, int32_t* d_ver, int32_t* d_par, int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && d_n_planes && d_pl_coef && d_Tcw && d_n_mp && d_mp_valid && d_mp_coef && d_mp_npts && d_mp_pts && th && d_match && d_ver &&
-                       d_par && d_nmatches, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && pl_stride >= 1 && mp_stride >= 1 && pts_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_plane_search_args(ctx, B, pl_stride, mp_stride, pts_stride, d_n_planes && d_pl_coef && d_Tcw && d_n_mp && d_mp_valid && d_mp_coef && d_mp_npts && d_mp_pts && th &&
+                                                                                       d_match && d_ver && d_par && d_nmatches))
+        return rc;
     PLANAR_HIP_CHECK(hipMemsetAsync(d_nmatches, 0, (size_t)B * 4, ctx->stream));
     hipLaunchKernelGGL(guided::plane_match_kernel, dim3(pl_stride, B), dim3(64), 0, ctx->stream, d_n_planes, pl_stride, d_pl_coef, d_Tcw, map_shared,
                        d_n_mp, mp_stride, d_mp_valid, d_mp_coef, d_mp_npts, pts_stride, d_mp_pts, th[0], th[1], th[2], th[3], d_match, d_ver, d_par,
@@ -1474,23 +1462,24 @@ int planar_plane_search_by_coefficients(planar_ctx* ctx, int B, const int32_t* n
                                         int map_shared, const int32_t* n_mp, int mp_stride, const uint8_t* mp_valid, const float* mp_coef,
                                         const int32_t* mp_npts, int pts_stride, const float* mp_pts, const float* th, int32_t* match, int32_t* ver,
                                         int32_t* par, int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && n_planes && pl_coef && Tcw && n_mp && mp_valid && mp_coef && mp_npts && mp_pts && th && match && ver && par && nmatches,
-                   PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && pl_stride >= 1 && mp_stride >= 1 && pts_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_plane_search_args(ctx, B, pl_stride, mp_stride, pts_stride, n_planes && pl_coef && Tcw && n_mp && mp_valid && mp_coef && mp_npts && mp_pts && th && match && ver &&
+                                                                                       par && nmatches))
+        return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int MB = map_shared ? 1 : B;
-    const size_t np = (size_t)B * pl_stride, nm = (size_t)MB * mp_stride;
-    const int a0 = s.in(n_planes, (size_t)B * 4), a1 = s.in(pl_coef, np * 16), a2 = s.in(Tcw, (size_t)B * 64), b0 = s.in(n_mp, (size_t)MB * 4),
-              b1 = s.in(mp_valid, nm), b2 = s.in(mp_coef, nm * 16), b3 = s.in(mp_npts, nm * 4), b4 = s.in(mp_pts, nm * pts_stride * 12);
-    const int o0 = s.inout(match, np * 4), o1 = s.inout(ver, np * 4), o2 = s.inout(par, np * 4), on = s.out(nmatches, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_plane_search_by_coefficients_dev(ctx, B, s.dev<int32_t>(a0), pl_stride, s.dev<float>(a1), s.dev<float>(a2), map_shared, s.dev<int32_t>(b0),
-                                                 mp_stride, s.dev<uint8_t>(b1), s.dev<float>(b2), s.dev<int32_t>(b3), pts_stride, s.dev<float>(b4), th,
-                                                 s.dev<int32_t>(o0), s.dev<int32_t>(o1), s.dev<int32_t>(o2), s.dev<int32_t>(on));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B, MB = map_shared ? 1 : nb, np = nb * pl_stride, nm = MB * mp_stride;
+    const auto d_n_planes = s.in(n_planes, nb);
+    const auto d_pl_coef = s.in(pl_coef, np * 4), d_Tcw = s.in(Tcw, nb * 16);
+    const auto d_n_mp = s.in(n_mp, MB);
+    const auto d_mp_valid = s.in(mp_valid, nm);
+    const auto d_mp_coef = s.in(mp_coef, nm * 4);
+    const auto d_mp_npts = s.in(mp_npts, nm);
+    const auto d_mp_pts = s.in(mp_pts, nm * pts_stride * 3);
+    const auto d_match = s.inout(match, np), d_ver = s.inout(ver, np), d_par = s.inout(par, np), d_n = s.out(nmatches, nb);
+    return s.run(ctx->stream, [&] {
+        return planar_plane_search_by_coefficients_dev(ctx, B, d_n_planes, pl_stride, d_pl_coef, d_Tcw, map_shared, d_n_mp, mp_stride, d_mp_valid, d_mp_coef, d_mp_npts, pts_stride,
+                                                       d_mp_pts, th, d_match, d_ver, d_par, d_n);
+    });
 }
 
 }  // extern "C"

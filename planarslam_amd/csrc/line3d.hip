@@ -425,18 +425,23 @@ int planar_is_line_good(planar_ctx* ctx, int B, const planar_keyline* keylines, 
     PLANAR_REQUIRE(B >= 1 && ln_stride >= 1, PLANAR_EINVAL, "bad size");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t bl = (size_t)B * ln_stride, dbytes = ((size_t)frame_stride_px * (B - 1) + (size_t)pitch_px * height) * 2;
-    Stager S;
-    const int i_kl = S.in(keylines, bl * sizeof(planar_keyline)), i_n = S.in(n_lines, (size_t)B * 4), i_d = S.in(depth, dbytes), i_s = S.in(seeds, (size_t)B * 4),
-              i_dl = S.out(depth_line, bl * 4), i_l3 = S.out(lines3d, bl * 48), i_g = S.out(good, bl), i_dir = S.out(direction, bl * 24), i_ni = S.out(n_inliers, bl * 4),
-              i_pk = S.out(packed_dirs, bl * 24), i_ng = S.out(n_good, (size_t)B * 4);
-    int rc = S.upload(st);
-    if (rc) return rc;
-    if ((rc = planar_is_line_good_dev(ctx, B, S.dev<planar_keyline>(i_kl), S.dev<int32_t>(i_n), ln_stride, S.dev<uint16_t>(i_d), width, height, pitch_px, frame_stride_px,
-                                      depth_factor, fx, fy, cx, cy, S.dev<uint32_t>(i_s), S.dev<float>(i_dl), S.dev<double>(i_l3), S.dev<uint8_t>(i_g), S.dev<double>(i_dir),
-                                      S.dev<int32_t>(i_ni), S.dev<double>(i_pk), S.dev<int32_t>(i_ng))))
-        return rc;
-    return S.download(st);
+    const size_t bl = (size_t)B * ln_stride;
+    Stager s;
+    const auto d_kl = s.in(keylines, bl);
+    const auto d_n = s.in(n_lines, (size_t)B);
+    const auto d_depth = s.in(depth, (size_t)frame_stride_px * (B - 1) + (size_t)pitch_px * height);
+    const auto d_seeds = s.in(seeds, (size_t)B);
+    const auto d_dl = s.out(depth_line, bl);
+    const auto d_l3 = s.out(lines3d, bl * 6);
+    const auto d_good = s.out(good, bl);
+    const auto d_dir = s.out(direction, bl * 3);
+    const auto d_ni = s.out(n_inliers, bl);
+    const auto d_pk = s.out(packed_dirs, bl * 3);
+    const auto d_ng = s.out(n_good, (size_t)B);
+    return s.run(st, [&] {
+        return planar_is_line_good_dev(ctx, B, d_kl, d_n, ln_stride, d_depth, width, height, pitch_px, frame_stride_px, depth_factor, fx, fy, cx, cy, d_seeds, d_dl, d_l3, d_good, d_dir,
+                                       d_ni, d_pk, d_ng);
+    });
 }
 
 }  // extern "C"

@@ -1581,13 +1581,8 @@ struct planar_lsd {
     int top_only = 0;    // planar_lsd_set_top_only: the NFA stage only for the regions that can end among the max_lines kept key lines
     int sort_smem_g = 0, sort_smem_l = 0, sort_rows = 0, sort_rows_long = 0;
     // planar_lsd_set_profiling: HIP events around the launches of a recorded call; slots: preprocessing (two blurs, gradient, Sobel), lsd_sort, lsd_detect,
-    // the rest (improve, accept, KeyLines, LBD)
-    bool profiling = false;
-    std::vector<std::vector<hipEvent_t>> ev_sets;
-    std::vector<char> ev_complete;       // the detect half of the set was recorded too (planar_lsd_detect_dev followed planar_lsd_preprocess_dev)
-    size_t ev_used = 0;
-    std::vector<hipEvent_t>* ev_cur = nullptr;
-    ~planar_lsd() { for (auto& v : ev_sets) for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    // the rest (improve, accept, KeyLines, LBD).  planar_lsd_preprocess_dev begins a set and records events 0-2, planar_lsd_detect_dev finishes it with 3-4.
+    LaunchProfile prof{4};
 };
 
 // host mirrors of the oracle's coefficient tables (same expressions, same libm)
@@ -1725,18 +1720,9 @@ int planar_lsd_preprocess_dev(planar_lsd* o, const uint8_t* d_gray, int B, int p
     uint8_t* ws = o->d_ws.as<uint8_t>();
     lsd::Misc* dm = o->d_misc.as<lsd::Misc>();
     PLANAR_HIP_CHECK(hipMemsetAsync(dm, 0, sizeof(lsd::Misc) * (size_t)B, st));
-    o->ev_cur = nullptr;
-    if (o->profiling) {
-        if (o->ev_used == o->ev_sets.size()) {
-            std::vector<hipEvent_t> v(5);
-            for (hipEvent_t& e : v) PLANAR_HIP_CHECK(hipEventCreate(&e));
-            o->ev_sets.push_back(v);
-            o->ev_complete.push_back(0);
-        }
-        o->ev_complete[o->ev_used] = 0;
-        o->ev_cur = &o->ev_sets[o->ev_used++];
-        (void)hipEventRecord((*o->ev_cur)[0], st);
-    }
+    const int rc = o->prof.begin();
+    if (rc) return rc;
+    o->prof.mark(st);
     const dim3 gfull((unsigned)(((P.W + 63) / 64) * ((P.H + 15) / 16) * B));
     if ((P.W & 3) == 0 && (pitch & 3) == 0 && (frame_stride & 3) == 0 && ((uintptr_t)d_gray & 3) == 0 && (P.off_blur7 & 3) == 0 && (P.off_blur5 & 3) == 0 && (P.frame_bytes & 3) == 0)
         hipLaunchKernelGGL(lsd::lsd_gauss75, gfull, dim3(256), 0, st, d_gray, pitch, frame_stride, P.W, P.H, o->d_taps.as<int>(), ws, P.frame_bytes, P.off_blur7, P.off_blur5, B);
@@ -1745,7 +1731,7 @@ int planar_lsd_preprocess_dev(planar_lsd* o, const uint8_t* d_gray, int B, int p
         hipLaunchKernelGGL(lsd::lsd_gauss<5>, gfull, dim3(256), 0, st, d_gray, pitch, frame_stride, P.W, P.H, o->d_taps.as<int>() + 8, ws, P.frame_bytes, P.off_blur5, B);
     }
     hipLaunchKernelGGL(lsd::lsd_grad, dim3((P.w + 63) / 64, (P.h + 3) / 4, B), dim3(256), 0, st, dP, o->d_cx.as<lsd::Coef>(), o->d_cy.as<lsd::Coef>(), ws, dm);
-    if (o->ev_cur) (void)hipEventRecord((*o->ev_cur)[1], st);
+    o->prof.mark(st);
     if (o->tie_order != 0) hipLaunchKernelGGL(lsd::lsd_sort_raster, dim3(B), dim3(lsd::SORT_NT), 0, st, dP, ws, dm);
     else {
         hipLaunchKernelGGL(lsd::lsd_sort_global, dim3(B), dim3(lsd::SORT_T), o->sort_smem_g, st, dP, ws, dm, o->sort_rows, o->sort_rows_long);
@@ -1753,7 +1739,7 @@ int planar_lsd_preprocess_dev(planar_lsd* o, const uint8_t* d_gray, int B, int p
         hipLaunchKernelGGL(lsd::lsd_sort_heap, dim3(B, lsd::SORT_HY), dim3(64), lsd::SORT_HCAP * 4, st, dP, ws, dm);
         hipLaunchKernelGGL(lsd::lsd_sort_compact, dim3(B), dim3(lsd::SORT_T), 0, st, dP, ws, dm);
     }
-    if (o->ev_cur) (void)hipEventRecord((*o->ev_cur)[2], st);
+    o->prof.mark(st);
     PLANAR_HIP_CHECK(hipGetLastError());
     o->pre_B = B;
     return PLANAR_OK;
@@ -1767,9 +1753,11 @@ int planar_lsd_detect_dev(planar_lsd* o, int B, int max_lines, planar_keyline* d
     const lsd::Plan* dP = o->d_plan.as<lsd::Plan>();
     uint8_t* ws = o->d_ws.as<uint8_t>();
     lsd::Misc* dm = o->d_misc.as<lsd::Misc>();
-    hipLaunchKernelGGL(lsd::lsd_detect, dim3(B), dim3(64), o->detect_smem, o->ctx->seq_begin(), dP, ws, dm);      // (the context's side stream when it has one)
-    o->ctx->seq_end();
-    if (o->ev_cur) (void)hipEventRecord((*o->ev_cur)[3], st);
+    const hipStream_t sq = o->ctx->seq_begin();      // (the context's side stream when it has one)
+    hipLaunchKernelGGL(lsd::lsd_detect, dim3(B), dim3(64), o->detect_smem, sq, dP, ws, dm);
+    const int rc = o->ctx->seq_end(sq);
+    if (rc) return rc;
+    o->prof.mark(st);
     if (!o->top_only) {
         hipLaunchKernelGGL(lsd::lsd_improve, dim3(128, B), dim3(64), 0, st, dP, ws, dm, -1);   // 512 / 2048 wavefronts per frame measure the same
         hipLaunchKernelGGL(lsd::lsd_accept, dim3(B), dim3(64), 0, st, dP, ws, dm, 0);
@@ -1787,7 +1775,7 @@ int planar_lsd_detect_dev(planar_lsd* o, int B, int max_lines, planar_keyline* d
         hipLaunchKernelGGL(lsd::lsd_keylines, dim3(B), dim3(64), 0, st, dP, ws, dm, max_lines, d_keylines, d_line_eq, d_n_lines, 1);
     }
     hipLaunchKernelGGL(lsd::lbd_describe, dim3(max_lines * B), dim3(64), 0, st, dP, ws, dm, max_lines, d_ldesc, B);
-    if (o->ev_cur) { (void)hipEventRecord((*o->ev_cur)[4], st); o->ev_complete[o->ev_used - 1] = 1; o->ev_cur = nullptr; }
+    o->prof.mark(st);
     PLANAR_HIP_CHECK(hipGetLastError());
     return PLANAR_OK;
 }
@@ -1796,27 +1784,14 @@ int planar_lsd_detect_dev(planar_lsd* o, int B, int max_lines, planar_keyline* d
 int planar_lsd_set_profiling(planar_lsd* o, int enable) {
     PLANAR_REQUIRE(o != nullptr, PLANAR_EINVAL, "lsd is null");
     PLANAR_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    o->profiling = enable != 0;
-    o->ev_used = 0; o->ev_cur = nullptr;
+    o->prof.on = enable != 0;
+    o->prof.reset();
     return PLANAR_OK;
 }
 int planar_lsd_get_profile(planar_lsd* o, double* total_ms /* [4] */, int64_t* calls) {
     PLANAR_REQUIRE(o && total_ms && calls, PLANAR_EINVAL, "null argument");
     PLANAR_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    for (int i = 0; i < 4; i++) total_ms[i] = 0;
-    int64_t counted = 0;
-    for (size_t c = 0; c < o->ev_used; c++) {
-        if (!o->ev_complete[c]) continue;            // a preprocess-only call: events [3], [4] were never recorded
-        for (int i = 0; i < 4; i++) {
-            float ms = 0;
-            PLANAR_HIP_CHECK(hipEventElapsedTime(&ms, o->ev_sets[c][i], o->ev_sets[c][i + 1]));
-            total_ms[i] += ms;
-        }
-        counted++;
-    }
-    *calls = counted;
-    o->ev_used = 0;
-    return PLANAR_OK;
+    return o->prof.sum(total_ms, calls);             // a preprocess-only call is not counted: its events 3, 4 were never recorded
 }
 
 int planar_lsd_extract_dev(planar_lsd* o, const uint8_t* d_gray, int B, int pitch, int64_t frame_stride, int max_lines, planar_keyline* d_keylines,

@@ -298,19 +298,18 @@ int planar_track_manhattan_frame(planar_ctx* ctx, int B, const float* R_last, co
         PLANAR_REQUIRE(n_normals[b] >= 0 && n_normals[b] <= sn_stride && n_lines[b] >= 0 && n_lines[b] <= ln_stride, PLANAR_EINVAL, "count exceeds its stride");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int i0 = s.in(R_last, (size_t)B * 36), i1 = s.in(normals, (size_t)B * sn_stride * 12), i2 = s.in(n_normals, (size_t)B * 4),
-              i3 = s.in(line_dirs, (size_t)B * ln_stride * 24), i4 = s.in(n_lines, (size_t)B * 4);
-    const int o0 = s.out(R_out, (size_t)B * 36);
-    const int o1 = member ? s.out(member, (size_t)B * (sn_stride + ln_stride)) : -1;
-    const int o2 = info ? s.out(info, (size_t)B * 32) : -1;
-    const int o3 = density ? s.out(density, (size_t)B * 12) : -1;
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_track_manhattan_frame_dev(ctx, B, s.dev<float>(i0), s.dev<float>(i1), s.dev<int32_t>(i2), sn_stride, s.dev<double>(i3), s.dev<int32_t>(i4),
-                                          ln_stride, s.dev<float>(o0), o1 >= 0 ? s.dev<uint8_t>(o1) : nullptr, o2 >= 0 ? s.dev<int32_t>(o2) : nullptr,
-                                          o3 >= 0 ? s.dev<float>(o3) : nullptr);
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B;
+    const auto d_R_last = s.in(R_last, nb * 9), d_normals = s.in(normals, nb * sn_stride * 3);
+    const auto d_n_normals = s.in(n_normals, nb);
+    const auto d_lines = s.in(line_dirs, nb * ln_stride * 3);
+    const auto d_n_lines = s.in(n_lines, nb);
+    const auto d_R_out = s.out(R_out, nb * 9);
+    const auto d_member = s.out(member, nb * (sn_stride + ln_stride));
+    const auto d_info = s.out(info, nb * 8);
+    const auto d_density = s.out(density, nb * 3);
+    return s.run(ctx->stream, [&] {
+        return planar_track_manhattan_frame_dev(ctx, B, d_R_last, d_normals, d_n_normals, sn_stride, d_lines, d_n_lines, ln_stride, d_R_out, d_member, d_info, d_density);
+    });
 }
 
 }  // extern "C"

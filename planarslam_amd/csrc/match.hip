@@ -180,40 +180,53 @@ __global__ __launch_bounds__(64) void distinctive_kernel(const unsigned char* __
 
 using namespace planar;
 
+// one argument check per entry-point pair: the host-pointer form calls it before it touches the device, the _dev form before it launches
+static int check_knn_args(const void* ctx, const void* q, const void* nq, int q_stride, const void* t, const void* nt, int t_stride, int B, int k, const void* idx, const void* dist) {
+    PLANAR_REQUIRE(ctx && q && nq && t && nt && idx && dist, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(B >= 1 && q_stride >= 1 && t_stride >= 1 && (k == 1 || k == 2), PLANAR_EINVAL, "bad sizes (k must be 1 or 2)");
+    return PLANAR_OK;
+}
+// planar_match_orb_points (a = current, b = last, flags = {has_mp, outlier}) and planar_lsd_search_by_descriptor (a = key frame, b = current, flags = {has_ml})
+static int check_assign_args(const void* ctx, const void* a, const void* na, int a_stride, const void* b, const void* nb, int b_stride, const void* flag0, const void* flag1, int B,
+                             const void* match, const void* count) {
+    PLANAR_REQUIRE(ctx && a && na && b && nb && flag0 && flag1 && match && count, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(B >= 1 && a_stride >= 1 && b_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    return PLANAR_OK;
+}
+
 extern "C" {
 
 int planar_hamming_knn_dev(planar_ctx* ctx, const uint8_t* d_q, const int32_t* d_nq, int q_stride, const uint8_t* d_t,
                            const int32_t* d_nt, int t_stride, int B, int k, int32_t* d_idx, int32_t* d_dist) {
-    PLANAR_REQUIRE(ctx && d_q && d_nq && d_t && d_nt && d_idx && d_dist, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && q_stride >= 1 && t_stride >= 1 && (k == 1 || k == 2), PLANAR_EINVAL, "bad sizes (k must be 1 or 2)");
+    if (int rc = check_knn_args(ctx, d_q, d_nq, q_stride, d_t, d_nt, t_stride, B, k, d_idx, d_dist)) return rc;
     return match::launch_knn(ctx, d_q, d_nq, q_stride, d_t, d_nt, t_stride, B, k, d_idx, d_dist);
 }
 
 int planar_hamming_knn(planar_ctx* ctx, const uint8_t* q, const int32_t* nq, int q_stride, const uint8_t* t, const int32_t* nt,
                        int t_stride, int B, int k, int32_t* idx, int32_t* dist) {
-    PLANAR_REQUIRE(ctx && q && nq && t && nt && idx && dist, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && q_stride >= 1 && t_stride >= 1 && (k == 1 || k == 2), PLANAR_EINVAL, "bad sizes (k must be 1 or 2)");
+    if (int rc = check_knn_args(ctx, q, nq, q_stride, t, nt, t_stride, B, k, idx, dist)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int iq = s.in(q, (size_t)B * q_stride * 32), inq = s.in(nq, (size_t)B * 4), it = s.in(t, (size_t)B * t_stride * 32), int_ = s.in(nt, (size_t)B * 4);
-    const int ii = s.out(idx, (size_t)B * q_stride * k * 4), id = s.out(dist, (size_t)B * q_stride * k * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    PLANAR_HIP_CHECK(hipMemsetAsync(s.dev<int32_t>(ii), 0xff, (size_t)B * q_stride * k * 4, ctx->stream));
-    PLANAR_HIP_CHECK(hipMemsetAsync(s.dev<int32_t>(id), 0, (size_t)B * q_stride * k * 4, ctx->stream));
-    rc = match::launch_knn(ctx, s.dev<uint8_t>(iq), s.dev<int32_t>(inq), q_stride, s.dev<uint8_t>(it), s.dev<int32_t>(int_), t_stride, B, k,
-                           s.dev<int32_t>(ii), s.dev<int32_t>(id));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B, n_out = nb * q_stride * k;
+    const auto d_q = s.in(q, nb * q_stride * 32);
+    const auto d_nq = s.in(nq, nb);
+    const auto d_t = s.in(t, nb * t_stride * 32);
+    const auto d_nt = s.in(nt, nb);
+    const auto d_idx = s.out(idx, n_out), d_dist = s.out(dist, n_out);
+    return s.run(ctx->stream, [&]() -> int {
+        PLANAR_HIP_CHECK(hipMemsetAsync(d_idx, 0xff, n_out * 4, ctx->stream));
+        PLANAR_HIP_CHECK(hipMemsetAsync(d_dist, 0, n_out * 4, ctx->stream));
+        return match::launch_knn(ctx, d_q, d_nq, q_stride, d_t, d_nt, t_stride, B, k, d_idx, d_dist);
+    });
 }
 
 int planar_match_orb_points_dev(planar_ctx* ctx, const uint8_t* d_cur, const int32_t* d_n_cur, int cur_stride, const uint8_t* d_last,
                                 const int32_t* d_n_last, int last_stride, const uint8_t* d_last_has_mp, const uint8_t* d_last_outlier,
                                 int B, int32_t* d_cur_match, int32_t* d_npair) {
-    PLANAR_REQUIRE(ctx && d_cur && d_n_cur && d_last && d_n_last && d_last_has_mp && d_last_outlier && d_cur_match && d_npair, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && cur_stride >= 1 && last_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    int rc = check_assign_args(ctx, d_cur, d_n_cur, cur_stride, d_last, d_n_last, last_stride, d_last_has_mp, d_last_outlier, B, d_cur_match, d_npair);
+    if (rc) return rc;
     const size_t n = (size_t)B * cur_stride;
-    int rc = ctx->ensure_scratch(2 * n * 4);
+    rc = ctx->ensure_scratch(2 * n * 4);
     if (rc) return rc;
     int32_t* idx = ctx->scratch.as<int32_t>();
     int32_t* dist = idx + n;
@@ -228,28 +241,26 @@ int planar_match_orb_points_dev(planar_ctx* ctx, const uint8_t* d_cur, const int
 int planar_match_orb_points(planar_ctx* ctx, const uint8_t* cur, const int32_t* n_cur, int cur_stride, const uint8_t* last,
                             const int32_t* n_last, int last_stride, const uint8_t* last_has_mp, const uint8_t* last_outlier, int B,
                             int32_t* cur_match, int32_t* npair) {
-    PLANAR_REQUIRE(ctx && cur && n_cur && last && n_last && last_has_mp && last_outlier && cur_match && npair, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && cur_stride >= 1 && last_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_assign_args(ctx, cur, n_cur, cur_stride, last, n_last, last_stride, last_has_mp, last_outlier, B, cur_match, npair)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int a = s.in(cur, (size_t)B * cur_stride * 32), b = s.in(n_cur, (size_t)B * 4), c = s.in(last, (size_t)B * last_stride * 32),
-              d = s.in(n_last, (size_t)B * 4), e = s.in(last_has_mp, (size_t)B * last_stride), f = s.in(last_outlier, (size_t)B * last_stride);
-    const int g = s.inout(cur_match, (size_t)B * cur_stride * 4), h = s.out(npair, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_match_orb_points_dev(ctx, s.dev<uint8_t>(a), s.dev<int32_t>(b), cur_stride, s.dev<uint8_t>(c), s.dev<int32_t>(d), last_stride,
-                                     s.dev<uint8_t>(e), s.dev<uint8_t>(f), B, s.dev<int32_t>(g), s.dev<int32_t>(h));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B;
+    const auto d_cur = s.in(cur, nb * cur_stride * 32);
+    const auto d_n_cur = s.in(n_cur, nb);
+    const auto d_last = s.in(last, nb * last_stride * 32);
+    const auto d_n_last = s.in(n_last, nb);
+    const auto d_has_mp = s.in(last_has_mp, nb * last_stride), d_outlier = s.in(last_outlier, nb * last_stride);
+    const auto d_match = s.inout(cur_match, nb * cur_stride), d_npair = s.out(npair, nb);
+    return s.run(ctx->stream, [&] { return planar_match_orb_points_dev(ctx, d_cur, d_n_cur, cur_stride, d_last, d_n_last, last_stride, d_has_mp, d_outlier, B, d_match, d_npair); });
 }
 
 int planar_lsd_search_by_descriptor_dev(planar_ctx* ctx, const uint8_t* d_kf, const int32_t* d_n_kf, int kf_stride, const uint8_t* d_cur,
                                         const int32_t* d_n_cur, int cur_stride, const uint8_t* d_kf_has_ml, int B, int32_t* d_cur_match,
                                         int32_t* d_nmatches) {
-    PLANAR_REQUIRE(ctx && d_kf && d_n_kf && d_cur && d_n_cur && d_kf_has_ml && d_cur_match && d_nmatches, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && kf_stride >= 1 && cur_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    int rc = check_assign_args(ctx, d_kf, d_n_kf, kf_stride, d_cur, d_n_cur, cur_stride, d_kf_has_ml, d_kf_has_ml, B, d_cur_match, d_nmatches);
+    if (rc) return rc;
     const size_t n = (size_t)B * kf_stride * 2;
-    int rc = ctx->ensure_scratch(2 * n * 4);
+    rc = ctx->ensure_scratch(2 * n * 4);
     if (rc) return rc;
     int32_t* idx = ctx->scratch.as<int32_t>();
     int32_t* dist = idx + n;
@@ -264,19 +275,17 @@ int planar_lsd_search_by_descriptor_dev(planar_ctx* ctx, const uint8_t* d_kf, co
 int planar_lsd_search_by_descriptor(planar_ctx* ctx, const uint8_t* kf, const int32_t* n_kf, int kf_stride, const uint8_t* cur,
                                     const int32_t* n_cur, int cur_stride, const uint8_t* kf_has_ml, int B, int32_t* cur_match,
                                     int32_t* nmatches) {
-    PLANAR_REQUIRE(ctx && kf && n_kf && cur && n_cur && kf_has_ml && cur_match && nmatches, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(B >= 1 && kf_stride >= 1 && cur_stride >= 1, PLANAR_EINVAL, "bad sizes");
+    if (int rc = check_assign_args(ctx, kf, n_kf, kf_stride, cur, n_cur, cur_stride, kf_has_ml, kf_has_ml, B, cur_match, nmatches)) return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int a = s.in(kf, (size_t)B * kf_stride * 32), b = s.in(n_kf, (size_t)B * 4), c = s.in(cur, (size_t)B * cur_stride * 32),
-              d = s.in(n_cur, (size_t)B * 4), e = s.in(kf_has_ml, (size_t)B * kf_stride);
-    const int g = s.out(cur_match, (size_t)B * cur_stride * 4), h = s.out(nmatches, (size_t)B * 4);
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    rc = planar_lsd_search_by_descriptor_dev(ctx, s.dev<uint8_t>(a), s.dev<int32_t>(b), kf_stride, s.dev<uint8_t>(c), s.dev<int32_t>(d),
-                                             cur_stride, s.dev<uint8_t>(e), B, s.dev<int32_t>(g), s.dev<int32_t>(h));
-    if (rc) return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B;
+    const auto d_kf = s.in(kf, nb * kf_stride * 32);
+    const auto d_n_kf = s.in(n_kf, nb);
+    const auto d_cur = s.in(cur, nb * cur_stride * 32);
+    const auto d_n_cur = s.in(n_cur, nb);
+    const auto d_has_ml = s.in(kf_has_ml, nb * kf_stride);
+    const auto d_match = s.out(cur_match, nb * cur_stride), d_n = s.out(nmatches, nb);
+    return s.run(ctx->stream, [&] { return planar_lsd_search_by_descriptor_dev(ctx, d_kf, d_n_kf, kf_stride, d_cur, d_n_cur, cur_stride, d_has_ml, B, d_match, d_n); });
 }
 
 int planar_distinctive_descriptors_dev(planar_ctx* ctx, int n_points, const uint8_t* d_desc, const int32_t* d_off, int max_obs, int32_t* d_best, int32_t* d_median) {
@@ -297,12 +306,10 @@ int planar_distinctive_descriptors(planar_ctx* ctx, int n_points, const uint8_t*
     PLANAR_REQUIRE(max_obs <= 2047, PLANAR_EINVAL, "a map point may have at most 2047 observations");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int i_d = s.in(desc, (size_t)off[n_points] * 32), i_o = s.in(off, (size_t)(n_points + 1) * 4), o_b = s.out(best, (size_t)n_points * 4),
-              o_m = median ? s.out(median, (size_t)n_points * 4) : -1;
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    if ((rc = planar_distinctive_descriptors_dev(ctx, n_points, s.dev<uint8_t>(i_d), s.dev<int32_t>(i_o), max_obs, s.dev<int32_t>(o_b), median ? s.dev<int32_t>(o_m) : nullptr))) return rc;
-    return s.download(ctx->stream);
+    const auto d_desc = s.in(desc, (size_t)off[n_points] * 32);
+    const auto d_off = s.in(off, (size_t)n_points + 1);
+    const auto d_best = s.out(best, (size_t)n_points), d_median = s.out(median, (size_t)n_points);
+    return s.run(ctx->stream, [&] { return planar_distinctive_descriptors_dev(ctx, n_points, d_desc, d_off, max_obs, d_best, d_median); });
 }
 
 }  // extern "C"

@@ -855,14 +855,9 @@ struct planar_orb {
         d_kept, d_kept_count, d_dropped;
     // staging for the host-pointer entry point
     DevBuf d_in, d_kps, d_desc, d_nout;
-    // optional per-launch HIP-event timing (planar_orb_set_profiling)
-    bool profiling = false;
-    std::vector<std::vector<hipEvent_t>> ev_sets;   // one set of (launches+1) events per recorded call
-    size_t ev_used = 0;
     std::vector<const char*> launch_names;          // kernel name per launch of one extract call
-    ~planar_orb() {
-        for (auto& v : ev_sets) for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
+    LaunchProfile prof;                             // optional per-launch HIP-event timing (planar_orb_set_profiling): one slot per launch
+    explicit planar_orb(int nlevels) : prof(nlevels + 5) {}
 };
 
 static inline int cv_round_f(float v) { return (int)nearbyintf(v); }
@@ -883,7 +878,7 @@ int planar_orb_create(planar_ctx* ctx, const planar_orb_params* p, int W, int H,
     PLANAR_REQUIRE(max_batch >= 1, PLANAR_EINVAL, "max_batch must be >= 1");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
 
-    planar_orb* o = new (std::nothrow) planar_orb();
+    planar_orb* o = new (std::nothrow) planar_orb(p->nlevels);
     PLANAR_REQUIRE(o != nullptr, PLANAR_ENOMEM, "host allocation failed");
     o->ctx = ctx; o->params = *p; o->W = W; o->H = H; o->max_batch = max_batch;
     const int nl = p->nlevels;
@@ -1060,8 +1055,8 @@ void planar_orb_destroy(planar_orb* o) { delete o; }
 int planar_orb_set_profiling(planar_orb* o, int enable) {
     PLANAR_REQUIRE(o != nullptr, PLANAR_EINVAL, "orb is null");
     PLANAR_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    o->profiling = enable != 0;
-    o->ev_used = 0;
+    o->prof.on = enable != 0;
+    o->prof.reset();
     return PLANAR_OK;
 }
 
@@ -1074,17 +1069,7 @@ const char* planar_orb_profile_launch_name(const planar_orb* o, int i) {
 int planar_orb_get_profile(planar_orb* o, double* total_ms, int64_t* calls) {
     PLANAR_REQUIRE(o && total_ms && calls, PLANAR_EINVAL, "null argument");
     PLANAR_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
-    const size_t nl = o->launch_names.size();
-    for (size_t i = 0; i < nl; i++) total_ms[i] = 0;
-    for (size_t c = 0; c < o->ev_used; c++)
-        for (size_t i = 0; i < nl; i++) {
-            float ms = 0;
-            PLANAR_HIP_CHECK(hipEventElapsedTime(&ms, o->ev_sets[c][i], o->ev_sets[c][i + 1]));
-            total_ms[i] += ms;
-        }
-    *calls = (int64_t)o->ev_used;
-    o->ev_used = 0;
-    return PLANAR_OK;
+    return o->prof.sum(total_ms, calls);
 }
 
 int planar_orb_max_keypoints(const planar_orb* o) { return o ? o->plan.kp_cap : PLANAR_EINVAL; }
@@ -1121,18 +1106,9 @@ int planar_orb_extract_dev(planar_orb* o, const uint8_t* d_gray, int B, int pitc
     const PlanDev& P = o->plan;
     const PlanDev* dp = o->d_plan.as<PlanDev>();
     uint8_t* pyr = o->d_pyr.as<uint8_t>();
-    std::vector<hipEvent_t>* evs = nullptr;
-    if (o->profiling) {
-        const size_t need = (size_t)P.nlevels + 5 + 1;
-        if (o->ev_used == o->ev_sets.size()) {
-            std::vector<hipEvent_t> v(need);
-            for (size_t i = 0; i < need; i++) PLANAR_HIP_CHECK(hipEventCreate(&v[i]));
-            o->ev_sets.push_back(v);
-        }
-        evs = &o->ev_sets[o->ev_used++];
-    }
-    int li = 0;
-    auto mark = [&]() { if (evs) (void)hipEventRecord((*evs)[li], st); li++; };
+    const int rc = o->prof.begin();
+    if (rc) return rc;
+    auto mark = [&]() { o->prof.mark(st); };
     mark();
     {
         const int n = (P.lv[0].pitch / 4) * P.lv[0].h;

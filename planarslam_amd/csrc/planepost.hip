@@ -952,10 +952,7 @@ struct planar_plane_clouds {
     std::vector<int32_t> last_status;           // per-frame codes of the last host-pointer compute call
     // planar_plane_clouds_set_profiling: HIP events around the launches of a recorded call; slots: plane_voxels, plane_items, plane_sort_global, plane_sort_lds,
     // plane_sort_heap (three launches), plane_tail
-    bool profiling = false;
-    std::vector<std::vector<hipEvent_t>> ev_sets;
-    size_t ev_used = 0;
-    ~planar_plane_clouds() { for (auto& v : ev_sets) for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    planar::LaunchProfile prof{6};
 };
 
 using namespace planar;
@@ -1063,23 +1060,14 @@ int planar_plane_clouds_read_timing(planar_plane_clouds* p, int B, int64_t* out)
 int planar_plane_clouds_set_profiling(planar_plane_clouds* p, int enable) {
     PLANAR_REQUIRE(p != nullptr, PLANAR_EINVAL, "null argument");
     PLANAR_HIP_CHECK(hipStreamSynchronize(p->ctx->stream));
-    p->profiling = enable != 0;
-    p->ev_used = 0;
+    p->prof.on = enable != 0;
+    p->prof.reset();
     return PLANAR_OK;
 }
 int planar_plane_clouds_get_profile(planar_plane_clouds* p, double* total_ms /* [6] */, int64_t* calls) {
     PLANAR_REQUIRE(p && total_ms && calls, PLANAR_EINVAL, "null argument");
     PLANAR_HIP_CHECK(hipStreamSynchronize(p->ctx->stream));
-    for (int i = 0; i < 6; i++) total_ms[i] = 0;
-    for (size_t c = 0; c < p->ev_used; c++)
-        for (int i = 0; i < 6; i++) {
-            float ms = 0;
-            PLANAR_HIP_CHECK(hipEventElapsedTime(&ms, p->ev_sets[c][i], p->ev_sets[c][i + 1]));
-            total_ms[i] += ms;
-        }
-    *calls = (int64_t)p->ev_used;
-    p->ev_used = 0;
-    return PLANAR_OK;
+    return p->prof.sum(total_ms, calls);
 }
 
 // diagnostics: per frame of the last call {ranges left to libstdc++'s heap-sort fallback, their elements, the longest, LDS-tier blocks}
@@ -1122,17 +1110,9 @@ int planar_plane_clouds_compute_dev(planar_plane_clouds* p, const uint16_t* d_de
     hipStream_t st = p->ctx->stream;
     unsigned char* ws = p->ws.as<unsigned char>();
     long long* tm = p->timing ? p->dbg.as<long long>() : nullptr;
-    std::vector<hipEvent_t>* evs = nullptr;
-    if (p->profiling) {
-        if (p->ev_used == p->ev_sets.size()) {
-            std::vector<hipEvent_t> v(7);
-            for (hipEvent_t& e : v) PLANAR_HIP_CHECK(hipEventCreate(&e));
-            p->ev_sets.push_back(v);
-        }
-        evs = &p->ev_sets[p->ev_used++];
-    }
-    int li = 0;
-    auto mark = [&]() { if (evs) (void)hipEventRecord((*evs)[li], st); li++; };
+    const int rc = p->prof.begin();
+    if (rc) return rc;
+    auto mark = [&]() { p->prof.mark(st); };
     mark();
     hipLaunchKernelGGL(planepost::plane_voxels_kernel, dim3(B), dim3(planepost::NT), p->smem, st, G, d_depth, pitch_px, (long)frame_stride_px, d_labels, d_n_planes, ws, tm);
     mark();
@@ -1173,23 +1153,24 @@ int planar_plane_clouds_compute(planar_plane_clouds* p, const uint16_t* depth, i
     PLANAR_HIP_CHECK(hipSetDevice(p->ctx->device));
     const int PS = p->G.pl_stride, MP = p->G.max_points, HW = p->G.W * p->G.H;
     Stager s;
-    const int i_depth = s.in(depth, ((size_t)frame_stride_px * (B - 1) + (size_t)pitch_px * p->G.H) * 2), i_lab = s.in(labels, (size_t)B * HW * 4),
-              i_pl = s.in(planes, (size_t)B * planar_peac_max_planes() * 64), i_np = s.in(n_planes, (size_t)B * 4);
-    const int o_n = s.out(n_out, (size_t)B * 4), o_coef = s.out(coef, (size_t)B * PS * 16), o_src = s.out(src, (size_t)B * PS * 4),
-              o_off = s.out(pt_off, (size_t)B * (PS + 1) * 4), o_pts = s.out(points, (size_t)B * MP * 12);
+    const size_t nb = (size_t)B;
+    const auto d_depth = s.in(depth, (size_t)frame_stride_px * (B - 1) + (size_t)pitch_px * p->G.H);
+    const auto d_lab = s.in(labels, nb * HW);
+    const auto d_pl = s.in(planes, nb * planar_peac_max_planes() * 8);
+    const auto d_np = s.in(n_planes, nb);
+    const auto o_n = s.out(n_out, nb);                       // the first output: zero_from(o_n) below
+    const auto o_coef = s.out(coef, nb * PS * 4);
+    const auto o_src = s.out(src, nb * PS), o_off = s.out(pt_off, nb * (PS + 1));
+    const auto o_pts = s.out(points, nb * MP * 3);
     std::vector<int32_t> h_status(B);
-    const int o_st = s.out(h_status.data(), (size_t)B * 4);
-    const int o_state = state ? s.out(state, (size_t)B * PS * 4) : -1, o_nvox = nvox ? s.out(nvox, (size_t)B * PS * 4) : -1,
-              o_info = info ? s.out(info, (size_t)B * PS * 48) : -1;
+    const auto o_st = s.out(h_status.data(), nb), o_state = s.out(state, nb * PS), o_nvox = s.out(nvox, nb * PS), o_info = s.out(info, nb * PS * 12);
     hipStream_t st = p->ctx->stream;
     int rc = s.upload(st);
     if (rc) return rc;
     // outputs not written for dropped planes are defined (zero)
-    PLANAR_HIP_CHECK(hipMemsetAsync(s.dev<uint8_t>(o_n), 0, s.total - s.items[o_n].off, st));
-    if ((rc = planar_plane_clouds_compute_dev(p, s.dev<uint16_t>(i_depth), B, pitch_px, frame_stride_px, fx, fy, cx, cy, depth_factor, s.dev<int32_t>(i_lab), s.dev<double>(i_pl),
-                                              s.dev<int32_t>(i_np), dist_th, leaf, s.dev<int32_t>(o_n), s.dev<float>(o_coef), s.dev<int32_t>(o_src), s.dev<int32_t>(o_off),
-                                              s.dev<float>(o_pts), s.dev<int32_t>(o_st), state ? s.dev<int32_t>(o_state) : nullptr, nvox ? s.dev<int32_t>(o_nvox) : nullptr,
-                                              info ? s.dev<int32_t>(o_info) : nullptr)))
+    PLANAR_HIP_CHECK(s.zero_from(o_n, st));
+    if ((rc = planar_plane_clouds_compute_dev(p, d_depth, B, pitch_px, frame_stride_px, fx, fy, cx, cy, depth_factor, d_lab, d_pl, d_np, dist_th, leaf, o_n, o_coef, o_src, o_off,
+                                              o_pts, o_st, o_state, o_nvox, o_info)))
         return rc;
     if ((rc = s.download(st))) return rc;
     p->last_status = h_status;                  // planar_plane_clouds_last_status: the per-frame codes of this call, for callers that branch on them
@@ -1213,8 +1194,10 @@ int planar_plane_refit(planar_plane_clouds* p, int n_clouds, const float* points
     for (int q = 0; q < n_clouds; q++) { PLANAR_REQUIRE(pt_off[q + 1] >= pt_off[q], PLANAR_EINVAL, "pt_off must be non-decreasing"); max_n = std::max(max_n, pt_off[q + 1] - pt_off[q]); }
     PLANAR_REQUIRE(max_n <= 32768 && pt_off[0] == 0, PLANAR_EINVAL, "a cloud may hold at most 32768 points");
     Stager s;
-    const int i_pts = s.in(points, (size_t)pt_off[n_clouds] * 12), i_off = s.in(pt_off, (size_t)(n_clouds + 1) * 4), io_pl = s.inout(planes, (size_t)n_clouds * 16),
-              o_st = s.out(state, (size_t)n_clouds * 4), o_info = info ? s.out(info, (size_t)n_clouds * 48) : -1;
+    const auto d_pts = s.in(points, (size_t)pt_off[n_clouds] * 3);
+    const auto d_off = s.in(pt_off, (size_t)n_clouds + 1);
+    const auto io_pl = s.inout(planes, (size_t)n_clouds * 4);
+    const auto o_st = s.out(state, (size_t)n_clouds), o_info = s.out(info, (size_t)n_clouds * 12);
     hipStream_t st = p->ctx->stream;
     int rc = s.upload(st);
     if (rc) return rc;
@@ -1222,8 +1205,7 @@ int planar_plane_refit(planar_plane_clouds* p, int n_clouds, const float* points
     G.dist_th = dist_th;
     const size_t smem = align_up((size_t)std::max(max_n, 1) * 2, (size_t)16);
     if (smem > 40 * 1024) PLANAR_HIP_CHECK(hipFuncSetAttribute((const void*)planepost::refit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(planepost::refit_kernel, dim3(n_clouds), dim3(64), smem, st, G, n_clouds, s.dev<float>(i_pts), s.dev<int>(i_off), p->rng.as<int>(), s.dev<float>(io_pl),
-                       s.dev<int>(o_st), info ? s.dev<int>(o_info) : nullptr);
+    hipLaunchKernelGGL(planepost::refit_kernel, dim3(n_clouds), dim3(64), smem, st, G, n_clouds, d_pts, d_off, p->rng.as<int>(), io_pl, o_st, o_info);
     PLANAR_HIP_CHECK(hipGetLastError());
     return s.download(st);
 }
@@ -1246,14 +1228,14 @@ int planar_flag_matched_plane_points(planar_ctx* ctx, int B, const float* Tcw, c
     PLANAR_REQUIRE(B >= 1 && n_points >= 0 && pl_stride >= 1, PLANAR_EINVAL, "bad size");
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
-    const int i_T = s.in(Tcw, (size_t)B * 64), i_c = s.in(coef, (size_t)B * pl_stride * 16), i_m = s.in(matched, (size_t)B * pl_stride), i_n = s.in(n_planes, (size_t)B * 4),
-              i_x = s.in(xw, (size_t)(points_shared ? 1 : B) * n_points * 12), io_f = s.inout(flags, (size_t)B * n_points), o_nm = n_matches ? s.out(n_matches, (size_t)B * 4) : -1;
-    int rc = s.upload(ctx->stream);
-    if (rc) return rc;
-    if ((rc = planar_flag_matched_plane_points_dev(ctx, B, s.dev<float>(i_T), s.dev<float>(i_c), s.dev<uint8_t>(i_m), s.dev<int32_t>(i_n), pl_stride, s.dev<float>(i_x), n_points,
-                                                   points_shared, s.dev<uint8_t>(io_f), n_matches ? s.dev<int32_t>(o_nm) : nullptr)))
-        return rc;
-    return s.download(ctx->stream);
+    const size_t nb = (size_t)B;
+    const auto d_T = s.in(Tcw, nb * 16), d_c = s.in(coef, nb * pl_stride * 4);
+    const auto d_m = s.in(matched, nb * pl_stride);
+    const auto d_n = s.in(n_planes, nb);
+    const auto d_x = s.in(xw, (size_t)(points_shared ? 1 : B) * n_points * 3);
+    const auto io_f = s.inout(flags, nb * n_points);
+    const auto o_nm = s.out(n_matches, nb);
+    return s.run(ctx->stream, [&] { return planar_flag_matched_plane_points_dev(ctx, B, d_T, d_c, d_m, d_n, pl_stride, d_x, n_points, points_shared, io_f, o_nm); });
 }
 
 int planar_merge_plane_points(planar_plane_clouds* p, const double* Twc, const float* frame_points, int n_frame, const float* map_points, int n_map, float leaf,
@@ -1263,31 +1245,32 @@ int planar_merge_plane_points(planar_plane_clouds* p, const double* Twc, const f
     PLANAR_HIP_CHECK(hipSetDevice(p->ctx->device));
     const int n = n_frame + n_map;
     Stager s;
-    const int i_T = s.in(Twc, 128), i_f = s.in(frame_points, (size_t)n_frame * 12), i_m = s.in(map_points, (size_t)n_map * 12), t_all = s.add(nullptr, nullptr, (size_t)std::max(n, 1) * 12),
-              t_out = s.add(nullptr, nullptr, (size_t)p->G.max_points * 12);
+    const auto d_T = s.in(Twc, 16);
+    const auto d_f = s.in(frame_points, (size_t)n_frame * 3), d_m = s.in(map_points, (size_t)n_map * 3);     // (null when there are none)
+    const auto t_all = s.temp<float>((size_t)std::max(n, 1) * 3), t_out = s.temp<float>((size_t)p->G.max_points * 3);
     int32_t h[2] = {0, 0};
-    const int o_h = s.out(h, 8);
+    const auto o_h = s.out(h, 2);
     hipStream_t st = p->ctx->stream;
     int rc = s.upload(st);
     if (rc) return rc;
     planepost::Geo G = p->G;
     G.leaf = leaf;
-    if (n) hipLaunchKernelGGL(planepost::merge_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, s.dev<double>(i_T), s.dev<float>(i_f), n_frame, s.dev<float>(i_m), n_map, s.dev<float>(t_all));
+    if (n) hipLaunchKernelGGL(planepost::merge_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_T, d_f, n_frame, d_m, n_map, t_all);
     unsigned char* ws = p->ws.as<unsigned char>();
-    hipLaunchKernelGGL(planepost::cloud_voxels_kernel, dim3(1), dim3(planepost::NT), p->smem_cloud, st, G, s.dev<float>(t_all), n, ws);
+    hipLaunchKernelGGL(planepost::cloud_voxels_kernel, dim3(1), dim3(planepost::NT), p->smem_cloud, st, G, t_all, n, ws);
     hipLaunchKernelGGL(planepost::plane_sort_global<planepost::PS_SHIFT>, dim3(1), dim3(planepost::PS_T), p->smem_sort_g, st, G, ws, p->sort_rows);
     hipLaunchKernelGGL(planepost::plane_sort_lds<planepost::PS_SHIFT>, dim3(1, planepost::PS_EARLY + planepost::PS_R), dim3(planepost::PS_LT), p->smem_sort_l, st, G, ws);
     for (int c = 0; c < 2; c++) {                            // the LDS tier's fallback jobs (the global tier's ran inside plane_sort_lds)
         const planepost::HeapClass& H = planepost::PS_HC[c];
         hipLaunchKernelGGL(planepost::plane_sort_heap<planepost::PS_SHIFT>, dim3(1, H.wgs), dim3(64 * H.waves), (size_t)H.cap * 4 * H.waves, st, G, ws, 1, c ? planepost::PS_HC[c - 1].max_len + 1 : 0, H.max_len, H.cap);
     }
-    hipLaunchKernelGGL(planepost::cloud_sums_kernel, dim3(1), dim3(planepost::NT), 0, st, G, s.dev<float>(t_all), ws, s.dev<float>(t_out), s.dev<int>(o_h), s.dev<int>(o_h) + 1);
+    hipLaunchKernelGGL(planepost::cloud_sums_kernel, dim3(1), dim3(planepost::NT), 0, st, G, t_all, ws, t_out, o_h, o_h + 1);
     PLANAR_HIP_CHECK(hipGetLastError());
     if ((rc = s.download(st))) return rc;
     if (h[1]) { set_error("merge_plane_points: more than %d voxels, voxel index overflow, or a std::sort order that is not reproducible (code %d)", p->G.max_points, h[1]); return PLANAR_ECAPACITY; }
     PLANAR_REQUIRE(h[0] <= out_cap, PLANAR_ECAPACITY, "out_cap too small");
     *n_out = h[0];
-    if (h[0]) PLANAR_HIP_CHECK(hipMemcpy(out_points, s.dev<float>(t_out), (size_t)h[0] * 12, hipMemcpyDeviceToHost));
+    if (h[0]) PLANAR_HIP_CHECK(hipMemcpy(out_points, t_out, (size_t)h[0] * 12, hipMemcpyDeviceToHost));
     return PLANAR_OK;
 }
 
