@@ -327,6 +327,66 @@ int planar_search_by_bow_dev(planar_ctx* ctx, int B, const int32_t* d_n_kf, int 
                              int f_stride, const int32_t* d_f_node, const float* d_f_angle, const uint8_t* d_f_desc, float nn_ratio,
                              int check_orientation, int32_t* d_match, int32_t* d_nmatches);
 
+/* ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:309-540): epipolar BoW search + triangulation ---------------------------- */
+#define PLANAR_TRI_MAX_NEIGHBOURS 32 /* limit on the neighbours per current key frame (the reference asks for 10, 20 when monocular) */
+
+/* What the key frames of one call share (include/KeyFrame.h): intrinsics, mfScaleFactor, mvScaleFactors, mvLevelSigma2. */
+typedef struct planar_tri_camera {
+    float fx, fy, cx, cy, invfx, invfy;         /* KeyFrame::fx .. invfy, as the key frame stores them; mK = [fx 0 cx; 0 fy cy; 0 0 1] */
+    float scale_factor;                         /* mfScaleFactor (ratioFactor = 1.5f * mfScaleFactor)                                 */
+    int32_t n_levels;                           /* mnScaleLevels, 1 .. PLANAR_MAX_LEVELS; key-point octaves must lie below it         */
+    float scale_factors[PLANAR_MAX_LEVELS];     /* mvScaleFactors                                                                     */
+    float level_sigma2[PLANAR_MAX_LEVELS];      /* mvLevelSigma2                                                                      */
+} planar_tri_camera;
+
+/* `count` key frames, [count][stride] arrays.  The second group is read by planar_create_new_map_points only (NULL for the search). */
+typedef struct planar_tri_keyframes {
+    int32_t count, stride;           /* stride <= PLANAR_MAX_FRAME_KEYS                                                     */
+    const int32_t* n;                /* [count]             KeyFrame::N                                                      */
+    const planar_keypoint* keys_un;  /* [count][stride]     mvKeysUn (pt, angle, octave are read)                            */
+    const float* u_right;            /* [count][stride]     mvuRight (>= 0: stereo)                                          */
+    const uint8_t* desc;             /* [count][stride][32] mDescriptors; the array must start on a 16-byte boundary (read as 16-byte words) */
+    const int32_t* node;             /* [count][stride]     mFeatVec as planar_bow_transform writes it: node id, -1 = none   */
+    const uint8_t* occupied;         /* [count][stride]     GetMapPoint(i) != NULL on entry                                  */
+    const float* Tcw;                /* [count][16]         Tcw; Ow is derived as KeyFrame::SetPose does (src/KeyFrame.cc:79-93) */
+    const planar_keypoint* keys;     /* [count][stride]     mvKeys: KeyFrame::UnprojectStereo reads the DISTORTED point      */
+    const float* depth;              /* [count][stride]     mvDepth (> 0 wherever u_right >= 0)                              */
+    const float* cos_stereo;         /* [count][stride]     cos(2 * atan2(mb / 2, mvDepth[i])) in float, by the HOST's libm  */
+    const float* Twc;                /* [count][16]         Twc as the key frame holds it (UnprojectStereo)                  */
+    const float* mb;                 /* [count]             KeyFrame::mb                                                     */
+    const float* mbf;                /* [count]             KeyFrame::mbf                                                    */
+} planar_tri_keyframes;
+
+/* ORBmatcher(., check_orientation)::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:661-827) with
+ * F12 = LocalMapping::ComputeF12(pKF1, pKF2) (src/LocalMapping.cc:1141-1157), for kf1->count (key frame 1, key frame 2) pairs: pair b is
+ * entry b of both views.  Kept as the reference has them: vbMatched2 is never set, so two features of key frame 1 may take the same feature of
+ * key frame 2; the smallest distance <= 50 among the candidates that pass every gate wins and the LAST such candidate (ascending idx2) on a tie.
+ *   match12[b][idx1] (out, idx1 < n): vMatches12[idx1], the index in key frame 2 or -1; vMatchedPairs is its ascending-idx1 read.
+ *   nmatches[b]: the function's return value. */
+int planar_search_for_triangulation(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_keyframes* kf1, const planar_tri_keyframes* kf2,
+                                    int only_stereo, int check_orientation, int32_t* match12, int32_t* nmatches);
+int planar_search_for_triangulation_dev(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_keyframes* d_kf1,
+                                        const planar_tri_keyframes* d_kf2, int only_stereo, int check_orientation, int32_t* d_match12,
+                                        int32_t* d_nmatches);
+
+/* LocalMapping::CreateNewMapPoints for cur->count current key frames (RGB-D / stereo: mbMonocular == false).  Current key frame b has
+ * n_neigh[b] <= max_neigh neighbours, GetBestCovisibilityKeyFrames' order, at entries b * max_neigh + k of `neigh`.  The reference leaves
+ * the loop when CheckNewKeyFrames() turns true (:341): a caller that wants to stop early passes fewer neighbours.
+ *   n_new[b]            how many points the reference creates (at most n[b]: an accepted feature is occupied for the later neighbours)
+ *   new_neigh / new_idx1 / new_idx2 [b][j], new_x3d [b][j][3], j < n_new[b]: the neighbour slot k, the two feature indices and the
+ *       position handed to MapPoint's constructor, in the reference's creation order (k ascending, then idx1 ascending).  Entries at and
+ *       beyond n_new[b] are not written.  The capacity is cur->stride per key frame.
+ * Input the reference would fault on creates no point instead: a stereo feature (u_right >= 0) whose depth is not > 0 when UnprojectStereo is its
+ * source; an octave outside [0, PLANAR_MAX_LEVELS) is taken modulo PLANAR_MAX_LEVELS.  `cam` is a HOST pointer in both flavours.
+ * new MapPoint, AddObservation, AddMapPoint, ComputeDistinctiveDescriptors and UpdateNormalAndDepth stay with the caller
+ * (planar_distinctive_descriptors, planar_update_normal_and_depth). */
+int planar_create_new_map_points(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_keyframes* cur, const planar_tri_keyframes* neigh,
+                                 const int32_t* n_neigh, int max_neigh, int32_t* n_new, int32_t* new_neigh, int32_t* new_idx1, int32_t* new_idx2,
+                                 float* new_x3d);
+int planar_create_new_map_points_dev(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_keyframes* d_cur,
+                                     const planar_tri_keyframes* d_neigh, const int32_t* d_n_neigh, int max_neigh, int32_t* d_n_new,
+                                     int32_t* d_new_neigh, int32_t* d_new_idx1, int32_t* d_new_idx2, float* d_new_x3d);
+
 /* Frame::isInFrustum(MapPoint*, viewingCosLimit) (src/Frame.cc:312-367) for every local map point of B frames: fills the tracking
  * fields SearchByProjection(F, vpMapPoints, th) reads (the non-const twins of planar_map_probes' arrays).
  *   frame: Tcw, fx fy cx cy bf, min/max bounds are read (mRcw, mtcw, mOw are derived as Frame::UpdatePoseMatrices does, :301-306)

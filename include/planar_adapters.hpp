@@ -6,6 +6,7 @@
 //   PlaneDetection              <- include/PlaneExtractor.h:36-56, src/PlaneExtractor.cpp             (always)
 //   Planar_SLAM::LineSegment    <- include/LSDextractor.h:344-352, src/LSDextractor.cpp               (PLANAR_ADAPTERS_WITH_LINES)
 //   ORBmatcher::Fuse / LSDmatcher::Fuse (search on the device, map edits as in the reference)         (PLANAR_ADAPTERS_WITH_FUSE, needs one accessor, see there)
+//   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -22,6 +23,7 @@
 #include <opencv2/features2d/features2d.hpp>
 
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -797,6 +799,94 @@ inline int Optimizer::TranslationOptimization(Frame* pFrame) { return planar_det
 
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_TRACKING
+
+// ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:309-540), everything up to "Triangulation is succesfull".  Enabled with PLANAR_ADAPTERS_WITH_NEW_POINTS.
+//      Takes the current key frame and its neighbours (GetBestCovisibilityKeyFrames' order; pass fewer to mirror the CheckNewKeyFrames() return), packs them, calls
+//      planar_create_new_map_points and returns the candidates in the reference's creation order.  The caller keeps the reference's own statements for each of them:
+//          MapPoint* pMP = new MapPoint(x3D, mpCurrentKeyFrame, mpMap); pMP->AddObservation(mpCurrentKeyFrame, idx1); pMP->AddObservation(vpNeighKFs[neighbour], idx2);
+//          mpCurrentKeyFrame->AddMapPoint(pMP, idx1); vpNeighKFs[neighbour]->AddMapPoint(pMP, idx2); ComputeDistinctiveDescriptors(); UpdateNormalAndDepth(); ...
+//      A failing call degrades to "no new points".  KeyFrameT is Planar_SLAM::KeyFrame (a template only so that a test can pass a stand-in): N, mvKeysUn, mvKeys,
+//      mvuRight, mvDepth, mDescriptors, mFeatVec, GetMapPoint, GetPose, GetPoseInverse, mb, mbf, fx fy cx cy invfx invfy, mfScaleFactor, mvScaleFactors, mvLevelSigma2 are read.
+#ifdef PLANAR_ADAPTERS_WITH_NEW_POINTS
+namespace planar_adapter {
+
+struct NewPointCandidate {
+    int neighbour;        // index into vpNeighKFs
+    int idx1, idx2;       // feature of the current key frame, feature of the neighbour
+    float x3D[3];         // the position handed to MapPoint's constructor
+};
+
+namespace detail {
+// the arrays of `count` key frames behind one planar_tri_keyframes
+struct TriPack {
+    int32_t stride;
+    std::vector<int32_t> n, node;
+    std::vector<planar_keypoint> keys_un, keys;
+    std::vector<float> u_right, depth, cos_stereo, Tcw, Twc, mb, mbf;
+    std::vector<uint8_t> desc, occupied;
+    TriPack(size_t count, int32_t s) : stride(s), n(count, 0), node(count * s, -1), keys_un(count * s), keys(count * s), u_right(count * s, -1.f), depth(count * s, -1.f),
+                                       cos_stereo(count * s, 0.f), Tcw(count * 16, 0.f), Twc(count * 16, 0.f), mb(count, 0.f), mbf(count, 0.f), desc(count * s * 32, 0),
+                                       occupied(count * s, 0) {}
+    template <class KeyFrameT> void put(size_t e, KeyFrameT* kf) {
+        const size_t o = e * stride;
+        const int N = kf->N;
+        n[e] = N; mb[e] = kf->mb; mbf[e] = kf->mbf;
+        for (int i = 0; i < N; i++) {
+            std::memcpy(&keys_un[o + i], &kf->mvKeysUn[i], sizeof(planar_keypoint));
+            std::memcpy(&keys[o + i], &kf->mvKeys[i], sizeof(planar_keypoint));
+            u_right[o + i] = kf->mvuRight[i];
+            depth[o + i] = kf->mvDepth[i];
+            // src/LocalMapping.cc:411, :413 in the host's float libm: the value decides a branch, so it is not left to the device
+            cos_stereo[o + i] = std::cos(2 * std::atan2(kf->mb / 2, kf->mvDepth[i]));
+            std::memcpy(&desc[(o + i) * 32], kf->mDescriptors.ptr(i), 32);
+            occupied[o + i] = kf->GetMapPoint(i) != NULL;
+        }
+        for (const auto& kv : kf->mFeatVec) for (unsigned int i : kv.second) if ((int)i < N) node[o + i] = (int32_t)kv.first;
+        const cv::Mat T = kf->GetPose(), Ti = kf->GetPoseInverse();
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { Tcw[e * 16 + 4 * r + c] = T.template at<float>(r, c); Twc[e * 16 + 4 * r + c] = Ti.template at<float>(r, c); }
+    }
+    planar_tri_keyframes view() const {
+        planar_tri_keyframes v;
+        v.count = (int32_t)n.size(); v.stride = stride; v.n = n.data(); v.keys_un = keys_un.data(); v.u_right = u_right.data(); v.desc = desc.data(); v.node = node.data();
+        v.occupied = occupied.data(); v.Tcw = Tcw.data(); v.keys = keys.data(); v.depth = depth.data(); v.cos_stereo = cos_stereo.data(); v.Twc = Twc.data();
+        v.mb = mb.data(); v.mbf = mbf.data();
+        return v;
+    }
+};
+}  // namespace detail
+
+template <class KeyFrameT>
+inline std::vector<NewPointCandidate> CreateNewMapPoints(KeyFrameT* pKF, const std::vector<KeyFrameT*>& vpNeighKFs) {
+    std::vector<NewPointCandidate> out;
+    const int K = (int)vpNeighKFs.size();
+    if (!pKF || pKF->N <= 0 || K == 0) return out;
+    if (K > PLANAR_TRI_MAX_NEIGHBOURS) { std::fprintf(stderr, "planar (CreateNewMapPoints): more than %d neighbours - degraded to \"nothing found\"\n", PLANAR_TRI_MAX_NEIGHBOURS); return out; }
+    int32_t stride = pKF->N;
+    for (KeyFrameT* kf : vpNeighKFs) if (kf->N > stride) stride = kf->N;
+    planar_tri_camera cam;
+    std::memset(&cam, 0, sizeof(cam));
+    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.invfx = pKF->invfx; cam.invfy = pKF->invfy; cam.scale_factor = pKF->mfScaleFactor;
+    cam.n_levels = (int32_t)pKF->mvScaleFactors.size();
+    for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) { cam.scale_factors[l] = pKF->mvScaleFactors[l]; cam.level_sigma2[l] = pKF->mvLevelSigma2[l]; }
+    detail::TriPack cur(1, stride), nb((size_t)K, stride);
+    cur.put(0, pKF);
+    for (int k = 0; k < K; k++) nb.put((size_t)k, vpNeighKFs[k]);
+    const planar_tri_keyframes vc = cur.view(), vn = nb.view();
+    std::vector<int32_t> kk(stride, -1), i1(stride, -1), i2(stride, -1);
+    std::vector<float> x((size_t)stride * 3, 0.f);
+    int32_t n_neigh = K, n_new = 0;
+    {
+        Runtime::Lane& L = Runtime::get().lane(TRACKING);
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_create_new_map_points(L.ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data()), "planar_create_new_map_points")) return out;
+    }
+    out.resize(n_new);
+    for (int j = 0; j < n_new; j++) { out[j].neighbour = kk[j]; out[j].idx1 = i1[j]; out[j].idx2 = i2[j]; for (int c = 0; c < 3; c++) out[j].x3D[c] = x[3 * j + c]; }
+    return out;
+}
+
+}  // namespace planar_adapter
+#endif   // PLANAR_ADAPTERS_WITH_NEW_POINTS
 
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.

@@ -81,6 +81,16 @@ class KeyframeProbes(C.Structure):
     _fields_ = [("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "usable", "found", "xw", "min_dist", "max_dist", "angle", "desc")]
 
 
+class TriCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
+
+
+class TriKeyframes(C.Structure):
+    _fields_ = [("count", C.c_int32), ("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "keys_un", "u_right", "desc", "node", "occupied", "Tcw", "keys",
+                                                                                       "depth", "cos_stereo", "Twc", "mb", "mbf")]
+
+
 class TrackMatches(C.Structure):
     _fields_ = [("B", C.c_int32), ("stride", C.c_int32), ("mp_stride", C.c_int32), ("n_levels", C.c_int32), ("n", C.c_void_p), ("keys_un", C.c_void_p),
                 ("u_right", C.c_void_p), ("pt_match", C.c_void_p), ("mp_xw", C.c_void_p), ("mp_valid", C.c_void_p), ("inv_level_sigma2", C.c_float * MAX_LEVELS),
@@ -143,6 +153,10 @@ _SIGS = {
     "planar_is_in_frustum_points_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_float, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 6),
     "planar_is_in_frustum_lines": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 4),
     "planar_is_in_frustum_lines_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 4),
+    "planar_search_for_triangulation": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_search_for_triangulation_dev": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_create_new_map_points": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "planar_create_new_map_points_dev": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "planar_search_by_bow": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] +
                              [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_bow_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] +

@@ -117,6 +117,12 @@ class ORBmatcher:
         check(lib().planar_search_by_projection_map(self.ctx.h, C.byref(fv), C.byref(pv), th, self.mfNNratio, m.ctypes.data, nm.ctypes.data))
         return m, nm
 
+    def SearchForTriangulation(self, cam: dict, kf1: dict, kf2: dict, bOnlyStereo=False, match12=None):
+        """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:661-827) with F12 = LocalMapping::ComputeF12,
+        for B key-frame pairs (see planarslam_amd.newpoints for the dicts) -> (vMatches12 [B, S], nmatches [B]); vMatchedPairs is its ascending-idx1 read"""
+        from . import newpoints
+        return newpoints.search_for_triangulation(self.ctx, cam, kf1, kf2, bOnlyStereo, self.mbCheckOrientation, match12)
+
     def SearchByProjectionKeyFrame(self, cur: dict, kf: dict, th: float, ORBdist: int, log_scale_factor: float | None = None,
                                    n_levels: int | None = None, cur_match=None):
         """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), the relocalisation search.  cur: a frame dict with Tcw and
