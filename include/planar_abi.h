@@ -187,6 +187,7 @@ int planar_hamming_knn_dev(planar_ctx* ctx, const uint8_t* d_q, const int32_t* d
  * desc[off[p] .. off[p + 1]) (the rows pKF->mDescriptors.row(idx) of its non-bad key frames, in the order of the observation map); best[p] = index within that
  * list of the descriptor with the least median Hamming distance to all of them (first minimum; -1 without observations), median[p] (or NULL) that median.
  * _dev: max_obs = an upper bound of the observations per point (<= 2047; a point with more gets best = -2). */
+/* MapLine::ComputeDistinctiveDescriptors (src/MapLine.cpp:241) is the same computation on LBD rows (32 bytes, the median at (n - 1) / 2): pass mLineDescriptors rows. */
 int planar_distinctive_descriptors(planar_ctx* ctx, int n_points, const uint8_t* desc, const int32_t* off, int32_t* best, int32_t* median);
 int planar_distinctive_descriptors_dev(planar_ctx* ctx, int n_points, const uint8_t* d_desc, const int32_t* d_off, int max_obs, int32_t* d_best, int32_t* d_median);
 
@@ -386,6 +387,80 @@ int planar_create_new_map_points(planar_ctx* ctx, const planar_tri_camera* cam, 
 int planar_create_new_map_points_dev(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_keyframes* d_cur,
                                      const planar_tri_keyframes* d_neigh, const int32_t* d_n_neigh, int max_neigh, int32_t* d_n_new,
                                      int32_t* d_new_neigh, int32_t* d_new_idx1, int32_t* d_new_idx2, float* d_new_x3d);
+
+/* ---- LocalMapping::CreateNewMapLines2 (src/LocalMapping.cc:800-1037): key-frame / key-frame LBD search + depth lines + gates ---------- */
+#define PLANAR_MAX_KEYFRAME_LINES 256 /* limit on the line stride of a key-frame view (the extractor keeps the top 40 lines by default) */
+
+/* `count` key frames, [count][stride] arrays, as planar_lsd_extract and planar_is_line_good leave them.  The two searches read n, ldesc and
+ * occupied only (the rest may be NULL). */
+struct planar_keyline;
+typedef struct planar_tri_line_keyframes {
+    int32_t count, stride;           /* stride <= PLANAR_MAX_KEYFRAME_LINES                                                         */
+    const int32_t* n;                /* [count]             the number of key lines (mLineDescriptors.rows)                          */
+    const struct planar_keyline* keylines; /* [count][stride] mvKeyLines, the struct below (start_x/y, end_x/y and octave are read)        */
+    const uint8_t* ldesc;            /* [count][stride][32] mLineDescriptors; must start on a 16-byte boundary (else PLANAR_EINVAL) */
+    const uint8_t* occupied;         /* [count][stride]     GetMapLine(i) != NULL on entry                                           */
+    const float* depth_line;         /* [count][stride]     mvDepthLine, exactly as planar_is_line_good writes it (> 0: a 3-D line)  */
+    const double* lines3d;           /* [count][stride][6]  mvLines3D (camera frame), exactly as planar_is_line_good writes it      */
+    const float* Tcw;                /* [count][16]         Tcw; Ow is derived as KeyFrame::SetPose does                             */
+    const float* Twc;                /* [count][16]         Twc as the key frame holds it (KeyFrame::obtain3DLine)                   */
+    const float* mb;                 /* [count]             KeyFrame::mb                                                             */
+} planar_tri_line_keyframes;
+
+/* LSDmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs) (src/LSDmatcher.cpp:334-367) for kf1->count pairs; pair b is entry b of both
+ * views.  BFMatcher(NORM_HAMMING).knnMatch(k = 2) over ALL lines of both key frames (occupied ones included; the lowest train index wins a
+ * tie), KeyFrame::lineDescriptorMAD (src/KeyFrame.cc:858-883) over all those matches, nn12_dist_th = 0.1 * nn12_mad; query qdx is kept when
+ * neither it nor its best target is occupied and double(d1 - d0) > nn12_dist_th.
+ *   match12[b][qdx] (out, qdx < n1): the target index or -1; vMatchedPairs is its ascending-qdx read.   nmatches[b]: the return value.
+ *   nn_mad / nn12_mad [b] (may be NULL): what lineDescriptorMAD returned, before the factor; 0 where no match exists.
+ * Input the reference would fault on gives no matches: n1 == 0, and n2 < 2 (lmatches[i][1] does not exist). */
+int planar_lsd_search_for_triangulation(planar_ctx* ctx, const planar_tri_line_keyframes* kf1, const planar_tri_line_keyframes* kf2, int32_t* match12,
+                                        int32_t* nmatches, double* nn_mad, double* nn12_mad);
+int planar_lsd_search_for_triangulation_dev(planar_ctx* ctx, const planar_tri_line_keyframes* d_kf1, const planar_tri_line_keyframes* d_kf2,
+                                            int32_t* d_match12, int32_t* d_nmatches, double* d_nn_mad, double* d_nn12_mad);
+/* LSDmatcher::SearchByDescriptor(KeyFrame* pKF, KeyFrame* pKF2, vpMapLineMatches) (src/LSDmatcher.cpp:281-314): the same knn and the same
+ * function of the same matches (pKF2->lineDescriptorMAD), factor 0.5; query qdx is kept when double(d1 - d0) > nn12_dist_th and its best
+ * target has a map line (kf2->occupied).  match12[b][qdx]: the target whose map line vpMapLineMatches[qdx] becomes, or -1. */
+int planar_lsd_search_by_descriptor_kf(planar_ctx* ctx, const planar_tri_line_keyframes* kf1, const planar_tri_line_keyframes* kf2, int32_t* match12,
+                                       int32_t* nmatches);
+int planar_lsd_search_by_descriptor_kf_dev(planar_ctx* ctx, const planar_tri_line_keyframes* d_kf1, const planar_tri_line_keyframes* d_kf2,
+                                           int32_t* d_match12, int32_t* d_nmatches);
+
+/* LocalMapping::CreateNewMapLines2 for cur->count current key frames (mbMonocular == false); neighbours as planar_create_new_map_points takes
+ * them (entries b * max_neigh + k of `neigh`, GetBestCovisibilityKeyFrames' order).  Per neighbour: the baseline gate, SearchForTriangulation,
+ * then per kept pair the 3-D segment of KeyFrame::obtain3DLine (src/KeyFrame.cc:738-747), the four depth signs, the four reprojection gates at
+ * 5.991 * sigma2[octave], the zero distances and the two-sided scale test on both end points.  ComputeF12's result is unused by the reference's
+ * line path and is not computed.  Kept as the reference has them: bStereo2 reads the CURRENT key frame's depth_line at the NEIGHBOUR's index
+ * (:885); two lines of the current key frame may take the same idx2; an accepted idx1 is occupied for the later neighbours.
+ *   n_new[b]; new_neigh / new_idx1 / new_idx2 [b][j], new_line [b][j][6], j < n_new[b]: the neighbour slot, the two line indices and the six
+ *       floats handed to MapLine's constructor, widened to double as its Vector6d holds them, in creation order (k ascending, then idx1
+ *       ascending).  Nothing is written at or beyond n_new[b].  The capacity is cur->stride per key frame.
+ * Input the reference would fault on: n1 == 0 or a neighbour with fewer than 2 lines gives no pair; idx2 >= n1 in the bStereo2 read (past the end
+ * of mvDepthLine) counts as not stereo; an octave outside the levels is taken modulo PLANAR_MAX_LEVELS; n_neigh[b] == 0 gives n_new[b] == 0.
+ * `cam` is a HOST pointer in both flavours.  new MapLine, AddObservation, AddMapLine, ComputeDistinctiveDescriptors and UpdateAverageDir stay
+ * with the caller (planar_distinctive_descriptors, planar_update_average_dir). */
+int planar_create_new_map_lines(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_line_keyframes* cur, const planar_tri_line_keyframes* neigh,
+                                const int32_t* n_neigh, int max_neigh, int32_t* n_new, int32_t* new_neigh, int32_t* new_idx1, int32_t* new_idx2,
+                                double* new_line);
+int planar_create_new_map_lines_dev(planar_ctx* ctx, const planar_tri_camera* cam, const planar_tri_line_keyframes* d_cur,
+                                    const planar_tri_line_keyframes* d_neigh, const int32_t* d_n_neigh, int max_neigh, int32_t* d_n_new,
+                                    int32_t* d_new_neigh, int32_t* d_new_idx1, int32_t* d_new_idx2, double* d_new_line);
+
+/* MapLine::UpdateAverageDir (src/MapLine.cpp:320-367) for G groups of map lines; group g = the lines whose reference key frame has the pose
+ * ref_Tcw[g], shaped like planar_update_normal_and_depth.
+ *   n [G], xw6 [G][stride][6] (mWorldPos: start xyz, end xyz), valid [G][stride] or NULL (0 = no line: its outputs are left alone)
+ *   ref_octave [G][stride]: the octave of the line's key line in the reference key frame (modulo PLANAR_MAX_LEVELS)
+ *   obs_off [G * stride + 1], obs_ow [.][3]: camera centres (float, as GetCameraCenter gives them) of the observing key frames in observation-map
+ *            order; both NULL: every line is observed by its reference key frame only
+ *   scale_factors [n_levels] (mvScaleFactors) is a HOST pointer in both flavours
+ *   normal [G][stride][3] (mNormalVector: the mean of the unit vectors from the camera centres to the mid point, in double),
+ *   min_dist / max_dist [G][stride] (mfMinDistance / mfMaxDistance); a line without observations keeps its values */
+int planar_update_average_dir(planar_ctx* ctx, int G, const int32_t* n, int stride, const double* xw6, const uint8_t* valid, const float* ref_Tcw,
+                              const int32_t* ref_octave, const int32_t* obs_off, const float* obs_ow, const float* scale_factors, int n_levels,
+                              double* normal, float* min_dist, float* max_dist);
+int planar_update_average_dir_dev(planar_ctx* ctx, int G, const int32_t* d_n, int stride, const double* d_xw6, const uint8_t* d_valid,
+                                  const float* d_ref_Tcw, const int32_t* d_ref_octave, const int32_t* d_obs_off, const float* d_obs_ow,
+                                  const float* scale_factors, int n_levels, double* d_normal, float* d_min_dist, float* d_max_dist);
 
 /* Frame::isInFrustum(MapPoint*, viewingCosLimit) (src/Frame.cc:312-367) for every local map point of B frames: fills the tracking
  * fields SearchByProjection(F, vpMapPoints, th) reads (the non-const twins of planar_map_probes' arrays).

@@ -888,6 +888,144 @@ inline std::vector<NewPointCandidate> CreateNewMapPoints(KeyFrameT* pKF, const s
 }  // namespace planar_adapter
 #endif   // PLANAR_ADAPTERS_WITH_NEW_POINTS
 
+// ---- LocalMapping::CreateNewMapLines2 (src/LocalMapping.cc:800-1037), everything up to "new MapLine", and LSDmatcher::SearchForTriangulation
+//      (src/LSDmatcher.cpp:334-367).  Enabled with PLANAR_ADAPTERS_WITH_NEW_LINES.  CreateNewMapLines takes the current key frame and its neighbours
+//      (GetBestCovisibilityKeyFrames' order; pass fewer to mirror the CheckNewKeyFrames() return), packs them, calls planar_create_new_map_lines and returns the
+//      candidates in the reference's creation order.  The caller keeps the reference's own statements for each of them:
+//          MapLine* pML = new MapLine(line3D, mpCurrentKeyFrame, mpMap); pML->AddObservation(mpCurrentKeyFrame, idx1); pML->AddObservation(vpNeighKFs[neighbour], idx2);
+//          mpCurrentKeyFrame->AddMapLine(pML, idx1); vpNeighKFs[neighbour]->AddMapLine(pML, idx2); ComputeDistinctiveDescriptors(); UpdateAverageDir(); ...
+//      A failing call, more than PLANAR_TRI_MAX_NEIGHBOURS neighbours or a key frame with more than PLANAR_MAX_KEYFRAME_LINES lines degrades to "no new lines".
+//      KeyFrameT is Planar_SLAM::KeyFrame (a template only so that a test can pass a stand-in): mvKeyLines, mLineDescriptors, mvDepthLine, mvLines3D, GetMapLine,
+//      GetPose, GetPoseInverse, mb, fx fy cx cy invfx invfy, mfScaleFactor, mvScaleFactors, mvLevelSigma2 are read.  Kept as the reference has them: bStereo2 reads the
+//      current key frame's mvDepthLine at the neighbour's index, two lines may take one idx2, F12 is not computed (its result is unused by the line path).
+//      With PLANAR_ADAPTERS_LSDMATCHER_TRIANGULATION as well (after the reference's LSDmatcher.h) LSDmatcher::SearchForTriangulation itself is defined here.
+#ifdef PLANAR_ADAPTERS_WITH_NEW_LINES
+#include <opencv2/line_descriptor/descriptor.hpp>
+namespace planar_adapter {
+
+struct NewLineCandidate {
+    int neighbour;        // index into vpNeighKFs
+    int idx1, idx2;       // line of the current key frame, line of the neighbour
+    double line3D[6];     // the Vector6d handed to MapLine's constructor: floats widened to double
+};
+
+namespace detail {
+// the arrays of `count` key frames behind one planar_tri_line_keyframes
+struct TriLinePack {
+    int32_t stride;
+    std::vector<int32_t> n;
+    std::vector<planar_keyline> keylines;
+    std::vector<uint8_t> ldesc_store, occupied;
+    std::vector<float> depth_line, Tcw, Twc, mb;
+    std::vector<double> lines3d;
+    uint8_t* ldesc;       // 16-byte aligned inside ldesc_store
+    TriLinePack(size_t count, int32_t s) : stride(s), n(count, 0), keylines(count * s), ldesc_store(count * s * 32 + 16, 0), occupied(count * s, 0), depth_line(count * s, -1.f),
+                                           Tcw(count * 16, 0.f), Twc(count * 16, 0.f), mb(count, 0.f), lines3d(count * s * 6, 0.0) {
+        std::memset(keylines.data(), 0, keylines.size() * sizeof(planar_keyline));
+        ldesc = ldesc_store.data() + ((16 - ((uintptr_t)ldesc_store.data() & 15)) & 15);
+    }
+    // what the two searches read (n, ldesc, occupied)
+    template <class KeyFrameT> void put_search(size_t e, KeyFrameT* kf) {
+        static_assert(sizeof(cv::line_descriptor::KeyLine) == sizeof(planar_keyline), "KeyLine layout");
+        const size_t o = e * stride;
+        const int N = kf->mLineDescriptors.rows;
+        n[e] = N;
+        for (int i = 0; i < N; i++) {
+            std::memcpy(ldesc + (o + i) * 32, kf->mLineDescriptors.ptr(i), 32);
+            occupied[o + i] = kf->GetMapLine(i) != NULL;
+        }
+    }
+    template <class KeyFrameT> void put(size_t e, KeyFrameT* kf) {
+        put_search(e, kf);
+        const size_t o = e * stride;
+        int N = n[e];
+        // the reference keeps mvKeyLines, mvDepthLine and mvLines3D as long as mLineDescriptors has rows; a shorter one leaves its lines without depth (-1, zeros)
+        if ((size_t)N > kf->mvKeyLines.size()) N = (int)kf->mvKeyLines.size();
+        if ((size_t)N > kf->mvDepthLine.size()) N = (int)kf->mvDepthLine.size();
+        if ((size_t)N > kf->mvLines3D.size()) N = (int)kf->mvLines3D.size();
+        mb[e] = kf->mb;
+        for (int i = 0; i < N; i++) {
+            std::memcpy(&keylines[o + i], &kf->mvKeyLines[i], sizeof(planar_keyline));
+            depth_line[o + i] = kf->mvDepthLine[i];
+            for (int c = 0; c < 6; c++) lines3d[(o + i) * 6 + c] = kf->mvLines3D[i](c);
+        }
+        const cv::Mat T = kf->GetPose(), Ti = kf->GetPoseInverse();
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { Tcw[e * 16 + 4 * r + c] = T.template at<float>(r, c); Twc[e * 16 + 4 * r + c] = Ti.template at<float>(r, c); }
+    }
+    planar_tri_line_keyframes view(bool search) const {
+        planar_tri_line_keyframes v;
+        std::memset(&v, 0, sizeof(v));
+        v.count = (int32_t)n.size(); v.stride = stride; v.n = n.data(); v.ldesc = ldesc; v.occupied = occupied.data();
+        if (!search) { v.keylines = keylines.data(); v.depth_line = depth_line.data(); v.lines3d = lines3d.data(); v.Tcw = Tcw.data(); v.Twc = Twc.data(); v.mb = mb.data(); }
+        return v;
+    }
+};
+}  // namespace detail
+
+template <class KeyFrameT>
+inline std::vector<NewLineCandidate> CreateNewMapLines(KeyFrameT* pKF, const std::vector<KeyFrameT*>& vpNeighKFs) {
+    std::vector<NewLineCandidate> out;
+    const int K = (int)vpNeighKFs.size();
+    if (!pKF || pKF->mLineDescriptors.rows <= 0 || K == 0) return out;
+    if (K > PLANAR_TRI_MAX_NEIGHBOURS) { std::fprintf(stderr, "planar (CreateNewMapLines): more than %d neighbours - degraded to \"nothing found\"\n", PLANAR_TRI_MAX_NEIGHBOURS); return out; }
+    int32_t stride = pKF->mLineDescriptors.rows;
+    for (KeyFrameT* kf : vpNeighKFs) if (kf->mLineDescriptors.rows > stride) stride = kf->mLineDescriptors.rows;
+    if (stride > PLANAR_MAX_KEYFRAME_LINES) { std::fprintf(stderr, "planar (CreateNewMapLines): more than %d lines in a key frame - degraded to \"nothing found\"\n", PLANAR_MAX_KEYFRAME_LINES); return out; }
+    planar_tri_camera cam;
+    std::memset(&cam, 0, sizeof(cam));
+    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.invfx = pKF->invfx; cam.invfy = pKF->invfy; cam.scale_factor = pKF->mfScaleFactor;
+    cam.n_levels = (int32_t)pKF->mvScaleFactors.size();
+    for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) { cam.scale_factors[l] = pKF->mvScaleFactors[l]; cam.level_sigma2[l] = pKF->mvLevelSigma2[l]; }
+    detail::TriLinePack cur(1, stride), nb((size_t)K, stride);
+    cur.put(0, pKF);
+    for (int k = 0; k < K; k++) nb.put((size_t)k, vpNeighKFs[k]);
+    const planar_tri_line_keyframes vc = cur.view(false), vn = nb.view(false);
+    std::vector<int32_t> kk(stride, -1), i1(stride, -1), i2(stride, -1);
+    std::vector<double> x((size_t)stride * 6, 0.0);
+    int32_t n_neigh = K, n_new = 0;
+    {
+        Runtime::Lane& L = Runtime::get().lane(TRACKING);
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_create_new_map_lines(L.ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data()), "planar_create_new_map_lines")) return out;
+    }
+    out.resize(n_new);
+    for (int j = 0; j < n_new; j++) { out[j].neighbour = kk[j]; out[j].idx1 = i1[j]; out[j].idx2 = i2[j]; for (int c = 0; c < 6; c++) out[j].line3D[c] = x[6 * j + c]; }
+    return out;
+}
+
+// LSDmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs): the pairs in ascending qdx, the count returned.  A failing call gives no pairs.
+template <class KeyFrameT>
+inline int SearchLinesForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<std::pair<size_t, size_t>>& vMatchedPairs) {
+    vMatchedPairs.clear();
+    const int32_t n1 = pKF1->mLineDescriptors.rows, n2 = pKF2->mLineDescriptors.rows;
+    const int32_t stride = n1 > n2 ? n1 : n2;
+    if (n1 <= 0 || n2 < 2) return 0;   // the reference would index lmatches[i][1]
+    if (stride > PLANAR_MAX_KEYFRAME_LINES) { std::fprintf(stderr, "planar (SearchForTriangulation): more than %d lines in a key frame - degraded to \"nothing found\"\n", PLANAR_MAX_KEYFRAME_LINES); return 0; }
+    detail::TriLinePack a(1, stride), b(1, stride);
+    a.put_search(0, pKF1);
+    b.put_search(0, pKF2);
+    const planar_tri_line_keyframes va = a.view(true), vb = b.view(true);
+    std::vector<int32_t> match(stride, -1);
+    int32_t nmatches = 0;
+    {
+        Runtime::Lane& L = Runtime::get().lane(TRACKING);
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_lsd_search_for_triangulation(L.ctx, &va, &vb, match.data(), &nmatches, NULL, NULL), "planar_lsd_search_for_triangulation")) return 0;
+    }
+    for (int q = 0; q < n1; q++) if (match[q] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)q, (size_t)match[q]));
+    return nmatches;
+}
+
+}  // namespace planar_adapter
+#ifdef PLANAR_ADAPTERS_LSDMATCHER_TRIANGULATION
+namespace Planar_SLAM {
+inline int LSDmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<std::pair<size_t, size_t>>& vMatchedPairs) {
+    return planar_adapter::SearchLinesForTriangulation(pKF1, pKF2, vMatchedPairs);
+}
+}  // namespace Planar_SLAM
+#endif
+#endif   // PLANAR_ADAPTERS_WITH_NEW_LINES
+
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.
 //      Define PLANAR_ADAPTERS_WITH_LOCAL_BA after including KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, Map.h, Optimizer.h, Config.h. --------------

@@ -86,6 +86,10 @@ class TriCamera(C.Structure):
                 ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
 
 
+class TriLineKeyframes(C.Structure):
+    _fields_ = [("count", C.c_int32), ("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "keylines", "ldesc", "occupied", "depth_line", "lines3d", "Tcw", "Twc", "mb")]
+
+
 class TriKeyframes(C.Structure):
     _fields_ = [("count", C.c_int32), ("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "keys_un", "u_right", "desc", "node", "occupied", "Tcw", "keys",
                                                                                        "depth", "cos_stereo", "Twc", "mb", "mbf")]
@@ -157,6 +161,14 @@ _SIGS = {
     "planar_search_for_triangulation_dev": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_create_new_map_points": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "planar_create_new_map_points_dev": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriKeyframes), C.POINTER(TriKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "planar_lsd_search_for_triangulation": (C.c_int, [C.c_void_p, C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes)] + [C.c_void_p] * 4),
+    "planar_lsd_search_for_triangulation_dev": (C.c_int, [C.c_void_p, C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes)] + [C.c_void_p] * 4),
+    "planar_lsd_search_by_descriptor_kf": (C.c_int, [C.c_void_p, C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes)] + [C.c_void_p] * 2),
+    "planar_lsd_search_by_descriptor_kf_dev": (C.c_int, [C.c_void_p, C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes)] + [C.c_void_p] * 2),
+    "planar_create_new_map_lines": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "planar_create_new_map_lines_dev": (C.c_int, [C.c_void_p, C.POINTER(TriCamera), C.POINTER(TriLineKeyframes), C.POINTER(TriLineKeyframes), C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "planar_update_average_dir": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3),
+    "planar_update_average_dir_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3),
     "planar_search_by_bow": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] +
                              [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_bow_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] +

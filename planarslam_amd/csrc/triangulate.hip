@@ -16,11 +16,11 @@
 //   * tri_orient_kernel (the plain search with check_orientation): the 30-bin histogram, ComputeThreeMaxima and nmatches.
 // Float / double mix as the reference has it, -ffp-contract=off; bit-exact with tests/golden/new_points_ref.npz (tools/gen_golden_new_points.py: the real reference) and tests/host_shim/new_points_host.cpp.
 #include "common.h"
+#include "tri_shared.h"
 
 namespace planar {
 namespace tri {
 
-constexpr int NT = 256;
 constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
 constexpr int TH_LOW = 50, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:39-40
 constexpr int NODE_NEVER = -2;                   // LDS node value of a feature of key frame 2 that no idx1 may take
@@ -40,7 +40,6 @@ struct Args {
     float* new_x3d;
 };
 
-struct Pose { float Rcw[9], tcw[3], Ow[3]; };
 struct PairLds {
     Pose p1, p2;
     float F12[9], ex, ey;
@@ -50,8 +49,6 @@ struct Lds {
     int node2[MAXN];
     PairLds pr;
 };
-
-__device__ inline int clamp_n(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
 
 // cv::gemm, CV_32F small-matrix path: float products summed left to right
 __device__ inline void mul33(const float* A, const float* B, float* D) {
@@ -63,23 +60,6 @@ __device__ inline void mul33(const float* A, const float* B, float* D) {
             D[3 * i + j] = t;
         }
 }
-__device__ inline float row3(const float* r, float x0, float x1, float x2) {
-    float t = r[0] * x0;
-    t = t + r[1] * x1;
-    t = t + r[2] * x2;
-    return t;
-}
-__device__ inline double dot3(const float* a, float b0, float b1, float b2) {
-    double s = 0;
-    s += (double)a[0] * (double)b0; s += (double)a[1] * (double)b1; s += (double)a[2] * (double)b2;
-    return s;
-}
-__device__ inline double norm3(float a0, float a1, float a2) {
-    double s = 0;
-    s += (double)a0 * (double)a0; s += (double)a1 * (double)a1; s += (double)a2 * (double)a2;
-    return sqrt(s);
-}
-
 // Mat::inv() (DECOMP_LU) of a 3x3 CV_32F matrix: det3 and the cofactors in double, times 1 / det
 __device__ inline void inv33(const float* S, float* D) {
     double d = S[0] * ((double)S[4] * S[8] - (double)S[5] * S[7]) - S[1] * ((double)S[3] * S[8] - (double)S[5] * S[6]) +
@@ -95,17 +75,6 @@ __device__ inline void inv33(const float* S, float* D) {
     D[6] = (float)(((double)S[3] * S[7] - (double)S[4] * S[6]) * d);
     D[7] = (float)(((double)S[1] * S[6] - (double)S[0] * S[7]) * d);
     D[8] = (float)(((double)S[0] * S[4] - (double)S[1] * S[3]) * d);
-}
-
-// Rcw, tcw, and Ow = -Rwc * tcw as KeyFrame::SetPose forms it (Rwc a matrix: the small-matrix path, (float)((double)t * -1.0))
-__device__ inline void load_pose(const float* T, Pose& p) {
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.Rcw[3 * r + c] = T[4 * r + c]; p.tcw[r] = T[4 * r + 3]; }
-    for (int i = 0; i < 3; i++) {
-        float t = p.Rcw[i] * p.tcw[0];
-        t = t + p.Rcw[3 + i] * p.tcw[1];
-        t = t + p.Rcw[6 + i] * p.tcw[2];
-        p.Ow[i] = (float)((double)t * -1.0);
-    }
 }
 
 // ComputeF12 and the epipole of key frame 1 in key frame 2 (src/ORBmatcher.cc:668-674); one lane
@@ -409,20 +378,6 @@ __global__ __launch_bounds__(NT) void tri_kernel(const Args a) {
     a.acc_k[o1 + idx1] = acc_k;
     a.acc_idx2[o1 + idx1] = acc_idx2;
     a.acc_x3d[(o1 + idx1) * 3] = acc_x[0]; a.acc_x3d[(o1 + idx1) * 3 + 1] = acc_x[1]; a.acc_x3d[(o1 + idx1) * 3 + 2] = acc_x[2];
-}
-
-// exclusive scan of one flag per thread over the workgroup: the rank of this thread's flag, the total in *total
-__device__ inline int block_rank(bool flag, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wsum[w] = __popcll(m);
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < NT / 64; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
-    *total = tot;
-    return base + before;
 }
 
 // one workgroup per current key frame: the accepted features in the reference's creation order, neighbour ascending, then idx1 ascending

@@ -179,6 +179,18 @@ class LSDmatcher:
         self.mfNNratio = nnratio
         self.ctx = ctx or Context(0)
 
+    def SearchForTriangulation(self, kf1: dict, kf2: dict, match12=None):
+        """LSDmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs) (src/LSDmatcher.cpp:334-367) for B key-frame pairs (see planarslam_amd.newlines for
+        the dicts) -> (match12 [B, S], nmatches [B]); vMatchedPairs is the ascending-qdx read of match12"""
+        from . import newlines
+        return newlines.search_for_triangulation(self.ctx, kf1, kf2, match12)[:2]
+
+    def SearchByDescriptorKF(self, kf1: dict, kf2: dict, match12=None):
+        """LSDmatcher::SearchByDescriptor(KeyFrame* pKF, KeyFrame* pKF2, vpMapLineMatches) (src/LSDmatcher.cpp:281-314) -> (the line of pKF2 per line of pKF or
+        -1 [B, S], nmatches [B])"""
+        from . import newlines
+        return newlines.search_by_descriptor_kf(self.ctx, kf1, kf2, match12)
+
     def SearchByProjection(self, lines: dict, maplines: dict, scale_factors, th: float = 1.0, match=None):
         """lines: n, keylines (KEYLINE_DTYPE [B,S]), ldesc, optional blocked ; maplines: n, in_view, proj [B,M,4], level,
         view_cos, desc, observed.  Returns (match [B,S] = map-line index / -1, nmatches)."""
