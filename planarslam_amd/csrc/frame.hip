@@ -9,6 +9,7 @@
 //   planar_discard_outliers    the loop after the optimiser (src/Tracking.cc:1784-1812): matches flagged as outliers are dropped
 // All three are gathers over small records: HBM-bound (a few hundred bytes per keypoint), one thread per element, no LDS.
 #include "common.h"
+#include "ref_arith.h"
 
 namespace planar {
 namespace frame {
@@ -35,15 +36,11 @@ __global__ __launch_bounds__(256) void stereo_kernel(const planar_keypoint* __re
             zz = d;
             ur = ku.x - K.bf / d;
             const float x = (ku.x - K.cx) * d * invfx, y = (ku.y - K.cy) * d * invfy;
-            // mOw = -mRcw.t() * mtcw: transposed operand -> general gemm, double accumulation; mRwc * x3Dc + mOw: small-matrix gemm, float sums
+            // mOw = -mRcw.t() * mtcw (a Frame's centre, one component at a time), then mRwc * x3Dc + mOw
 #pragma unroll
             for (int r = 0; r < 3; r++) {
-                const double s = (double)T[r] * (double)T[3] + (double)T[4 + r] * (double)T[7] + (double)T[8 + r] * (double)T[11];
-                const float Ow = (float)(s * -1.0);
-                float t = T[r] * x;
-                t = t + T[4 + r] * y;
-                t = t + T[8 + r] * d;
-                X[r] = (float)((double)t * 1.0 + (double)Ow * 1.0);
+                const float Ow = ref::gemm_general_neg(ref::dot3_flat(T[r], T[4 + r], T[8 + r], T[3], T[7], T[11]));
+                X[r] = ref::gemm_small_row_add(T[r], T[4 + r], T[8 + r], x, y, d, Ow);
             }
             ok = 1;
         }
@@ -155,7 +152,7 @@ __global__ __launch_bounds__(256) void discard_kernel(const int32_t* __restrict_
 }
 
 // MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:347-388): thread = map point.  Group g = the points whose reference key frame has pose ref_Tcw[g];
-// its camera centre is KeyFrame::SetPose's Ow = -Rwc * tcw (src/KeyFrame.cc:85-86: Rwc materialised -> cv::gemm's float small-matrix path, negated).
+// its camera centre is a KeyFrame's (ref::load_pose_keyframe).
 struct Scales { float sf[PLANAR_MAX_LEVELS]; int n_levels; };
 __global__ __launch_bounds__(256) void normal_depth_kernel(const int32_t* __restrict__ n, int stride, const float* __restrict__ xw, const uint8_t* __restrict__ valid,
                                                            const float* __restrict__ ref_Tcw, const planar_keypoint* __restrict__ keys_un,
@@ -165,32 +162,24 @@ __global__ __launch_bounds__(256) void normal_depth_kernel(const int32_t* __rest
     if (i >= stride || i >= n[g]) return;
     const size_t o = (size_t)g * stride + i;
     if (valid && !valid[o]) return;
-    const float* T = ref_Tcw + (size_t)g * 16;
-    float Ow[3], pos[3];
+    ref::Pose P;
+    ref::load_pose_keyframe(ref_Tcw + (size_t)g * 16, P);
+    const float* Ow = P.Ow;
+    float pos[3];
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-        float t = T[r] * T[3];
-        t = t + T[4 + r] * T[7];
-        t = t + T[8 + r] * T[11];
-        Ow[r] = (float)((double)t * -1.0);
-        pos[r] = xw[o * 3 + r];
-    }
+    for (int r = 0; r < 3; r++) pos[r] = xw[o * 3 + r];
     float nrm[3] = {0.f, 0.f, 0.f};
     const int o0 = obs_off ? obs_off[o] : 0, nobs = obs_off ? obs_off[o + 1] - o0 : 1;
     if (nobs <= 0) return;                                             // observations.empty(): the point keeps what it had
     for (int q = 0; q < nobs; q++) {
         float d[3];
-        double s = 0;
 #pragma unroll
-        for (int k = 0; k < 3; k++) { d[k] = pos[k] - (obs_off ? obs_ow[(size_t)(o0 + q) * 3 + k] : Ow[k]); s += (double)d[k] * (double)d[k]; }
-        const float fa = (float)(1.0 / sqrt(s));                       // normali / cv::norm(normali): the scale cast to float, float multiply
+        for (int k = 0; k < 3; k++) d[k] = pos[k] - (obs_off ? obs_ow[(size_t)(o0 + q) * 3 + k] : Ow[k]);
+        const float fa = (float)(1.0 / ref::norm3(d));                 // normali / cv::norm(normali): the scale cast to float, float multiply
 #pragma unroll
         for (int k = 0; k < 3; k++) nrm[k] = d[k] * fa + nrm[k] * 1.0f;
     }
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { const float pc = pos[k] - Ow[k]; s += (double)pc * (double)pc; }
-    const float dist = (float)sqrt(s);
+    const float dist = (float)ref::norm3(pos[0] - Ow[0], pos[1] - Ow[1], pos[2] - Ow[2]);
     const int level = min(max(keys_un[o].octave, 0), S.n_levels - 1);   // as assemble_kernel: an octave outside the pyramid must not index past the table
     const float mx = dist * S.sf[level];
     max_dist[o] = mx;

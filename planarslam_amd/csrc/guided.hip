@@ -22,15 +22,19 @@
 // The chunk size adapts to the LDS list capacity, so there is no overflow path.  One workgroup per frame
 // (pair); the batch dimension fills the GPU.  Integer / float32 work, bit-exact with the oracle.
 #include "common.h"
+#include "ref_arith.h"
 
 namespace planar {
 namespace guided {
+
+using ref::HISTO_LENGTH;
+using ref::Pose;
 
 constexpr int NT = 256;
 constexpr int NCELL = PLANAR_GRID_COLS * PLANAR_GRID_ROWS;
 constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
 constexpr int CAND_CAP = 8192;       // candidates of one chunk of probes; with it the workgroup needs 61 KB of LDS (two per CU)
-constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:38-40
+constexpr int TH_HIGH = 100, TH_LOW = 50;   // src/ORBmatcher.cc:38-39
 
 enum { MODE_FRAME = 0, MODE_MAP = 1, MODE_BOW = 2, MODE_KF = 3 };
 
@@ -48,39 +52,10 @@ struct Lds {
     int n_ev, nmatches, m_fit, wsum[NT / 64];
 };
 
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
+// a shuffle butterfly; planar::wave_min_u32 (wave_ops.h) is a DPP ladder.  Swapping one for the other changes the benchmarked path: a change of its own.
+__device__ inline uint32_t wave_min_u32_shfl(uint32_t v) {
     for (int o = 32; o >= 1; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
     return v;
-}
-
-// exclusive scan of one int per thread over the workgroup; returns the exclusive prefix, total in *total
-__device__ inline int block_exscan(int v, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < NT / 64; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
-    *total = tot;
-    return base + inc - v;
-}
-
-__device__ inline int hamming256(const uint32_t* a, const uint8_t* b) {
-    const uint4* p = (const uint4*)b;
-    const uint4 x = p[0], y = p[1];
-    return __popc(a[0] ^ x.x) + __popc(a[1] ^ x.y) + __popc(a[2] ^ x.z) + __popc(a[3] ^ x.w) + __popc(a[4] ^ y.x) + __popc(a[5] ^ y.y) +
-           __popc(a[6] ^ y.z) + __popc(a[7] ^ y.w);
-}
-
-__device__ inline void load_desc(uint32_t* a, const uint8_t* p) {
-    const uint4* q = (const uint4*)p;
-    const uint4 x = q[0], y = q[1];
-    a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w; a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
 }
 
 // Frame::AssignFeaturesToGrid (src/Frame.cc:155-166, PosInGrid :526-535) into cell_start / items.
@@ -101,7 +76,7 @@ __device__ void build_grid(L& s, const planar_frame_view& f, const planar_keypoi
     int local = 0;
     for (int k = 0; k < PER; k++) local += (int)cnt[tid * PER + k];
     int total;
-    int run = block_exscan(local, s.wsum, &total);
+    int run = ref::block_exscan<NT / 64>(local, s.wsum, &total);
     for (int k = 0; k < PER; k++) {
         const int c = tid * PER + k, n = (int)cnt[c];
         s.cell_start[c] = (uint16_t)run;
@@ -172,12 +147,6 @@ __device__ inline void walk_window(const L& s, const planar_frame_view& f, const
     }
 }
 
-// cv::gemm float32 small-matrix path (see oracle/guided_oracle.cpp header)
-__device__ inline float gemm3_row(float a0, float a1, float a2, const float* x, float c) {
-    const float t = a0 * x[0] + a1 * x[1] + a2 * x[2];
-    return (float)((double)t * 1.0 + (double)c * 1.0);
-}
-
 struct Args {
     planar_frame_view f;
     planar_last_frame_view last;
@@ -190,29 +159,6 @@ struct Args {
     float lsf;
     int n_levels, orb_dist;
 };
-
-// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1666-1708) on bin counts
-__device__ inline void three_maxima(const int* h, int& ind1, int& ind2, int& ind3) {
-    int max1 = 0, max2 = 0, max3 = 0;
-    ind1 = ind2 = ind3 = -1;
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-        const int sz = h[i];
-        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-        else if (sz > max3) { max3 = sz; ind3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-}
-
-__device__ inline int rot_bin(float a_from, float a_to) {
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = a_from - a_to;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
-}
 
 // Order-bound part: wavefront 0 resolves probes [0, m) of the current chunk in order.
 //   MODE_FRAME: best only, TH_HIGH;  MODE_MAP: best + second with the same-level ratio test;  MODE_BOW: TH_LOW + ratio;
@@ -237,7 +183,7 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
             }
             k1 = min(k1, key);
         }
-        k1 = wave_min_u32(k1);
+        k1 = wave_min_u32_shfl(k1);
         if (k1 == 0xffffffffu) continue;
         const int bestDist = (int)(k1 >> 16), bestK = (int)(k1 & 0xffff);
         const uint32_t e1 = s.cand[off + bestK];
@@ -255,7 +201,7 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
                 }
                 k2 = min(k2, key);
             }
-            k2 = wave_min_u32(k2);
+            k2 = wave_min_u32_shfl(k2);
             if (k2 != 0xffffffffu) {
                 bestDist2 = (int)(k2 >> 16);
                 bestLevel2 = (s.cand[off + (k2 & 0xffff)] >> 12) & 0xf;
@@ -277,14 +223,15 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
                 const float to = MODE == MODE_BOW ? to_angle_f[bestIdx] : keys[bestIdx].angle;
                 const int n = s.n_ev++;
                 s.ev_idx[n] = (uint16_t)bestIdx;
-                s.ev_bin[n] = (uint8_t)rot_bin(from_angle[id], to);
+                s.ev_bin[n] = (uint8_t)ref::rot_bin(from_angle[id], to);
             }
         }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// rotation-consistency post-step shared by MODE_FRAME and MODE_BOW
+// rotation-consistency post-step shared by MODE_FRAME and MODE_BOW.  rotation_filter_ranked computes the same another way; merging them changes the
+// benchmarked MODE_FRAME instruction stream, so that is a measured change of its own.
 __device__ void rotation_filter(Lds& s, int32_t* match) {
     const int tid = threadIdx.x;
     if (tid < HISTO_LENGTH) s.hist[tid] = 0;
@@ -294,7 +241,7 @@ __device__ void rotation_filter(Lds& s, int32_t* match) {
     __syncthreads();
     if (tid == 0) {
         int i1, i2, i3;
-        three_maxima(s.hist, i1, i2, i3);
+        ref::three_maxima(s.hist, i1, i2, i3);
         s.keep[0] = i1; s.keep[1] = i2; s.keep[2] = i3;
         int removed = 0;
         for (int i = 0; i < HISTO_LENGTH; i++)
@@ -364,22 +311,15 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     }
 
     // per-frame constants of the frame-to-frame variant (src/ORBmatcher.cc:1408-1420)
-    float Rcw[9], tcw[3], Ow[3];
+    Pose P;
     bool bForward = false, bBackward = false;
     size_t po;
     int NP;
     const uint8_t *probe_desc, *observed;
     if (MODE == MODE_FRAME) {
-        const float* Tc = f.Tcw + (size_t)b * 16;
         const float* Tl = a.last.Tcw + (size_t)b * 16;
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcw[3 * r + c] = Tc[4 * r + c]; tcw[r] = Tc[4 * r + 3]; }
-        float twc[3];
-        for (int i = 0; i < 3; i++) {
-            double sum = 0;
-            for (int k = 0; k < 3; k++) sum += (double)Rcw[3 * k + i] * (double)tcw[k];
-            twc[i] = (float)(sum * -1.0);
-        }
-        const float tlc2 = gemm3_row(Tl[8], Tl[9], Tl[10], twc, Tl[11]);
+        ref::load_pose_frame(f.Tcw + (size_t)b * 16, P);                               // twc = -Rcw.t()*tcw (:1408) is the frame's own centre
+        const float tlc2 = ref::gemm_small_row_add(Tl + 8, P.Ow, Tl[11]);
         bForward = tlc2 > f.b && !a.mono;
         bBackward = -tlc2 > f.b && !a.mono;
         po = (size_t)b * a.last.stride;
@@ -387,14 +327,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
         probe_desc = a.last.mp_desc + po * 32;
         observed = a.last.mp_observed + po;
     } else if (MODE == MODE_KF) {
-        // Ow = -Rcw.t()*tcw (src/ORBmatcher.cc:1541-1543), the same product as the frame variant's twc
-        const float* Tc = f.Tcw + (size_t)b * 16;
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcw[3 * r + c] = Tc[4 * r + c]; tcw[r] = Tc[4 * r + 3]; }
-        for (int i = 0; i < 3; i++) {
-            double sum = 0;
-            for (int k = 0; k < 3; k++) sum += (double)Rcw[3 * k + i] * (double)tcw[k];
-            Ow[i] = (float)(sum * -1.0);
-        }
+        ref::load_pose_frame(f.Tcw + (size_t)b * 16, P);                               // Ow = -Rcw.t()*tcw (src/ORBmatcher.cc:1541-1543)
         po = (size_t)b * a.kf.stride;
         NP = a.kf.n[b];
         probe_desc = a.kf.desc + po * 32;
@@ -418,9 +351,9 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             if (MODE == MODE_FRAME) {
                 if (a.last.usable[po + p]) {
                     const float* xw = a.last.xw + (po + p) * 3;
-                    const float xc = gemm3_row(Rcw[0], Rcw[1], Rcw[2], xw, tcw[0]);
-                    const float yc = gemm3_row(Rcw[3], Rcw[4], Rcw[5], xw, tcw[1]);
-                    const float zc = gemm3_row(Rcw[6], Rcw[7], Rcw[8], xw, tcw[2]);
+                    const float xc = ref::gemm_small_row_add(P.Rcw, xw, P.tcw[0]);
+                    const float yc = ref::gemm_small_row_add(P.Rcw + 3, xw, P.tcw[1]);
+                    const float zc = ref::gemm_small_row_add(P.Rcw + 6, xw, P.tcw[2]);
                     const float invzc = (float)(1.0 / (double)zc);
                     if (!(invzc < 0)) {
                         u = f.fx * xc * invzc + f.cx;
@@ -439,15 +372,15 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             } else if (MODE == MODE_KF) {
                 if (a.kf.usable[po + p] && !(a.kf.found && a.kf.found[po + p])) {                       // :1558
                     const float* X = a.kf.xw + (po + p) * 3;
-                    const float xc = gemm3_row(Rcw[0], Rcw[1], Rcw[2], X, tcw[0]);
-                    const float yc = gemm3_row(Rcw[3], Rcw[4], Rcw[5], X, tcw[1]);
-                    const float zc = gemm3_row(Rcw[6], Rcw[7], Rcw[8], X, tcw[2]);
+                    const float xc = ref::gemm_small_row_add(P.Rcw, X, P.tcw[0]);
+                    const float yc = ref::gemm_small_row_add(P.Rcw + 3, X, P.tcw[1]);
+                    const float zc = ref::gemm_small_row_add(P.Rcw + 6, X, P.tcw[2]);
                     const float invzc = (float)(1.0 / (double)zc);                                      // no depth test in this overload
                     u = f.fx * xc * invzc + f.cx;
                     v = f.fy * yc * invzc + f.cy;
                     if (!(u < f.min_x || u > f.max_x) && !(v < f.min_y || v > f.max_y)) {
-                        const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
-                        const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);   // cv::norm
+                        const float PO[3] = {X[0] - P.Ow[0], X[1] - P.Ow[1], X[2] - P.Ow[2]};
+                        const float dist3D = (float)ref::norm3(PO);
                         const float maxDistance = 1.2f * a.kf.max_dist[po + p], minDistance = 0.8f * a.kf.min_dist[po + p];
                         if (!(dist3D < minDistance || dist3D > maxDistance)) {
                             const float ratio = a.kf.max_dist[po + p] / dist3D;                        // MapPoint::PredictScale (src/MapPoint.cc:419-434)
@@ -474,7 +407,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
         int cnt = 0;
         if (valid) walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
         int total;
-        const int off = block_exscan(cnt, s.wsum, &total);
+        const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
         if (tid == 0) s.m_fit = 0;
         __syncthreads();
         const bool fits = p < NP && off + cnt <= CAND_CAP;
@@ -486,10 +419,10 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
         const int m = s.m_fit;
         if (fits && valid && cnt > 0) {
             uint32_t d[8];
-            load_desc(d, probe_desc + (size_t)p * 32);
+            ref::load_desc(d, probe_desc + (size_t)p * 32);
             int k = off;
             walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int idx, int oct) {
-                const int dist = hamming256(d, desc + (size_t)idx * 32);
+                const int dist = ref::hamming256(d, desc + (size_t)idx * 32);
                 s.cand[k++] = ((uint32_t)dist << 16) | ((uint32_t)(oct & 0xf) << 12) | (uint32_t)idx;
             });
         }
@@ -579,7 +512,7 @@ __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
         }
         const int cnt = valid ? hi - lo : 0;
         int total;
-        const int off = block_exscan(cnt, s.wsum, &total);
+        const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
         if (tid == 0) s.m_fit = 0;
         __syncthreads();
         const bool fits = p < NK && off + cnt <= CAND_CAP;
@@ -591,10 +524,10 @@ __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
         const int m = s.m_fit;
         if (fits && cnt > 0) {
             uint32_t d[8];
-            load_desc(d, g.kf_desc + (ko + kf) * 32);
+            ref::load_desc(d, g.kf_desc + (ko + kf) * 32);
             for (int k = 0; k < cnt; k++) {
                 const int idx = (int)(L.fkey[lo + k] & 0xfff);
-                const int dist = hamming256(d, g.f_desc + (fo + idx) * 32);
+                const int dist = ref::hamming256(d, g.f_desc + (fo + idx) * 32);
                 s.cand[off + k] = ((uint32_t)dist << 16) | (uint32_t)idx;
             }
         }
@@ -651,7 +584,7 @@ __global__ __launch_bounds__(64) void lsd_projection_kernel(LineArgs a) {
         const int minLevel = lvl - 1, maxLevel = lvl;
         const bool bCheckLevels = (minLevel > 0) || (maxLevel > 0);
         uint32_t d[8];
-        load_desc(d, a.ml_desc + (mo + j) * 32);
+        ref::load_desc(d, a.ml_desc + (mo + j) * 32);
         uint32_t k1 = 0xffffffffu, k2 = 0xffffffffu;   // dist << 16 | line index
         // pass 1: best ; pass 2: second best (stable order == ascending line index)
         for (int pass = 0; pass < 2; pass++) {
@@ -670,11 +603,11 @@ __global__ __launch_bounds__(64) void lsd_projection_kernel(LineArgs a) {
                         if (k.octave < minLevel) ok = false;
                         if (maxLevel >= 0 && k.octave > maxLevel) ok = false;
                     }
-                    if (ok && !((blk[i >> 5] >> (i & 31)) & 1u)) key = ((uint32_t)hamming256(d, ldesc + (size_t)i * 32) << 16) | (uint32_t)i;
+                    if (ok && !((blk[i >> 5] >> (i & 31)) & 1u)) key = ((uint32_t)ref::hamming256(d, ldesc + (size_t)i * 32) << 16) | (uint32_t)i;
                 }
                 kmin = min(kmin, key);
             }
-            kmin = wave_min_u32(kmin);
+            kmin = wave_min_u32_shfl(kmin);
             if (pass == 0) { k1 = kmin; if (k1 == 0xffffffffu) break; } else k2 = kmin;
         }
         if (k1 == 0xffffffffu) continue;
@@ -745,20 +678,6 @@ __global__ __launch_bounds__(64) void plane_match_kernel(const int32_t* n_planes
 }
 
 // ---- Frame::isInFrustum for points (src/Frame.cc:312-367) and lines (:369-438): one thread per map point / map line ------------
-struct FrustumPose { float Rcw[9], tcw[3], Ow[3]; };
-__device__ inline FrustumPose frustum_pose(const float* T) {
-    FrustumPose p;
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.Rcw[3 * r + c] = T[4 * r + c]; p.tcw[r] = T[4 * r + 3]; }
-    for (int i = 0; i < 3; i++) {   // Frame::UpdatePoseMatrices: mOw = -mRcw.t()*mtcw (general gemm path, double accumulation)
-        double s = 0;
-        for (int k = 0; k < 3; k++) s += (double)p.Rcw[3 * k + i] * (double)p.tcw[k];
-        p.Ow[i] = (float)(s * -1.0);
-    }
-    return p;
-}
-__device__ inline float norm3(const float* v) { return (float)sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); }
-__device__ inline double dot3(const float* a, const float* b) { return (double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2]; }
-
 __global__ __launch_bounds__(256) void frustum_points_kernel(planar_frame_view F, float lsf, int n_levels, const int32_t* __restrict__ n, int stride,
                                                              const uint8_t* __restrict__ valid, const float* __restrict__ xw,
                                                              const float* __restrict__ normal, const float* __restrict__ min_dist,
@@ -770,10 +689,11 @@ __global__ __launch_bounds__(256) void frustum_points_kernel(planar_frame_view F
     const size_t o = (size_t)b * stride + j;
     in_view[o] = 0;
     if (!valid[o]) return;
-    const FrustumPose P = frustum_pose(F.Tcw + (size_t)b * 16);
+    Pose P;
+    ref::load_pose_frame(F.Tcw + (size_t)b * 16, P);
     const float X[3] = {xw[3 * o], xw[3 * o + 1], xw[3 * o + 2]};
-    const float PcX = gemm3_row(P.Rcw[0], P.Rcw[1], P.Rcw[2], X, P.tcw[0]), PcY = gemm3_row(P.Rcw[3], P.Rcw[4], P.Rcw[5], X, P.tcw[1]);
-    const float PcZ = gemm3_row(P.Rcw[6], P.Rcw[7], P.Rcw[8], X, P.tcw[2]);
+    const float PcX = ref::gemm_small_row_add(P.Rcw, X, P.tcw[0]), PcY = ref::gemm_small_row_add(P.Rcw + 3, X, P.tcw[1]);
+    const float PcZ = ref::gemm_small_row_add(P.Rcw + 6, X, P.tcw[2]);
     if (PcZ < 0.0f) return;
     const float invz = 1.0f / PcZ;
     const float u = F.fx * PcX * invz + F.cx, v = F.fy * PcY * invz + F.cy;
@@ -781,10 +701,10 @@ __global__ __launch_bounds__(256) void frustum_points_kernel(planar_frame_view F
     if (v < F.min_y || v > F.max_y) return;
     const float maxDistance = 1.2f * max_dist[o], minDistance = 0.8f * min_dist[o];
     const float PO[3] = {X[0] - P.Ow[0], X[1] - P.Ow[1], X[2] - P.Ow[2]};
-    const float dist = norm3(PO);
+    const float dist = (float)ref::norm3(PO);
     if (dist < minDistance || dist > maxDistance) return;
     const float Pn[3] = {normal[3 * o], normal[3 * o + 1], normal[3 * o + 2]};
-    const float viewCos = (float)(dot3(PO, Pn) / (double)dist);
+    const float viewCos = (float)(ref::dot3_flat(PO, Pn) / (double)dist);
     if (viewCos < limit) return;
     const float ratio = max_dist[o] / dist;   // MapPoint::PredictScale (src/MapPoint.cc:419-434)
     int nScale = (int)ceilf((float)log((double)ratio) / lsf);
@@ -802,13 +722,14 @@ __global__ __launch_bounds__(256) void frustum_lines_kernel(planar_frame_view F,
     const size_t o = (size_t)b * stride + j;
     in_view[o] = 0;
     if (!valid[o]) return;
-    const FrustumPose P = frustum_pose(F.Tcw + (size_t)b * 16);
+    Pose P;
+    ref::load_pose_frame(F.Tcw + (size_t)b * 16, P);
     float SP[3], EP[3];
     for (int k = 0; k < 3; k++) { SP[k] = (float)xw6[6 * o + k]; EP[k] = (float)xw6[6 * o + 3 + k]; }
-    const float SPcX = gemm3_row(P.Rcw[0], P.Rcw[1], P.Rcw[2], SP, P.tcw[0]), SPcY = gemm3_row(P.Rcw[3], P.Rcw[4], P.Rcw[5], SP, P.tcw[1]);
-    const float SPcZ = gemm3_row(P.Rcw[6], P.Rcw[7], P.Rcw[8], SP, P.tcw[2]);
-    const float EPcX = gemm3_row(P.Rcw[0], P.Rcw[1], P.Rcw[2], EP, P.tcw[0]), EPcY = gemm3_row(P.Rcw[3], P.Rcw[4], P.Rcw[5], EP, P.tcw[1]);
-    const float EPcZ = gemm3_row(P.Rcw[6], P.Rcw[7], P.Rcw[8], EP, P.tcw[2]);
+    const float SPcX = ref::gemm_small_row_add(P.Rcw, SP, P.tcw[0]), SPcY = ref::gemm_small_row_add(P.Rcw + 3, SP, P.tcw[1]);
+    const float SPcZ = ref::gemm_small_row_add(P.Rcw + 6, SP, P.tcw[2]);
+    const float EPcX = ref::gemm_small_row_add(P.Rcw, EP, P.tcw[0]), EPcY = ref::gemm_small_row_add(P.Rcw + 3, EP, P.tcw[1]);
+    const float EPcZ = ref::gemm_small_row_add(P.Rcw + 6, EP, P.tcw[2]);
     if (SPcZ < 0.0f || EPcZ < 0.0f) return;
     const float invz1 = 1.0f / SPcZ;
     const float u1 = F.fx * SPcX * invz1 + F.cx, v1 = F.fy * SPcY * invz1 + F.cy;
@@ -821,10 +742,10 @@ __global__ __launch_bounds__(256) void frustum_lines_kernel(planar_frame_view F,
     const float maxDistance = 1.2f * max_dist[o], minDistance = 0.8f * min_dist[o];
     float OM[3];
     for (int k = 0; k < 3; k++) OM[k] = (float)((double)(SP[k] + EP[k]) * 0.5) - P.Ow[k];
-    const float dist = norm3(OM);
+    const float dist = (float)ref::norm3(OM);
     if (dist < minDistance || dist > maxDistance) return;
     const float pn[3] = {(float)normal[3 * o], (float)normal[3 * o + 1], (float)normal[3 * o + 2]};
-    const float viewCos = (float)(dot3(OM, pn) / (double)dist);
+    const float viewCos = (float)(ref::dot3_flat(OM, pn) / (double)dist);
     if (viewCos < limit) return;
     const float ratio = max_dist[o] / dist;   // MapLine::PredictScale (src/MapLine.cpp:381-390): not clamped
     in_view[o] = 1;
@@ -852,7 +773,6 @@ struct FuseArgs {
     const float *xw, *normal, *min_dist, *max_dist;
     int32_t *fuse_idx, *fuse_dist, *n_fused;
 };
-__device__ inline float fuse_norm3(const float* v) { return (float)sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); }   // cv::norm: double accumulation
 
 __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
     __shared__ FuseLds s;
@@ -864,15 +784,10 @@ __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
     const uint8_t* kdesc = f.desc + (size_t)b * f.stride * 32;
     if (tid == 0) s.n_fused = 0;
     build_grid(s, f, keys, N);                                   // KeyFrame::mGrid is the frame's (src/KeyFrame.cc:56-63)
-    // GetRotation / GetTranslation / GetCameraCenter (src/KeyFrame.cc:79-93, 107-130): Ow = -Rwc * tcw, general gemm path (double accumulation)
-    const float* T = f.Tcw + (size_t)b * 16;
-    float Rcw[9], tcw[3], Ow[3];
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcw[3 * r + c] = T[4 * r + c]; tcw[r] = T[4 * r + 3]; }
-    for (int i = 0; i < 3; i++) {
-        double sum = 0;
-        for (int k = 0; k < 3; k++) sum += (double)Rcw[3 * k + i] * (double)tcw[k];
-        Ow[i] = (float)(sum * -1.0);
-    }
+    // GetRotation / GetTranslation / GetCameraCenter (src/KeyFrame.cc:79-93, 107-130).  The view handed in is a planar_frame_view and the oracle forms its
+    // centre as a Frame's (general gemm path), so the frame loader it is; a KeyFrame's own SetPose would take load_pose_keyframe.
+    Pose P;
+    ref::load_pose_frame(f.Tcw + (size_t)b * 16, P);
     const size_t po = a.shared ? 0 : (size_t)b * a.stride;
     const size_t oo = (size_t)b * a.stride;
     const int NP = a.n[a.shared ? 0 : b];
@@ -881,8 +796,8 @@ __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
         int bestDist = 256, bestIdx = -1;
         if (j < NP && a.usable[po + j]) {                                              // rows beyond n[b] read -1 / 256
             const float* X = a.xw + (po + j) * 3;
-            const float xc = gemm3_row(Rcw[0], Rcw[1], Rcw[2], X, tcw[0]), yc = gemm3_row(Rcw[3], Rcw[4], Rcw[5], X, tcw[1]);
-            const float zc = gemm3_row(Rcw[6], Rcw[7], Rcw[8], X, tcw[2]);
+            const float xc = ref::gemm_small_row_add(P.Rcw, X, P.tcw[0]), yc = ref::gemm_small_row_add(P.Rcw + 3, X, P.tcw[1]);
+            const float zc = ref::gemm_small_row_add(P.Rcw + 6, X, P.tcw[2]);
             if (!(zc < 0.0f)) {                                                        // :858
                 const float invz = 1.0f / zc;
                 const float x = xc * invz, y = yc * invz;
@@ -890,17 +805,17 @@ __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
                 if (u >= f.min_x && u < f.max_x && v >= f.min_y && v < f.max_y) {       // KeyFrame::IsInImage
                     const float ur = u - f.bf * invz;
                     const float maxDistance = 1.2f * a.max_dist[po + j], minDistance = 0.8f * a.min_dist[po + j];
-                    const float PO[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
-                    const float dist3D = fuse_norm3(PO);
+                    const float PO[3] = {X[0] - P.Ow[0], X[1] - P.Ow[1], X[2] - P.Ow[2]};
+                    const float dist3D = (float)ref::norm3(PO);
                     const float* Pn = a.normal + (po + j) * 3;
-                    const double dotp = (double)PO[0] * Pn[0] + (double)PO[1] * Pn[1] + (double)PO[2] * Pn[2];
+                    const double dotp = ref::dot3_flat(PO, Pn);
                     if (!(dist3D < minDistance || dist3D > maxDistance) && !(dotp < 0.5 * (double)dist3D)) {     // :878, :884
                         const float ratio = a.max_dist[po + j] / dist3D;                // MapPoint::PredictScale (src/MapPoint.cc:402-417)
                         int lvl = (int)ceilf((float)log((double)ratio) / a.lsf);
                         if (lvl < 0) lvl = 0; else if (lvl >= a.n_levels) lvl = a.n_levels - 1;
                         const float radius = a.th * f.scale_factors[lvl];
                         uint32_t d[8];
-                        load_desc(d, a.desc + (po + j) * 32);
+                        ref::load_desc(d, a.desc + (po + j) * 32);
                         // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678): the frame's window walk without level bounds
                         const int nMinCellX = max(0, (int)floorf((u - f.min_x - radius) * f.grid_w_inv));
                         const int nMaxCellX = min(PLANAR_GRID_COLS - 1, (int)ceilf((u - f.min_x + radius) * f.grid_w_inv));
@@ -925,7 +840,7 @@ __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
                                         const float e2 = ex * ex + ey * ey;
                                         if ((double)(e2 * a.inv_sigma2[kl]) > 5.99) continue;                   // :938
                                     }
-                                    const int dist = hamming256(d, kdesc + (size_t)idx * 32);
+                                    const int dist = ref::hamming256(d, kdesc + (size_t)idx * 32);
                                     if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
                                 }
                             }
@@ -965,14 +880,8 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
     const int NM = a.n_ml[a.shared ? 0 : b];
     const planar_keyline* kl = a.keylines + lo;
     const uint8_t* ldesc = a.ldesc + lo * 32;
-    const float* T = f.Tcw + (size_t)b * 16;
-    float Rcw[9], tcw[3], Ow[3];
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rcw[3 * r + c] = T[4 * r + c]; tcw[r] = T[4 * r + 3]; }
-    for (int i = 0; i < 3; i++) {
-        double sum = 0;
-        for (int k = 0; k < 3; k++) sum += (double)Rcw[3 * k + i] * (double)tcw[k];
-        Ow[i] = (float)(sum * -1.0);
-    }
+    Pose P;
+    ref::load_pose_frame(f.Tcw + (size_t)b * 16, P);   // as fuse_kernel
     int fused = 0;
     for (int j = lane; j < a.ml_stride; j += 64) {
         int bestDist = 0x7fffffff, bestIdx = -1;
@@ -982,10 +891,10 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
         if (go) {
             float SP[3], EP[3];
             for (int k = 0; k < 3; k++) { SP[k] = (float)a.xw6[6 * (mo + j) + k]; EP[k] = (float)a.xw6[6 * (mo + j) + 3 + k]; }
-            const float SPcX = gemm3_row(Rcw[0], Rcw[1], Rcw[2], SP, tcw[0]), SPcY = gemm3_row(Rcw[3], Rcw[4], Rcw[5], SP, tcw[1]);
-            const float SPcZ = gemm3_row(Rcw[6], Rcw[7], Rcw[8], SP, tcw[2]);
-            const float EPcX = gemm3_row(Rcw[0], Rcw[1], Rcw[2], EP, tcw[0]), EPcY = gemm3_row(Rcw[3], Rcw[4], Rcw[5], EP, tcw[1]);
-            const float EPcZ = gemm3_row(Rcw[6], Rcw[7], Rcw[8], EP, tcw[2]);
+            const float SPcX = ref::gemm_small_row_add(P.Rcw, SP, P.tcw[0]), SPcY = ref::gemm_small_row_add(P.Rcw + 3, SP, P.tcw[1]);
+            const float SPcZ = ref::gemm_small_row_add(P.Rcw + 6, SP, P.tcw[2]);
+            const float EPcX = ref::gemm_small_row_add(P.Rcw, EP, P.tcw[0]), EPcY = ref::gemm_small_row_add(P.Rcw + 3, EP, P.tcw[1]);
+            const float EPcZ = ref::gemm_small_row_add(P.Rcw + 6, EP, P.tcw[2]);
             go = !(SPcZ < 0.0f || EPcZ < 0.0f);
             const float invz1 = 1.0f / SPcZ, invz2 = 1.0f / EPcZ;
             u1 = f.fx * SPcX * invz1 + f.cx; v1 = f.fy * SPcY * invz1 + f.cy;
@@ -994,11 +903,11 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
             if (u2 < f.min_x || u2 > f.max_x || v2 < f.min_y || v2 > f.max_y) go = false;
             const float maxDistance = 1.2f * a.max_dist[mo + j], minDistance = 0.8f * a.min_dist[mo + j];
             float OM[3];
-            for (int k = 0; k < 3; k++) OM[k] = (float)((double)(SP[k] + EP[k]) * 0.5) - Ow[k];
-            const float dist = fuse_norm3(OM);
+            for (int k = 0; k < 3; k++) OM[k] = (float)((double)(SP[k] + EP[k]) * 0.5) - P.Ow[k];
+            const float dist = (float)ref::norm3(OM);
             if (dist < minDistance || dist > maxDistance) go = false;
             const float pn[3] = {(float)a.normal[3 * (mo + j)], (float)a.normal[3 * (mo + j) + 1], (float)a.normal[3 * (mo + j) + 2]};
-            const double dotp = (double)OM[0] * pn[0] + (double)OM[1] * pn[1] + (double)OM[2] * pn[2];
+            const double dotp = ref::dot3_flat(OM, pn);
             if (dotp < 0.5 * (double)dist) go = false;
             const float ratio = a.max_dist[mo + j] / dist;                   // MapLine::PredictScale: not clamped
             lvl = (int)ceilf((float)log((double)ratio) / a.lsf);
@@ -1007,7 +916,7 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
         }
         if (go) {
             uint32_t d[8];
-            load_desc(d, a.ml_desc + (mo + j) * 32);
+            ref::load_desc(d, a.ml_desc + (mo + j) * 32);
             for (int i = 0; i < NLn; i++) {
                 const planar_keyline k = kl[i];
                 const double mx = 0.5 * (double)(u1 + u2) - (double)k.pt_x, my = 0.5 * (double)(v1 + v2) - (double)k.pt_y;
@@ -1016,7 +925,7 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
                 const float slope = (v1 - v2) / (u1 - u2) - k.angle;
                 if ((double)slope > (double)radius * 0.01) continue;
                 if (k.octave < lvl - 1 || k.octave > lvl) continue;          // :968
-                const int dist = hamming256(d, ldesc + (size_t)i * 32);
+                const int dist = ref::hamming256(d, ldesc + (size_t)i * 32);
                 if (dist < bestDist) { bestDist = dist; bestIdx = i; }
             }
         }

@@ -23,6 +23,7 @@
 //   K7 lbd_describe     one wavefront per kept line: 63 support rows on 63 lanes, band sums in reference order
 // HBM traffic is small (a 640x480 frame: 0.3 MB in, 3 KB out, ~5 MB of L2-resident intermediates); K4 is latency bound.
 #include "common.h"
+#include "ref_arith.h"
 #include "wave_ops.h"
 #include "lsd_nfa.h"
 #include "isort.h"
@@ -248,20 +249,6 @@ __global__ __launch_bounds__(256) void lsd_grad(const Plan* __restrict__ plan, c
 }
 
 // ---- K3: the visiting order: descending 1024-bin norm, ties as std::sort leaves them ----------------------------------------------------
-template <int NW>   // exclusive scan over a workgroup of NW wavefronts
-__device__ inline int block_exscan(int v, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    __syncthreads();
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int i = 0; i < NW; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
-    *total = tot;
-    return base + inc - v;
-}
-
 __device__ __forceinline__ void wave_sync();
 __device__ __forceinline__ void lds_sync();
 // lsd.cpp sorts all (w-1)(h-1) gradient pixels by their 1024-bin norm with std::sort(compare_norm: a.norm > b.norm), so pixels of equal bin are
@@ -463,7 +450,7 @@ __global__ __launch_bounds__(SORT_NT) void lsd_sort_raster(const Plan* __restric
         int total;
         {   // exclusive scan of the 32 x SORT_NW counters in (digit, wavefront) order by the first wavefronts
             const int v = tid < 32 * SORT_NW ? wcnt[tid] : 0;
-            const int ex = block_exscan<SORT_NW>(v, wsum, &total);
+            const int ex = ref::block_exscan<SORT_NW>(v, wsum, &total);
             if (tid < 32 * SORT_NW) wcnt[tid] = ex;
         }
         __syncthreads();

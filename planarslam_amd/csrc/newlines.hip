@@ -19,13 +19,13 @@
 //   * nl_average_dir_kernel: one thread per map line.
 // Float / double mix as the reference has it, -ffp-contract=off; bit-exact with tests/golden/new_lines_ref.npz and tests/host_shim/new_lines_host.cpp.
 #include "common.h"
-#include "tri_shared.h"
+#include "ref_arith.h"
 
 namespace planar {
 namespace nl {
 
-using tri::NT;
-using tri::Pose;
+using ref::Pose;
+constexpr int NT = 256;
 constexpr int MAXL = PLANAR_MAX_KEYFRAME_LINES;
 constexpr int NBINS = 257;   // a Hamming distance of 32 bytes, a difference of two, or the absolute deviation of either from a median: 0 .. 256
 static_assert(MAXL <= NT, "one thread owns one query line");
@@ -87,15 +87,15 @@ __device__ inline int iabs(int v) { return v < 0 ? -v : v; }
 
 // KeyFrame::obtain3DLine (src/KeyFrame.cc:738-747): the end points narrowed to float, Twc applied on the float gemm path
 __device__ inline void obtain_3d_line(const double* L, const float* Twc, float* sp, float* ep) {
-    const float a0 = (float)L[0], a1 = (float)L[1], a2 = (float)L[2], b0 = (float)L[3], b1 = (float)L[4], b2 = (float)L[5];
+    const float a[3] = {(float)L[0], (float)L[1], (float)L[2]}, b[3] = {(float)L[3], (float)L[4], (float)L[5]};
     for (int i = 0; i < 3; i++) {
-        sp[i] = (float)((double)tri::row3(Twc + 4 * i, a0, a1, a2) + (double)Twc[4 * i + 3]);
-        ep[i] = (float)((double)tri::row3(Twc + 4 * i, b0, b1, b2) + (double)Twc[4 * i + 3]);
+        sp[i] = ref::gemm_small_row_add(Twc + 4 * i, a, Twc[4 * i + 3]);
+        ep[i] = ref::gemm_small_row_add(Twc + 4 * i, b, Twc[4 * i + 3]);
     }
 }
 
 // Rcw.row(i).dot(x) + tcw(i) as a float
-__device__ inline float cam_coord(const Pose& p, int i, const float* x) { return (float)(tri::dot3(p.Rcw + 3 * i, x[0], x[1], x[2]) + (double)p.tcw[i]); }
+__device__ inline float cam_coord(const Pose& p, int i, const float* x) { return (float)(ref::dot3(p.Rcw + 3 * i, x) + (double)p.tcw[i]); }
 
 // the reprojection gate of one end point in one key frame (src/LocalMapping.cc:940-988): true when the pair goes on
 __device__ inline bool reproj_ok(const planar_tri_camera& cam, const Pose& p, const float* x, float z, float px, float py, float sigma2) {
@@ -131,10 +131,10 @@ __device__ bool line_gates(const Args& a, const Lds& s, int e1, int e2, int n1, 
     if (!reproj_ok(cam, p1, ep, zep1, kl1.end_x, kl1.end_y, sigma1)) return false;
     if (!reproj_ok(cam, p2, sp, zsp2, kl2.start_x, kl2.start_y, sigma2)) return false;
     if (!reproj_ok(cam, p2, ep, zep2, kl2.end_x, kl2.end_y, sigma2)) return false;
-    const float distsp1 = (float)tri::norm3(sp[0] - p1.Ow[0], sp[1] - p1.Ow[1], sp[2] - p1.Ow[2]);
-    const float distep1 = (float)tri::norm3(ep[0] - p1.Ow[0], ep[1] - p1.Ow[1], ep[2] - p1.Ow[2]);
-    const float distsp2 = (float)tri::norm3(sp[0] - p2.Ow[0], sp[1] - p2.Ow[1], sp[2] - p2.Ow[2]);
-    const float distep2 = (float)tri::norm3(ep[0] - p2.Ow[0], ep[1] - p2.Ow[1], ep[2] - p2.Ow[2]);
+    const float distsp1 = (float)ref::norm3(sp[0] - p1.Ow[0], sp[1] - p1.Ow[1], sp[2] - p1.Ow[2]);
+    const float distep1 = (float)ref::norm3(ep[0] - p1.Ow[0], ep[1] - p1.Ow[1], ep[2] - p1.Ow[2]);
+    const float distsp2 = (float)ref::norm3(sp[0] - p2.Ow[0], sp[1] - p2.Ow[1], sp[2] - p2.Ow[2]);
+    const float distep2 = (float)ref::norm3(ep[0] - p2.Ow[0], ep[1] - p2.Ow[1], ep[2] - p2.Ow[2]);
     if (distsp1 == 0 || distep1 == 0 || distsp2 == 0 || distep2 == 0) return false;
     const float ratioFactor = 1.5f * cam.scale_factor;
     const float ratioDistsp = distsp2 / distsp1, ratioDistep = distep2 / distep1;
@@ -150,7 +150,7 @@ template <int MODE>
 __global__ __launch_bounds__(NT) void nl_pair_kernel(const Args a) {
     __shared__ Lds s;
     const int k = blockIdx.x, e1 = blockIdx.y, tid = threadIdx.x;
-    const int n1 = tri::clamp_n(a.k1.n[e1], a.k1.stride);
+    const int n1 = ref::clamp_n(a.k1.n[e1], a.k1.stride);
     const size_t o1 = (size_t)e1 * a.k1.stride;
     int e2 = e1;
     if (MODE == CREATE) {
@@ -160,16 +160,16 @@ __global__ __launch_bounds__(NT) void nl_pair_kernel(const Args a) {
         e2 = e1 * a.max_neigh + k;
     }
     const size_t o2 = (size_t)e2 * a.k2.stride;
-    const int n2 = tri::clamp_n(a.k2.n[e2], a.k2.stride);
+    const int n2 = ref::clamp_n(a.k2.n[e2], a.k2.stride);
     const bool mine = tid < n1;
     int32_t* const surv = MODE == CREATE ? a.surv_idx2 + ((size_t)e1 * a.max_neigh + k) * a.k1.stride : nullptr;
 
     if (tid == 0) {
         s.skip = 0; s.count = 0; s.sel = 0;
         if (MODE == CREATE) {   // the baseline test (:839-845): cv::norm accumulates in double
-            tri::load_pose(a.k1.Tcw + (size_t)e1 * 16, s.p1);
-            tri::load_pose(a.k2.Tcw + (size_t)e2 * 16, s.p2);
-            const float baseline = (float)tri::norm3(s.p2.Ow[0] - s.p1.Ow[0], s.p2.Ow[1] - s.p1.Ow[1], s.p2.Ow[2] - s.p1.Ow[2]);
+            ref::load_pose_keyframe(a.k1.Tcw + (size_t)e1 * 16, s.p1);
+            ref::load_pose_keyframe(a.k2.Tcw + (size_t)e2 * 16, s.p2);
+            const float baseline = (float)ref::norm3(s.p2.Ow[0] - s.p1.Ow[0], s.p2.Ow[1] - s.p1.Ow[1], s.p2.Ow[2] - s.p1.Ow[2]);
             if (baseline < a.k2.mb[e2]) s.skip = 1;
         }
     }
@@ -195,8 +195,7 @@ __global__ __launch_bounds__(NT) void nl_pair_kernel(const Args a) {
         const uint4 qa = q[0], qb = q[1];
         for (int t = 0; t < n2; t++) {
             const uint4 ta = s.t[2 * t], tb = s.t[2 * t + 1];
-            const int d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) + __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) +
-                          __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+            const int d = ref::hamming256(qa, qb, ta, tb);
             if (d < d0) { d1 = d0; d0 = d; i0 = t; }
             else if (d < d1) d1 = d;
         }
@@ -245,7 +244,7 @@ __global__ __launch_bounds__(NT) void nl_pair_kernel(const Args a) {
 __global__ __launch_bounds__(NT) void nl_compact_kernel(const Args a) {
     __shared__ int wsum[NT / 64];
     const int e1 = blockIdx.x, tid = threadIdx.x;
-    const int n1 = tri::clamp_n(a.k1.n[e1], a.k1.stride);
+    const int n1 = ref::clamp_n(a.k1.n[e1], a.k1.stride);
     const size_t o1 = (size_t)e1 * a.k1.stride;
     int nn = a.n_neigh[e1];
     nn = nn < 0 ? 0 : (nn > a.max_neigh ? a.max_neigh : nn);
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(NT) void nl_compact_kernel(const Args a) {
         const int idx2 = tid < n1 ? a.surv_idx2[so] : -1;
         const bool flag = !taken && idx2 >= 0;
         int total;
-        const int r = tri::block_rank(flag, wsum, &total);
+        const int r = ref::block_rank<NT / 64>(flag, wsum, &total);
         if (flag) {   // out + r < n1 <= stride: every idx1 is accepted at most once
             const size_t j = o1 + out + r;
             a.new_neigh[j] = k; a.new_idx1[j] = tid; a.new_idx2[j] = idx2;
@@ -275,11 +274,11 @@ __global__ __launch_bounds__(256) void nl_average_dir_kernel(const int32_t* n, i
                                                              const int32_t* ref_octave, const int32_t* obs_off, const float* obs_ow, const Scales S, double* normal,
                                                              float* min_dist, float* max_dist) {
     const int g = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= tri::clamp_n(n[g], stride)) return;
+    if (i >= ref::clamp_n(n[g], stride)) return;
     const size_t j = (size_t)g * stride + i;
     if (valid && !valid[j]) return;
     Pose p;
-    tri::load_pose(ref_Tcw + (size_t)g * 16, p);
+    ref::load_pose_keyframe(ref_Tcw + (size_t)g * 16, p);
     const double* P = xw6 + j * 6;
     const float* ow = nullptr;   // null: the reference key frame alone observes the line
     int cnt = 1;
@@ -296,7 +295,7 @@ __global__ __launch_bounds__(256) void nl_average_dir_kernel(const int32_t* n, i
     }
     // cv: MP = 0.5 * (SP + EP) in float, CM = MP - Ow, dist = cv::norm(CM)
     const float cx = ((float)P[0] + (float)P[3]) * 0.5f - p.Ow[0], cy = ((float)P[1] + (float)P[4]) * 0.5f - p.Ow[1], cz = ((float)P[2] + (float)P[5]) * 0.5f - p.Ow[2];
-    const float dist = (float)tri::norm3(cx, cy, cz);
+    const float dist = (float)ref::norm3(cx, cy, cz);
     const int level = ref_octave[j] & (PLANAR_MAX_LEVELS - 1);
     float sf = S.sf[0];   // a select per level: a kernel argument indexed by a run-time value would be copied to scratch
 #pragma unroll

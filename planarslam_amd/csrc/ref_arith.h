@@ -1,0 +1,149 @@
+// planarslam_amd/csrc/ref_arith.h — the reference's float / double arithmetic, one definition per path, for the matcher and map-creation kernels
+// (guided.hip, frame.hip, triangulate.hip, newlines.hip; lsd.hip takes the workgroup scan).  Which path of OpenCV a small product takes decides its
+// last bit, so a name here says the path and its comment where the reference takes it.  Expressions only, device code only;
+// -ffp-contract=off.  The checkers (oracle/, tests/host_shim/) restate all of this on their own and must not include this file.
+#pragma once
+#include "common.h"
+
+namespace planar {
+namespace ref {
+
+constexpr int HISTO_LENGTH = 30;   // src/ORBmatcher.cc:40
+
+__device__ inline int clamp_n(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
+
+// ---- cv::gemm, CV_32F small-matrix path (a plain 3x3 by 3x1 or 3x3 product, no transposed operand): float products summed left to right ----
+// one row, before alpha / beta: ray = Rwc * xn (src/LocalMapping.cc:402-403), the negated row of KeyFrame::SetPose below
+__device__ inline float gemm_small_row(float a0, float a1, float a2, float x0, float x1, float x2) {
+    float t = a0 * x0;
+    t = t + a1 * x1;
+    t = t + a2 * x2;
+    return t;
+}
+// the row with its "+ c": (float)(t * alpha + c * beta), alpha = beta = 1.0 doubles.  Rcw * x3Dw + tcw (src/ORBmatcher.cc:1426, :1563, :857),
+// mRwc * x3Dc + mOw (src/Frame.cc:631), Twc.rowRange(0, 3).colRange(0, 3) * x3Dc + Twc.rowRange(0, 3).col(3) (src/KeyFrame.cc:732, :741, :743)
+__device__ inline float gemm_small_row_add(float a0, float a1, float a2, float x0, float x1, float x2, float c) {
+    const float t = gemm_small_row(a0, a1, a2, x0, x1, x2);
+    return (float)((double)t * 1.0 + (double)c * 1.0);
+}
+__device__ inline float gemm_small_row_add(const float* a, const float* x, float c) { return gemm_small_row_add(a[0], a[1], a[2], x[0], x[1], x[2], c); }
+
+// ---- double accumulation: Mat::dot (ray1.dot(ray2), Rcw.row(i).dot(x3Dt): src/LocalMapping.cc:404, :448-483) and one row of cv::gemm's general
+// path, which a transposed operand forces (-mRcw.t() * mtcw, src/Frame.cc:305).  Both start from zero ... ----
+__device__ inline double dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
+    double s = 0;
+    s += (double)a0 * (double)b0; s += (double)a1 * (double)b1; s += (double)a2 * (double)b2;
+    return s;
+}
+__device__ inline double dot3(const float* a, const float* b) { return dot3(a[0], a[1], a[2], b[0], b[1], b[2]); }
+__device__ inline double gemm_general_row(float a0, float a1, float a2, float x0, float x1, float x2) { return dot3(a0, a1, a2, x0, x1, x2); }
+// ... and this is the same sum as one expression, without the leading zero: it differs from dot3 in the sign of a zero result only (three products of
+// -0 give -0 here, +0 there).  PO.dot(Pn) of the frustum and fuse kernels (src/Frame.cc:350, src/ORBmatcher.cc:888) and the centre of the stereo kernel
+// were written this way and are pinned to their device code; new code takes dot3.
+__device__ inline double dot3_flat(float a0, float a1, float a2, float b0, float b1, float b2) {
+    return (double)a0 * (double)b0 + (double)a1 * (double)b1 + (double)a2 * (double)b2;
+}
+__device__ inline double dot3_flat(const float* a, const float* b) { return dot3_flat(a[0], a[1], a[2], b[0], b[1], b[2]); }
+
+// cv::norm of a 3-vector (NORM_L2: squares accumulated in double): src/Frame.cc:342, src/ORBmatcher.cc:879, :1579, src/LocalMapping.cc:349, :404, :506-509,
+// :841, :992-1001, src/MapPoint.cc:372, :377
+__device__ inline double norm3(float a0, float a1, float a2) {
+    double s = 0;
+    s += (double)a0 * (double)a0; s += (double)a1 * (double)a1; s += (double)a2 * (double)a2;
+    return sqrt(s);
+}
+__device__ inline double norm3(const float* v) { return norm3(v[0], v[1], v[2]); }
+
+// ---- the pose of a view and its camera centre.  The two classes of the reference form the centre on different paths, and the results differ in the
+// last bit: a Frame's pose goes through load_pose_frame, a KeyFrame's through load_pose_keyframe. ----
+struct Pose { float Rcw[9], tcw[3], Ow[3]; };
+
+__device__ inline void load_Rt(const float* T, Pose& p) {
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.Rcw[3 * r + c] = T[4 * r + c]; p.tcw[r] = T[4 * r + 3]; }
+}
+// one component of mOw = -mRcw.t() * mtcw from its accumulated row: alpha = -1 applied in double, then narrowed
+__device__ inline float gemm_general_neg(double s) { return (float)(s * -1.0); }
+// Frame::UpdatePoseMatrices (src/Frame.cc:301-305): mOw = -mRcw.t() * mtcw, the transposed operand takes the general path.  The matchers' own
+// "twc / Ow = -Rcw.t() * tcw" (src/ORBmatcher.cc:1408, :1543) is the same product.
+__device__ inline void load_pose_frame(const float* T, Pose& p) {
+    load_Rt(T, p);
+    for (int i = 0; i < 3; i++) p.Ow[i] = gemm_general_neg(gemm_general_row(p.Rcw[i], p.Rcw[3 + i], p.Rcw[6 + i], p.tcw[0], p.tcw[1], p.tcw[2]));
+}
+// KeyFrame::SetPose (src/KeyFrame.cc:79-93): Ow = -Rwc * tcw with Rwc = Rcw.t() a matrix of its own, so the small-matrix path, (float)((double)t * -1.0)
+__device__ inline void load_pose_keyframe(const float* T, Pose& p) {
+    load_Rt(T, p);
+    for (int i = 0; i < 3; i++) p.Ow[i] = (float)((double)gemm_small_row(p.Rcw[i], p.Rcw[3 + i], p.Rcw[6 + i], p.tcw[0], p.tcw[1], p.tcw[2]) * -1.0);
+}
+
+// ---- ORB / LBD descriptors: the Hamming distance of two 256-bit descriptors (ORBmatcher::DescriptorDistance, src/ORBmatcher.cc:1712; cv::NORM_HAMMING) ----
+__device__ inline int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
+           __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+// a descriptor kept as eight words against one in memory (16-byte aligned)
+__device__ inline void load_desc(uint32_t* a, const uint8_t* p) {
+    const uint4* q = (const uint4*)p;
+    const uint4 x = q[0], y = q[1];
+    a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w; a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
+}
+__device__ inline int hamming256(const uint32_t* a, const uint8_t* b) {
+    const uint4* p = (const uint4*)b;
+    return hamming256(make_uint4(a[0], a[1], a[2], a[3]), make_uint4(a[4], a[5], a[6], a[7]), p[0], p[1]);
+}
+
+// ---- the rotation-consistency check ----
+// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1666-1708) on bin counts
+__device__ inline void three_maxima(const int* h, int& ind1, int& ind2, int& ind3) {
+    int max1 = 0, max2 = 0, max3 = 0;
+    ind1 = ind2 = ind3 = -1;
+    for (int i = 0; i < HISTO_LENGTH; i++) {
+        const int sz = h[i];
+        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
+        else if (sz > max3) { max3 = sz; ind3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
+}
+// the histogram bin of a match (src/ORBmatcher.cc:1498-1503 and its copies at :245, :482, :614, :773, :1630)
+__device__ inline int rot_bin(float a_from, float a_to) {
+    const float factor = 1.0f / HISTO_LENGTH;
+    float rot = a_from - a_to;
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * factor);
+    if (bin == HISTO_LENGTH) bin = 0;
+    return bin;
+}
+
+// ---- workgroup scans over NW wavefronts; wsum holds NW ints of LDS, every thread of the workgroup calls ----
+// exclusive scan of one int per thread: returns the exclusive prefix, the total in *total
+template <int NW>
+__device__ inline int block_exscan(int v, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+    __syncthreads();
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int i = 0; i < NW; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
+    *total = tot;
+    return base + inc - v;
+}
+// the one-flag form: the rank of this thread's flag among the set ones, their number in *total
+template <int NW>
+__device__ inline int block_rank(bool flag, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (lane == 0) wsum[w] = __popcll(m);
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int i = 0; i < NW; i++) { if (i < w) base += wsum[i]; tot += wsum[i]; }
+    *total = tot;
+    return base + before;
+}
+
+}  // namespace ref
+}  // namespace planar

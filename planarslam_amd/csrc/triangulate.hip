@@ -16,13 +16,16 @@
 //   * tri_orient_kernel (the plain search with check_orientation): the 30-bin histogram, ComputeThreeMaxima and nmatches.
 // Float / double mix as the reference has it, -ffp-contract=off; bit-exact with tests/golden/new_points_ref.npz (tools/gen_golden_new_points.py: the real reference) and tests/host_shim/new_points_host.cpp.
 #include "common.h"
-#include "tri_shared.h"
+#include "ref_arith.h"
 
 namespace planar {
 namespace tri {
 
+using ref::HISTO_LENGTH;
+using ref::Pose;
+constexpr int NT = 256;
 constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
-constexpr int TH_LOW = 50, HISTO_LENGTH = 30;   // src/ORBmatcher.cc:39-40
+constexpr int TH_LOW = 50;   // src/ORBmatcher.cc:39
 constexpr int NODE_NEVER = -2;                   // LDS node value of a feature of key frame 2 that no idx1 may take
 
 struct Args {
@@ -85,7 +88,7 @@ __device__ void compute_pair(const planar_tri_camera& cam, PairLds& pr) {
     mul33(a.Rcw, R2t, R12);
     for (int i = 0; i < 9; i++) nR1[i] = a.Rcw[i] * -1.0f;
     mul33(nR1, R2t, P);
-    for (int i = 0; i < 3; i++) t12[i] = (float)((double)row3(P + 3 * i, b.tcw[0], b.tcw[1], b.tcw[2]) + (double)a.tcw[i]);
+    for (int i = 0; i < 3; i++) t12[i] = ref::gemm_small_row_add(P + 3 * i, b.tcw, a.tcw[i]);
     const float t12x[9] = {0, -t12[2], t12[1], t12[2], 0, -t12[0], -t12[1], t12[0], 0};
     const float K[9] = {cam.fx, 0, cam.cx, 0, cam.fy, cam.cy, 0, 0, 1};
     float Kt[9], Kti[9], Ki[9], M1[9], M2[9], F[9];
@@ -97,7 +100,7 @@ __device__ void compute_pair(const planar_tri_camera& cam, PairLds& pr) {
     mul33(M2, Ki, F);
     for (int i = 0; i < 9; i++) pr.F12[i] = F[i];
     float C2[3];
-    for (int i = 0; i < 3; i++) C2[i] = (float)((double)row3(b.Rcw + 3 * i, a.Ow[0], a.Ow[1], a.Ow[2]) + (double)b.tcw[i]);
+    for (int i = 0; i < 3; i++) C2[i] = ref::gemm_small_row_add(b.Rcw + 3 * i, a.Ow, b.tcw[i]);
     const float invz = 1.0f / C2[2];
     pr.ex = cam.fx * C2[0] * invz + cam.cx;
     pr.ey = cam.fy * C2[1] * invz + cam.cy;
@@ -196,8 +199,7 @@ __device__ int search_one(const Args& a, const Lds& s, const Feat1& f, size_t o2
         if (s.node2[idx2] != f.node) continue;
         const uint4* d2 = (const uint4*)(a.k2.desc + (o2 + idx2) * 32);
         const uint4 e0 = d2[0], e1 = d2[1];
-        const int dist = __popc(f.d0.x ^ e0.x) + __popc(f.d0.y ^ e0.y) + __popc(f.d0.z ^ e0.z) + __popc(f.d0.w ^ e0.w) + __popc(f.d1.x ^ e1.x) +
-                         __popc(f.d1.y ^ e1.y) + __popc(f.d1.z ^ e1.z) + __popc(f.d1.w ^ e1.w);
+        const int dist = ref::hamming256(f.d0, f.d1, e0, e1);
         if (dist > TH_LOW || dist > bestDist) continue;
         const planar_keypoint& kp2 = a.k2.keys_un[o2 + idx2];
         const float x2 = kp2.x, y2 = kp2.y;
@@ -216,8 +218,8 @@ __device__ int search_one(const Args& a, const Lds& s, const Feat1& f, size_t o2
 
 // KeyFrame::UnprojectStereo (src/KeyFrame.cc:720-736): the DISTORTED key point, Twc
 __device__ inline void unproject(const planar_tri_camera& cam, const planar_keypoint& kp, float z, const float* Twc, float* x3D) {
-    const float x = (kp.x - cam.cx) * z * cam.invfx, y = (kp.y - cam.cy) * z * cam.invfy;
-    for (int i = 0; i < 3; i++) x3D[i] = (float)((double)row3(Twc + 4 * i, x, y, z) + (double)Twc[4 * i + 3]);
+    const float xc[3] = {(kp.x - cam.cx) * z * cam.invfx, (kp.y - cam.cy) * z * cam.invfy, z};
+    for (int i = 0; i < 3; i++) x3D[i] = ref::gemm_small_row_add(Twc + 4 * i, xc, Twc[4 * i + 3]);
 }
 
 // the body of the triangulation loop (src/LocalMapping.cc:387-519) for one match: true when the reference creates the point
@@ -234,10 +236,10 @@ __device__ bool triangulate(const Args& a, const PairLds& pr, const Feat1& f, si
     const Pose &p1 = pr.p1, &p2 = pr.p2;
     float ray1[3], ray2[3];
     for (int i = 0; i < 3; i++) {   // Rwc * xn, Rwc = Rcw.t()
-        float t = p1.Rcw[i] * xn1x; t = t + p1.Rcw[3 + i] * xn1y; t = t + p1.Rcw[6 + i] * 1.0f; ray1[i] = t;
-        float u = p2.Rcw[i] * xn2x; u = u + p2.Rcw[3 + i] * xn2y; u = u + p2.Rcw[6 + i] * 1.0f; ray2[i] = u;
+        ray1[i] = ref::gemm_small_row(p1.Rcw[i], p1.Rcw[3 + i], p1.Rcw[6 + i], xn1x, xn1y, 1.0f);
+        ray2[i] = ref::gemm_small_row(p2.Rcw[i], p2.Rcw[3 + i], p2.Rcw[6 + i], xn2x, xn2y, 1.0f);
     }
-    const float cosParallaxRays = (float)(dot3(ray1, ray2[0], ray2[1], ray2[2]) / (norm3(ray1[0], ray1[1], ray1[2]) * norm3(ray2[0], ray2[1], ray2[2])));
+    const float cosParallaxRays = (float)(ref::dot3(ray1, ray2) / (ref::norm3(ray1) * ref::norm3(ray2)));
     float cosParallaxStereo = cosParallaxRays + 1;
     float cosParallaxStereo1 = cosParallaxStereo, cosParallaxStereo2 = cosParallaxStereo;
     if (bStereo1) cosParallaxStereo1 = a.k1.cos_stereo[o1 + idx1];
@@ -269,15 +271,15 @@ __device__ bool triangulate(const Args& a, const PairLds& pr, const Feat1& f, si
     } else
         return false;   // no stereo and very low parallax
 
-    const float z1 = (float)(dot3(p1.Rcw + 6, x3D[0], x3D[1], x3D[2]) + (double)p1.tcw[2]);
+    const float z1 = (float)(ref::dot3(p1.Rcw + 6, x3D) + (double)p1.tcw[2]);
     if (z1 <= 0) return false;
-    const float z2 = (float)(dot3(p2.Rcw + 6, x3D[0], x3D[1], x3D[2]) + (double)p2.tcw[2]);
+    const float z2 = (float)(ref::dot3(p2.Rcw + 6, x3D) + (double)p2.tcw[2]);
     if (z2 <= 0) return false;
     const float mbf = a.k1.mbf[e1];   // both right-image errors use the CURRENT key frame's mbf (src/LocalMapping.cc:471, :495)
 
     const float sigmaSquare1 = cam.level_sigma2[oct1];
-    const float x1 = (float)(dot3(p1.Rcw, x3D[0], x3D[1], x3D[2]) + (double)p1.tcw[0]);
-    const float y1 = (float)(dot3(p1.Rcw + 3, x3D[0], x3D[1], x3D[2]) + (double)p1.tcw[1]);
+    const float x1 = (float)(ref::dot3(p1.Rcw, x3D) + (double)p1.tcw[0]);
+    const float y1 = (float)(ref::dot3(p1.Rcw + 3, x3D) + (double)p1.tcw[1]);
     const float invz1 = (float)(1.0 / (double)z1);
     {
         const float u1 = cam.fx * x1 * invz1 + cam.cx, v1 = cam.fy * y1 * invz1 + cam.cy;
@@ -291,8 +293,8 @@ __device__ bool triangulate(const Args& a, const PairLds& pr, const Feat1& f, si
         }
     }
     const float sigmaSquare2 = cam.level_sigma2[oct2];
-    const float x2 = (float)(dot3(p2.Rcw, x3D[0], x3D[1], x3D[2]) + (double)p2.tcw[0]);
-    const float y2 = (float)(dot3(p2.Rcw + 3, x3D[0], x3D[1], x3D[2]) + (double)p2.tcw[1]);
+    const float x2 = (float)(ref::dot3(p2.Rcw, x3D) + (double)p2.tcw[0]);
+    const float y2 = (float)(ref::dot3(p2.Rcw + 3, x3D) + (double)p2.tcw[1]);
     const float invz2 = (float)(1.0 / (double)z2);
     {
         const float u2 = cam.fx * x2 * invz2 + cam.cx, v2 = cam.fy * y2 * invz2 + cam.cy;
@@ -305,8 +307,8 @@ __device__ bool triangulate(const Args& a, const PairLds& pr, const Feat1& f, si
             if ((double)(errX2 * errX2 + errY2 * errY2 + errX2_r * errX2_r) > 7.8 * (double)sigmaSquare2) return false;
         }
     }
-    const float dist1 = (float)norm3(x3D[0] - p1.Ow[0], x3D[1] - p1.Ow[1], x3D[2] - p1.Ow[2]);
-    const float dist2 = (float)norm3(x3D[0] - p2.Ow[0], x3D[1] - p2.Ow[1], x3D[2] - p2.Ow[2]);
+    const float dist1 = (float)ref::norm3(x3D[0] - p1.Ow[0], x3D[1] - p1.Ow[1], x3D[2] - p1.Ow[2]);
+    const float dist2 = (float)ref::norm3(x3D[0] - p2.Ow[0], x3D[1] - p2.Ow[1], x3D[2] - p2.Ow[2]);
     if (dist1 == 0 || dist2 == 0) return false;
     const float ratioFactor = 1.5f * cam.scale_factor;
     const float ratioDist = dist2 / dist1;
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(NT) void tri_kernel(const Args a) {
     __shared__ Lds s;
     const int e1 = blockIdx.y, tid = threadIdx.x;
     const int idx1 = blockIdx.x * NT + tid;
-    const int n1 = clamp_n(a.k1.n[e1], a.k1.stride);
+    const int n1 = ref::clamp_n(a.k1.n[e1], a.k1.stride);
     const size_t o1 = (size_t)e1 * a.k1.stride;
     const float* T1 = a.k1.Tcw + (size_t)e1 * 16;
     if ((int)blockIdx.x * NT >= n1) return;   // uniform over the workgroup: none of its idx1 exists
@@ -342,21 +344,21 @@ __global__ __launch_bounds__(NT) void tri_kernel(const Args a) {
     }
     int acc_k = -1, acc_idx2 = -1;
     float acc_x[3] = {0, 0, 0};
-    if (tid == 0) load_pose(T1, s.pr.p1);
+    if (tid == 0) ref::load_pose_keyframe(T1, s.pr.p1);
 
     for (int k = 0; k < nn; k++) {
         const int e2 = CREATE ? e1 * a.max_neigh + k : e1;
         const size_t o2 = (size_t)e2 * a.k2.stride;
         const float* T2 = a.k2.Tcw + (size_t)e2 * 16;
-        const int n2 = clamp_n(a.k2.n[e2], a.k2.stride);
+        const int n2 = ref::clamp_n(a.k2.n[e2], a.k2.stride);
         __syncthreads();   // the previous neighbour's LDS is no longer read
         if (tid == 0) {
-            load_pose(T2, s.pr.p2);
+            ref::load_pose_keyframe(T2, s.pr.p2);
             s.pr.n2 = n2;
             s.pr.skip = 0;
             if (CREATE) {   // the baseline test (:347-353): cv::norm accumulates in double
                 const Pose &p1 = s.pr.p1, &p2 = s.pr.p2;
-                const float baseline = (float)norm3(p2.Ow[0] - p1.Ow[0], p2.Ow[1] - p1.Ow[1], p2.Ow[2] - p1.Ow[2]);
+                const float baseline = (float)ref::norm3(p2.Ow[0] - p1.Ow[0], p2.Ow[1] - p1.Ow[1], p2.Ow[2] - p1.Ow[2]);
                 if (baseline < a.k2.mb[e2]) s.pr.skip = 1;
             }
             if (!s.pr.skip) compute_pair(a.cam, s.pr);
@@ -384,7 +386,7 @@ __global__ __launch_bounds__(NT) void tri_kernel(const Args a) {
 __global__ __launch_bounds__(NT) void tri_compact_kernel(const Args a) {
     __shared__ int wsum[NT / 64];
     const int e1 = blockIdx.x, tid = threadIdx.x;
-    const int n1 = clamp_n(a.k1.n[e1], a.k1.stride);
+    const int n1 = ref::clamp_n(a.k1.n[e1], a.k1.stride);
     const size_t o1 = (size_t)e1 * a.k1.stride;
     int nn = a.n_neigh[e1];
     nn = nn < 0 ? 0 : (nn > a.max_neigh ? a.max_neigh : nn);
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(NT) void tri_compact_kernel(const Args a) {
             const int idx1 = base + tid;
             const bool flag = idx1 < n1 && a.acc_k[o1 + idx1] == k;
             int total;
-            const int r = block_rank(flag, wsum, &total);
+            const int r = ref::block_rank<NT / 64>(flag, wsum, &total);
             if (flag) {   // out + r < n1 <= stride: every idx1 is accepted at most once
                 const size_t j = o1 + out + r;
                 a.new_neigh[j] = k; a.new_idx1[j] = idx1; a.new_idx2[j] = a.acc_idx2[o1 + idx1];
@@ -405,35 +407,17 @@ __global__ __launch_bounds__(NT) void tri_compact_kernel(const Args a) {
     if (tid == 0) a.n_new[e1] = out;
 }
 
-// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1666-1708) on bin counts
-__device__ inline void three_maxima(const int* h, int& ind1, int& ind2, int& ind3) {
-    int max1 = 0, max2 = 0, max3 = 0;
-    ind1 = ind2 = ind3 = -1;
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-        const int sz = h[i];
-        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-        else if (sz > max3) { max3 = sz; ind3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-}
-
 // one workgroup per pair: the rotation histogram of the matches (:768-778), the removal of all but its three maxima (:795-814), nmatches
 __global__ __launch_bounds__(NT) void tri_orient_kernel(const Args a) {
     __shared__ int hist[HISTO_LENGTH], keep[3], count;
     const int e = blockIdx.x, tid = threadIdx.x;
-    const int n1 = clamp_n(a.k1.n[e], a.k1.stride), n2 = clamp_n(a.k2.n[e], a.k2.stride);
+    const int n1 = ref::clamp_n(a.k1.n[e], a.k1.stride), n2 = ref::clamp_n(a.k2.n[e], a.k2.stride);
     const size_t o1 = (size_t)e * a.k1.stride, o2 = (size_t)e * a.k2.stride;
     if (tid < HISTO_LENGTH) hist[tid] = 0;
     if (tid == 0) count = 0;
     __syncthreads();
     auto bin_of = [&](int idx1, int idx2) {
-        const float factor = 1.0f / HISTO_LENGTH;
-        float rot = a.k1.keys_un[o1 + idx1].angle - a.k2.keys_un[o2 + idx2].angle;
-        if (rot < 0.0f) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == HISTO_LENGTH) bin = 0;
+        const int bin = ref::rot_bin(a.k1.keys_un[o1 + idx1].angle, a.k2.keys_un[o2 + idx2].angle);
         return bin < 0 ? 0 : (bin >= HISTO_LENGTH ? HISTO_LENGTH - 1 : bin);   // the reference asserts the range
     };
     if (a.check_orientation)
@@ -442,7 +426,7 @@ __global__ __launch_bounds__(NT) void tri_orient_kernel(const Args a) {
             if (m >= 0 && m < n2) atomicAdd(&hist[bin_of(idx1, m)], 1);
         }
     __syncthreads();
-    if (tid == 0) { int i1, i2, i3; three_maxima(hist, i1, i2, i3); keep[0] = i1; keep[1] = i2; keep[2] = i3; }
+    if (tid == 0) { int i1, i2, i3; ref::three_maxima(hist, i1, i2, i3); keep[0] = i1; keep[1] = i2; keep[2] = i3; }
     __syncthreads();
     int mine = 0;
     for (int idx1 = tid; idx1 < n1; idx1 += NT) {
