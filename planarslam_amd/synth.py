@@ -578,14 +578,15 @@ def guided_fuse_points(frame, seed=15, n_points=2500, hit=0.6, bits=60, pix_nois
     return frame, mp
 
 
-def guided_fuse_lines(B=3, n_lines=60, n_ml=300, seed=17, hit=0.6, bits=60):
+def guided_fuse_lines(B=3, n_lines=60, n_ml=300, seed=17, hit=0.6, bits=60, cam=None):
     """Key frames with key lines + map lines to fuse into them (LSDmatcher::Fuse): `hit` of the map lines are back-projections of a key line's end
     points (descriptor with up to `bits` flipped, predicted level at or one above the key line's octave), the rest random segments around the
-    camera (behind it, outside the image, out of range, oblique).  Returns (kf dict: Tcw + intrinsics + scale factors, lines dict, ml dict)."""
+    camera (behind it, outside the image, out of range, oblique).  cam: fx, fy, cx, cy, bf and optionally the image bounds min_x .. max_y (default TUM3,
+    the whole image).  Returns (kf dict: Tcw + intrinsics + scale factors, lines dict, ml dict)."""
     from ._lib import KEYLINE_DTYPE
     rng = np.random.default_rng(seed)
-    K = TUM3
-    kf = dict(B=B, Tcw=np.zeros((B, 16), np.float32), min_x=0.0, max_x=640.0, min_y=0.0, max_y=480.0, fx=K["fx"], fy=K["fy"], cx=K["cx"], cy=K["cy"], bf=K["bf"],
+    K = cam or TUM3
+    kf = dict(B=B, Tcw=np.zeros((B, 16), np.float32), min_x=K.get("min_x", 0.0), max_x=K.get("max_x", 640.0), min_y=K.get("min_y", 0.0), max_y=K.get("max_y", 480.0), fx=K["fx"], fy=K["fy"], cx=K["cx"], cy=K["cy"], bf=K["bf"],
               b=K["bf"] / K["fx"], scale_factors=scale_factors())
     kl = np.zeros((B, n_lines), KEYLINE_DTYPE)
     lines = dict(n=np.zeros(B, np.int32), keylines=kl, ldesc=rng.integers(0, 256, (B, n_lines, 32), dtype=np.uint8))

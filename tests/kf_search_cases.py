@@ -6,9 +6,11 @@ import numpy as np
 from planarslam_amd import synth
 
 
-def kf_case(B=4, N=1000, stride=None, seed=1, dup=0.3, crowd=0.3, found=0.1, blocked=0.1, bits=30):
+def kf_case(B=4, N=1000, stride=None, seed=1, dup=0.3, crowd=0.3, found=0.1, blocked=0.1, bits=30, frame=None):
+    """frame: a current frame to build on (its B and stride hold) instead of synth.guided_frame(B, N, stride, seed, crowd)"""
     rng = np.random.default_rng(seed + 1000)
-    fr = synth.guided_frame(B=B, N=N, stride=stride, seed=seed, crowd=crowd)
+    fr = synth.guided_frame(B=B, N=N, stride=stride, seed=seed, crowd=crowd) if frame is None else frame
+    B = fr["keys_un"].shape[0]
     cur, last = synth.guided_last_frame(fr, seed=seed + 1, dup=dup, bits=bits)
     S = last["usable"].shape[1]
     cur["blocked"] = (rng.random(cur["blocked"].shape) < blocked).astype(np.uint8)
@@ -40,6 +42,24 @@ CASES = [
     ("small_padded", dict(B=3, N=12, stride=40, seed=305), 10.0, 100, True),
     ("strict_dist", dict(B=2, N=1000, seed=306, bits=50), 3.0, 40, True),
 ]
+
+
+def load_host():
+    """tests/host_shim/kf_search_host.cpp (the restatement of the key-frame search, g++ -ffp-contract=off) as a ctypes library, built when it is out of date"""
+    import ctypes
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    so = os.path.join(root, "tests", "host_shim", "libkf_search_host.so")
+    src = os.path.join(root, "tests", "host_shim", "kf_search_host.cpp")
+    deps = [src, os.path.join(root, "include", "planar_abi.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-o", so, src])
+    L = ctypes.CDLL(so)
+    L.kf_search_host.restype = ctypes.c_int
+    L.kf_search_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_void_p]
+    return L
 
 
 def log_scale_factor(frame):

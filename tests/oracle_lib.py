@@ -514,14 +514,14 @@ def fuse_search(kf, mp, th, log_scale_factor, n_levels, shared=False, inv_level_
     return idx, dist, nf
 
 
-def ref_fuse(kf, mp, b, th, log_scale_factor, n_levels, shared=False, kf_state=None, kf_obs=None):
+def ref_fuse(kf, mp, b, th, log_scale_factor, n_levels, shared=False, kf_state=None, kf_obs=None, inv_level_sigma2=None):
     """One key frame through the REAL ORBmatcher::Fuse (oracle/_ref/ref_match, mode fuse).  Returns (fuse_idx [n], nFused)."""
     pb = 0 if shared else b
     npb = int(mp["n"][pb]); nk = int(kf["n"][b])
     state = np.zeros(nk, np.uint8) if kf_state is None else np.asarray(kf_state, np.uint8)[:nk]
     kobs = np.zeros(nk, np.int32) if kf_obs is None else np.asarray(kf_obs, np.int32)[:nk]
     blocks = [np.array([th, log_scale_factor, float(n_levels)], np.float32)] + _frame_blocks(kf, b) + [
-        _inv_sigma2(kf, n_levels), np.asarray(kf["Tcw"][b], np.float32), mp["usable"][pb, :npb].astype(np.uint8), mp["xw"][pb, :npb].astype(np.float32),
+        _inv_sigma2(kf, n_levels) if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)[:n_levels], np.asarray(kf["Tcw"][b], np.float32), mp["usable"][pb, :npb].astype(np.uint8), mp["xw"][pb, :npb].astype(np.float32),
         mp["normal"][pb, :npb].astype(np.float32), mp["min_dist"][pb, :npb].astype(np.float32), mp["max_dist"][pb, :npb].astype(np.float32), mp["desc"][pb, :npb],
         state, kobs, np.asarray(mp.get("observations", np.ones_like(mp["usable"], dtype=np.int32))[pb, :npb], np.int32)]
     idx, nf = _run_ref_match("fuse", blocks, 2)

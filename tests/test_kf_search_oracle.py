@@ -3,7 +3,6 @@ built with g++ -ffp-contract=off) against tests/golden/kf_proj_ref.npz, which to
 src/ORBmatcher.cc:1537-1663.  The GPU kernel is compared with both in tests/test_kf_search_gpu.py."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,21 +10,12 @@ import pytest
 import kf_search_cases as KC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "tests", "host_shim", "libkf_search_host.so")
 GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "kf_proj_ref.npz"))
 
 
 @pytest.fixture(scope="module")
 def host():
-    src = os.path.join(ROOT, "tests", "host_shim", "kf_search_host.cpp")
-    deps = [src, os.path.join(ROOT, "include", "planar_abi.h")]
-    if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-o", SO, src])
-    L = ctypes.CDLL(SO)
-    L.kf_search_host.restype = ctypes.c_int
-    L.kf_search_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                 ctypes.c_void_p]
-    return L
+    return KC.load_host()
 
 
 def host_search(L, cur, kf, th, orb, ori, match=None):

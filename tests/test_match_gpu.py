@@ -68,3 +68,89 @@ def test_lsd_search_by_descriptor():
     for b in range(B):
         om, on = ol.lsd_search_by_descriptor(kf[b][:n_kf[b]], cur[b][:n_cur[b]], has[b])
         assert nm[b] == on and np.array_equal(m[b, :n_cur[b]], om)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_hamming_knn_missing_neighbours_and_full_blocks(k):
+    """include/planar_abi.h: a missing neighbour is idx -1 / dist INT32_MAX.  Train sets of 0 and 1 rows at k = 2, an empty query set, and query counts that
+    fill their workgroups of 256 exactly."""
+    from planarslam_amd import hamming_knn
+    rng = np.random.default_rng(3)
+    B, qs, ts = 6, 512, 300
+    nq = np.array([256, 512, 0, 300, 256, 512], np.int32)
+    nt = np.array([0, 1, 300, 1, 300, 257], np.int32)
+    t = np.stack([_descs(rng, ts) for _ in range(B)])
+    q = np.stack([_descs(rng, qs, t[b], 40) for b in range(B)])
+    idx, dist = hamming_knn(q, nq, t, nt, k)
+    for b in range(B):
+        oi, od = ol.bf_knn(q[b][:nq[b]], t[b][:nt[b]], k)
+        np.testing.assert_array_equal(idx[b, :nq[b]], oi); np.testing.assert_array_equal(dist[b, :nq[b]], od)
+    imax = np.iinfo(np.int32).max
+    assert (idx[0, :256] == -1).all() and (dist[0, :256] == imax).all()
+    assert (idx[1, :512, 0] == 0).all() and (dist[1, :512, 0] < 256).all()
+    if k == 2:
+        assert (idx[1, :512, 1] == -1).all() and (dist[1, :512, 1] == imax).all()
+        assert (idx[3, :300, 1] == -1).all() and (dist[3, :300, 1] == imax).all()
+
+
+def test_lsd_search_by_descriptor_duplicate_rows():
+    """Duplicate current descriptors: the second distance equals the first, so the ratio is 1, or 0 / 0 (NaN) where a key-frame row is an exact copy, and neither is
+    below 1 / 1.5 (d / 0 cannot occur: the neighbours come sorted, so a zero second distance has a zero first)"""
+    from planarslam_amd import LSDmatcher
+    rng = np.random.default_rng(4)
+    B, ks, cs = 4, 24, 30
+    n_kf = np.array([24, 24, 10, 24], np.int32)
+    n_cur = np.array([30, 30, 2, 30], np.int32)
+    cur = np.stack([_descs(rng, cs) for _ in range(B)])
+    cur[0, 1::2] = cur[0, 0::2]                                   # every current row twice
+    cur[1, 15:] = cur[1, :15]
+    cur[2, 1] = cur[2, 0]
+    cur[3, 10:20] = cur[3, :10]                                   # a third of the rows twice, the others once
+    kf = np.stack([_descs(rng, ks, cur[b][:n_cur[b]], 30) for b in range(B)])
+    kf[0, :8] = cur[0, :16:2]                                     # exact copies of duplicated rows: 0 / 0
+    kf[1, 20:] = cur[1, 3:7]
+    kf[3, :4] = cur[3, 8:12]
+    has = np.ones((B, ks), np.uint8)
+    m, nm = LSDmatcher().SearchByDescriptor(kf, n_kf, cur, n_cur, has)
+    zero_over_zero = 0
+    for b in range(B):
+        _, od = ol.bf_knn(kf[b][:n_kf[b]], cur[b][:n_cur[b]], 2)
+        zero_over_zero += int(((od[:, 0] == 0) & (od[:, 1] == 0)).sum())
+        om, on = ol.lsd_search_by_descriptor(kf[b][:n_kf[b]], cur[b][:n_cur[b]], has[b])
+        assert nm[b] == on
+        np.testing.assert_array_equal(m[b, :n_cur[b]], om)
+    assert zero_over_zero >= 12 and (nm[:3] == 0).all() and nm[3] > 0
+
+
+def test_match_orb_points_threshold_and_rank():
+    """A distance exactly at max(2 * min_dist, 15) is no good match (`<`), with min_dist 0 (threshold 15) and 10 (threshold 20); and more good matches
+    than the last frame has key points, so that the outlier flag indexed by the good-match counter (src/ORBmatcher.cc:1385) is asked beyond n_last."""
+    from planarslam_amd import ORBmatcher
+
+    def flips(d, k, start=0):
+        bits = np.unpackbits(d); bits[start:start + k] ^= 1
+        return np.packbits(bits)
+    rng = np.random.default_rng(5)
+    B, cs, ls = 3, 300, 40
+    n_cur = np.array([40, 40, 300], np.int32)
+    n_last = np.array([40, 40, 5], np.int32)
+    last = np.stack([_descs(rng, ls) for _ in range(B)])
+    cur = np.stack([_descs(rng, cs) for _ in range(B)])
+    dist = np.full((B, cs), -1)
+    for i in range(40):                                           # min 0: 14 / 15 / 16 straddle the threshold 15
+        dist[0, i] = [0, 14, 15, 16][i % 4]; cur[0, i] = flips(last[0, i], dist[0, i])
+        dist[1, i] = [10, 19, 20, 21][i % 4]; cur[1, i] = flips(last[1, i], dist[1, i])          # min 10: threshold 20
+    for i in range(300):                                          # every current key point is a good match of one of 5 last key points
+        cur[2, i] = flips(last[2, i % 5], i % 3, start=8 * (i % 20))
+    has = np.ones((B, ls), np.uint8); has[:, 3::7] = 0
+    outl = np.zeros((B, ls), np.uint8); outl[:, 1::3] = 1; outl[2, 5:] = 1           # beyond n_last: must never be read as a flag
+    init = np.full((B, cs), -1, np.int32); init[:, ::9] = 4321
+    m, npair = ORBmatcher().MatchORBPoints(cur, n_cur, last, n_last, has, outl, init)
+    for b in range(B):
+        om, on = ol.match_orb_points(cur[b][:n_cur[b]], last[b][:n_last[b]], has[b], outl[b], init[b][:n_cur[b]])
+        assert npair[b] == on
+        np.testing.assert_array_equal(m[b, :n_cur[b]], om)
+        np.testing.assert_array_equal(m[b, n_cur[b]:], init[b, n_cur[b]:])
+    assert npair[0] == 20 and npair[1] == 20 and npair[2] == 300          # 0 and 14 (10 and 19) pass, the distance on the threshold does not
+    took = m[2, :300] != init[2, :300]
+    assert took[5:].sum() > 100                                   # ranks >= n_last do assign

@@ -30,11 +30,11 @@ def build(tmp):
     return exe
 
 
-def run_pair(exe, tmp, cur, kf, b, th, orb, ori):
+def run_pair(exe, tmp, cur, kf, b, th, orb, ori, lsf=None):
     fv, _ = guided.frame_view(cur)
     n, np_ = int(cur["n"][b]), int(kf["n"][b])
     intr = np.array([fv.min_x, fv.max_x, fv.min_y, fv.max_y, fv.grid_w_inv, fv.grid_h_inv, fv.fx, fv.fy, fv.cx, fv.cy], np.float32)
-    blocks = [np.array([th, orb, float(ori), KC.log_scale_factor(cur), len(cur["scale_factors"])], np.float32),
+    blocks = [np.array([th, orb, float(ori), KC.log_scale_factor(cur) if lsf is None else lsf, len(cur["scale_factors"])], np.float32),
               np.ascontiguousarray(cur["keys_un"][b, :n]), cur["desc"][b, :n], cur["blocked"][b, :n].astype(np.uint8), intr,
               np.asarray(cur["scale_factors"], np.float32), np.asarray(cur["Tcw"][b], np.float32),
               kf["usable"][b, :np_].astype(np.uint8), kf["found"][b, :np_].astype(np.uint8), kf["xw"][b, :np_].astype(np.float32),
