@@ -736,6 +736,52 @@ int planar_bow_transform(planar_vocab* voc, const uint8_t* desc, const int32_t* 
 int planar_bow_transform_dev(planar_vocab* voc, const uint8_t* d_desc, const int32_t* d_n, int B, int stride, int levelsup, int32_t* d_word,
                              double* d_weight, int32_t* d_node, int32_t* d_bow_word, double* d_bow_value, int32_t* d_bow_n);
 
+/* ---- key-frame database: BoW scores, relocalisation and loop candidates (replaces KeyFrameDatabase::DetectRelocalizationCandidates(Frame*),
+ *      src/KeyFrameDatabase.cc:199-309, as src/Tracking.cc:2561 calls it, KeyFrameDatabase::DetectLoopCandidates(KeyFrame*, float minScore), :76-197, as
+ *      src/LoopClosing.cc:141 calls it, and ORBVocabulary::score = L1Scoring::score, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68, src/LoopClosing.cc:134) ----
+ * A database is the key frames that KeyFrameDatabase::add() was called with, one per slot; the inverted file is not stored: the order of a word's list is the
+ * order of the add() calls (add_seq) among the key frames still present.  Limits (PLANAR_EINVAL beyond them): */
+#define PLANAR_KFDB_MAX_WORDS 4096     /* word_stride, q_word_stride: words of one BowVector, the feature limit of the key-frame views (PLANAR_MAX_FRAME_KEYS) */
+#define PLANAR_KFDB_MAX_KEYFRAMES 1024 /* kf_stride: slots of one database                                                                                    */
+typedef struct planar_kf_database {          /* G databases, padded like every other view */
+    int32_t kf_stride, word_stride;
+    const int32_t* n_kf;        /* [G]                          slots in use                                         */
+    const uint8_t* present;     /* [G][kf_stride]               in the inverted file (add()ed, not erase()d)         */
+    const int32_t* add_seq;     /* [G][kf_stride]               order of KeyFrameDatabase::add, unique per database  */
+    const int32_t* bow_n;       /* [G][kf_stride]                                                                    */
+    const int32_t* bow_word;    /* [G][kf_stride][word_stride]  mBowVec keys, ascending                              */
+    const double*  bow_value;   /* [G][kf_stride][word_stride]  must start on an 8-byte boundary                     */
+    const int32_t* covis;       /* [G][kf_stride][10]  GetBestCovisibilityKeyFrames(10) as slot indices, -1 = none / not in this database */
+} planar_kf_database;
+/* mode 0: DetectRelocalizationCandidates, mode 1: DetectLoopCandidates, for B queries.  `db` is a HOST pointer in both flavours (its arrays are device arrays
+ * in the _dev one).  Query b runs against database q_db[b] (several queries may share one; the host flavour stages databases 0 .. max(q_db)); its BowVector is
+ * q_bow_word / q_bow_value [B][q_word_stride] + q_bow_n [B], the layout planar_bow_transform_dev writes, so that call's output feeds this one without a copy.
+ *   excluded [B][kf_stride]   spConnectedKeyFrames.count(pKFi)      min_score [B]   the minScore argument       (loop mode only; may be NULL in mode 0)
+ *   score [B][kf_stride]  in/out: on entry what mRelocScore / mLoopScore held, on exit overwritten exactly where the reference assigns it (the key frames it
+ *       scores: more common words than minCommonWords).  In reloc mode a covisible neighbour that shares a word but is not scored contributes its STALE
+ *       mRelocScore, a member the reference never initialises: here that value is the caller's input (the adapter starts it at 0).
+ *   common_words [B][kf_stride]  mnRelocWords / mnLoopWords of the key frames that enter lKFsSharingWords, 0 for every other slot of the row
+ *   cand [B][kf_stride], n_cand [B]  the returned vector as slot indices, in its order; nothing is written beyond n_cand[b]
+ *   n_scored [B]  nscores (0 when no key frame shares a word)
+ * Kept as the reference has it: lKFsSharingWords in first-encounter order (ascending smallest common word, then add_seq); minCommonWords =
+ * (int)(maxCommonWords * 0.8f) and `>`; si = (float)score, accScore a float sum in neighbour order, bestScore on `>`; minScoreToRetain = 0.75f * bestAccScore and
+ * `>`, bestAccScore from 0 (reloc) or minScore (loop); loop mode: si < minScore is not listed but counts as a neighbour, an excluded key frame is neither;
+ * candidates deduplicated on pBestKF, first occurrence.  Left out: a query whose mnId is 0 meeting key frames whose constructor set mnRelocQuery / mnLoopQuery to 0
+ * (they would count as already seen); query ids are taken as unique.  B * kf_stride must stay below 2^31. */
+int planar_kfdb_detect(planar_ctx* ctx, int mode, const planar_kf_database* db, int B, const int32_t* q_db, const int32_t* q_bow_n, const int32_t* q_bow_word,
+                       const double* q_bow_value, int q_word_stride, const uint8_t* excluded, const float* min_score, float* score, int32_t* common_words,
+                       int32_t* n_cand, int32_t* cand, int32_t* n_scored);
+int planar_kfdb_detect_dev(planar_ctx* ctx, int mode, const planar_kf_database* db, int B, const int32_t* d_q_db, const int32_t* d_q_bow_n,
+                           const int32_t* d_q_bow_word, const double* d_q_bow_value, int q_word_stride, const uint8_t* d_excluded, const float* d_min_score,
+                           float* d_score, int32_t* d_common_words, int32_t* d_n_cand, int32_t* d_cand, int32_t* d_n_scored);
+/* L1Scoring::score(a, b) for P pairs of BowVectors ([P][a_stride] / [P][b_stride], strides up to PLANAR_KFDB_MAX_WORDS): the terms fabs(vi - wi) - fabs(vi) -
+ * fabs(wi) of the common words added in ascending word id as one FP64 chain, then -score / 2.0 (-0.0 without a common word).  out [P] is the double; the
+ * caller narrows it to float and takes its minimum as src/LoopClosing.cc:134 does. */
+int planar_bow_score(planar_ctx* ctx, int P, const int32_t* a_bow_n, const int32_t* a_bow_word, const double* a_bow_value, int a_stride, const int32_t* b_bow_n,
+                     const int32_t* b_bow_word, const double* b_bow_value, int b_stride, double* out);
+int planar_bow_score_dev(planar_ctx* ctx, int P, const int32_t* d_a_bow_n, const int32_t* d_a_bow_word, const double* d_a_bow_value, int a_stride,
+                         const int32_t* d_b_bow_n, const int32_t* d_b_bow_word, const double* d_b_bow_value, int b_stride, double* d_out);
+
 /* ---- 3-D line back-projection (replaces Frame::isLineGood, src/Frame.cc:189-267, with compPt3dCov / extract3dline_mahdist / verify3dLine /
  *      mah_dist3d_pt_line / computeLine3d_svd of src/LineExtractor.cpp:1157-1470) ----
  * keylines [B][ln_stride] = Frame::mvKeylinesUn, depth = the u16 depth image (imDepth = value * depth_factor), fx.. = Frame::fx.. (K(0,0) of compPt3dCov is fx).

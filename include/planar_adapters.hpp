@@ -7,6 +7,7 @@
 //   Planar_SLAM::LineSegment    <- include/LSDextractor.h:344-352, src/LSDextractor.cpp               (PLANAR_ADAPTERS_WITH_LINES)
 //   ORBmatcher::Fuse / LSDmatcher::Fuse (search on the device, map edits as in the reference)         (PLANAR_ADAPTERS_WITH_FUSE, needs one accessor, see there)
 //   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
+//   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1025,6 +1026,119 @@ inline int LSDmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, st
 }  // namespace Planar_SLAM
 #endif
 #endif   // PLANAR_ADAPTERS_WITH_NEW_LINES
+
+// ---- KeyFrameDatabase (include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc): add / erase / clear / DetectLoopCandidates / DetectRelocalizationCandidates with
+//      the reference's signatures.  Enabled with PLANAR_ADAPTERS_WITH_KFDB, after the reference's KeyFrame.h, Frame.h and ORBVocabulary.h.  The class keeps a HOST
+//      mirror (no device resource): one slot per key frame ever added, with a copy of its mBowVec, whether it is in the inverted file, the order of its add() and the
+//      two score members (mRelocScore / mLoopScore live HERE and start at 0: the reference never initialises them).  A query packs the mirror, asks every present
+//      key frame for GetBestCovisibilityKeyFrames(10), calls planar_kfdb_detect (the host flavour) and maps the slots back to pointers.  Of a key frame
+//      mBowVec (begin / end, ->first, ->second), GetBestCovisibilityKeyFrames and, of the query, mBowVec and GetConnectedKeyFrames are read; the members
+//      mnRelocQuery / mnRelocWords / mnLoopQuery / mnLoopWords of the key frames are NOT written (nothing else in the reference reads them).  A failing call, more
+//      than PLANAR_KFDB_MAX_KEYFRAMES slots or a BowVector of more than PLANAR_KFDB_MAX_WORDS words gives an empty vector.  add() of a key frame that is already in
+//      the database (the reference would list it twice) is ignored.
+#ifdef PLANAR_ADAPTERS_WITH_KFDB
+#include <list>
+#include <set>
+namespace planar_adapter {
+
+template <class KeyFrameT, class FrameT, class VocabularyT>
+class KeyFrameDatabaseT {
+public:
+    explicit KeyFrameDatabaseT(const VocabularyT&) {}    // the vocabulary is not read: the score is L1Scoring's, ORBvoc.txt's configuration
+    void add(KeyFrameT* pKF) {
+        std::lock_guard<std::mutex> g(mMutex);
+        auto it = slot_of_.find(pKF);
+        if (it == slot_of_.end()) { it = slot_of_.insert(std::make_pair(pKF, (int)slots_.size())).first; slots_.push_back(Slot()); slots_.back().kf = pKF; }
+        Slot& s = slots_[it->second];
+        if (s.present) return;
+        s.words.clear(); s.values.clear();
+        for (auto vit = pKF->mBowVec.begin(), vend = pKF->mBowVec.end(); vit != vend; ++vit) { s.words.push_back((int32_t)vit->first); s.values.push_back((double)vit->second); }
+        s.present = 1; s.add_seq = next_seq_++;
+    }
+    void erase(KeyFrameT* pKF) {
+        std::lock_guard<std::mutex> g(mMutex);
+        auto it = slot_of_.find(pKF);
+        if (it != slot_of_.end()) slots_[it->second].present = 0;
+    }
+    void clear() {
+        std::lock_guard<std::mutex> g(mMutex);
+        slots_.clear(); slot_of_.clear(); next_seq_ = 0;
+    }
+    std::vector<KeyFrameT*> DetectLoopCandidates(KeyFrameT* pKF, float minScore) {
+        std::set<KeyFrameT*> connected = pKF->GetConnectedKeyFrames();
+        return detect(1, pKF->mBowVec, &connected, minScore);
+    }
+    std::vector<KeyFrameT*> DetectRelocalizationCandidates(FrameT* F) { return detect(0, F->mBowVec, (const std::set<KeyFrameT*>*)NULL, 0.f); }
+
+protected:
+    struct Slot {
+        KeyFrameT* kf = NULL;
+        uint8_t present = 0;
+        int32_t add_seq = 0;
+        std::vector<int32_t> words;
+        std::vector<double> values;
+        float score[2] = {0.f, 0.f};     // mRelocScore, mLoopScore
+    };
+    template <class BowT>
+    std::vector<KeyFrameT*> detect(int mode, const BowT& bow, const std::set<KeyFrameT*>* connected, float minScore) {
+        std::vector<KeyFrameT*> out;
+        std::lock_guard<std::mutex> g(mMutex);
+        const size_t n = slots_.size();
+        if (n == 0) return out;
+        std::vector<int32_t> qw;
+        std::vector<double> qv;
+        for (auto vit = bow.begin(), vend = bow.end(); vit != vend; ++vit) { qw.push_back((int32_t)vit->first); qv.push_back((double)vit->second); }
+        size_t W = 1;
+        for (const Slot& s : slots_) if (s.present && s.words.size() > W) W = s.words.size();
+        if (n > PLANAR_KFDB_MAX_KEYFRAMES || W > PLANAR_KFDB_MAX_WORDS || qw.size() > PLANAR_KFDB_MAX_WORDS) {
+            std::fprintf(stderr, "planar (KeyFrameDatabase): more than %d key frames or %d words - degraded to \"nothing found\"\n", PLANAR_KFDB_MAX_KEYFRAMES, PLANAR_KFDB_MAX_WORDS);
+            return out;
+        }
+        const size_t QW = qw.size() ? qw.size() : 1;
+        qw.resize(QW, 0); qv.resize(QW, 0.0);
+        std::vector<uint8_t> present(n), excluded(n, 0);
+        std::vector<int32_t> add_seq(n), bow_n(n, 0), bow_word(n * W, 0), covis(n * 10, -1), common(n, 0), cand(n, -1);
+        std::vector<double> bow_value(n * W, 0.0);
+        std::vector<float> score(n);
+        for (size_t j = 0; j < n; j++) {
+            const Slot& s = slots_[j];
+            present[j] = s.present; add_seq[j] = s.add_seq; score[j] = s.score[mode];
+            if (!s.present) continue;
+            bow_n[j] = (int32_t)s.words.size();
+            std::copy(s.words.begin(), s.words.end(), bow_word.begin() + j * W);
+            std::copy(s.values.begin(), s.values.end(), bow_value.begin() + j * W);
+            const std::vector<KeyFrameT*> neigh = s.kf->GetBestCovisibilityKeyFrames(10);
+            for (size_t t = 0; t < neigh.size() && t < 10; t++) { const auto it = slot_of_.find(neigh[t]); if (it != slot_of_.end()) covis[j * 10 + t] = it->second; }
+            if (connected && connected->count(s.kf)) excluded[j] = 1;
+        }
+        planar_kf_database db;
+        db.kf_stride = (int32_t)n; db.word_stride = (int32_t)W;
+        const int32_t n_kf = (int32_t)n, q_db = 0, q_n = (int32_t)bow.size();
+        db.n_kf = &n_kf; db.present = present.data(); db.add_seq = add_seq.data(); db.bow_n = bow_n.data(); db.bow_word = bow_word.data(); db.bow_value = bow_value.data();
+        db.covis = covis.data();
+        int32_t n_cand = 0, n_scored = 0;
+        {
+            Runtime::Lane& L = Runtime::get().lane(TRACKING);
+            std::lock_guard<std::mutex> lg(L.mu);
+            if (!ok(planar_kfdb_detect(L.ctx, mode, &db, 1, &q_db, &q_n, qw.data(), qv.data(), (int)QW, mode ? excluded.data() : NULL, mode ? &minScore : NULL, score.data(),
+                                       common.data(), &n_cand, cand.data(), &n_scored), "planar_kfdb_detect")) return out;
+        }
+        for (size_t j = 0; j < n; j++) slots_[j].score[mode] = score[j];
+        out.reserve(n_cand);
+        for (int i = 0; i < n_cand; i++) out.push_back(slots_[cand[i]].kf);
+        return out;
+    }
+    std::vector<Slot> slots_;
+    std::map<KeyFrameT*, int> slot_of_;
+    int32_t next_seq_ = 0;
+    std::mutex mMutex;
+};
+
+}  // namespace planar_adapter
+namespace Planar_SLAM {
+typedef planar_adapter::KeyFrameDatabaseT<KeyFrame, Frame, ORBVocabulary> KeyFrameDatabase;
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_KFDB
 
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.

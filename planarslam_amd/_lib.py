@@ -103,6 +103,14 @@ class TrackMatches(C.Structure):
                 ("pl_match", C.c_void_p), ("mpl_coef", C.c_void_p), ("Tcw", C.c_void_p)]
 
 
+class KfDatabase(C.Structure):
+    _fields_ = [("kf_stride", C.c_int32), ("word_stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n_kf", "present", "add_seq", "bow_n", "bow_word", "bow_value", "covis")]
+
+
+KFDB_MAX_WORDS = 4096        # PLANAR_KFDB_MAX_WORDS
+KFDB_MAX_KEYFRAMES = 1024    # PLANAR_KFDB_MAX_KEYFRAMES
+
+
 class BAResult(C.Structure):
     _fields_ = [("kf_Tcw", C.c_void_p), ("lm", C.c_void_p), ("e_outlier", C.c_void_p), ("lm_iterations", C.c_int32), ("stopped", C.c_int32)]
 
@@ -227,6 +235,10 @@ _SIGS = {
     "planar_vocab_words": (C.c_int, [C.c_void_p]),
     "planar_bow_transform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "planar_bow_transform_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "planar_kfdb_detect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(KfDatabase), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
+    "planar_kfdb_detect_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(KfDatabase), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
+    "planar_bow_score": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
+    "planar_bow_score_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     "planar_is_line_good": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_is_line_good_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_normals_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -54,3 +54,10 @@ class ORBVocabulary:
         check(self.L.planar_bow_transform(self.h, d.ctypes.data, nn.ctypes.data, B, S, levelsup, out["word"].ctypes.data, out["weight"].ctypes.data, out["node"].ctypes.data,
                                           out["bow_word"].ctypes.data, out["bow_value"].ctypes.data, out["bow_n"].ctypes.data))
         return out
+
+    def score(self, v1, v2) -> float:
+        """ORBVocabulary::score(v1, v2) (L1Scoring::score, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) of two BowVectors given as (word ids ascending, values):
+        the double; src/LoopClosing.cc:134 narrows it to float"""
+        from .kfdb import bow_score, pad_bow
+        a, b = pad_bow([v1]), pad_bow([v2])
+        return float(bow_score(self.ctx, *a, *b)[0])
