@@ -554,6 +554,108 @@ int planar_lsd_fuse_search_dev(planar_ctx* ctx, const planar_frame_view* d_kf, f
                                const uint8_t* d_usable, const double* d_xw6, const double* d_normal, const float* d_min_dist, const float* d_max_dist,
                                const uint8_t* d_ml_desc, float th, int32_t* d_fuse_idx, int32_t* d_fuse_dist, int32_t* d_n_fused);
 
+/* ---- the loop thread's matchers (LoopClosing::ComputeSim3, src/LoopClosing.cc:323) ----
+ * pKF->GetMapPointMatches() of the key frame a planar_frame_view describes: entry i belongs to key point i, the arrays have the view's B and stride. */
+typedef struct planar_kf_points {
+    const uint8_t* usable;       /* [B][stride]     vpMapPoints[i] != NULL && !isBad()                                                 */
+    const float* xw;             /* [B][stride][3]  GetWorldPos()                                                                      */
+    const float* min_dist;       /* [B][stride]     mfMinDistance (the 0.8 of GetMinDistanceInvariance is applied here)                 */
+    const float* max_dist;       /* [B][stride]     mfMaxDistance (1.2 of GetMaxDistanceInvariance; PredictScale reads it bare)         */
+    const uint8_t* desc;         /* [B][stride][32] GetDescriptor()                                                                    */
+} planar_kf_points;
+
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1106-1330), batched over B independent key-frame pairs: the
+ * map points of pKF1 are searched in pKF2 under the similarity and those of pKF2 in pKF1, and a pair is stored where both searches agree.
+ *   kf1, kf2: n, keys_un, desc, Tcw (GetRotation() / GetTranslation() are its blocks), bounds, grid and scale_factors are read, u_right and blocked are
+ *       not; fx fy cx cy are taken from kf1 in BOTH directions, as the reference does (:1109-1112).  Both views have the same B.
+ *   log_scale_factor / n_levels 1, 2 = pKF1's and pKF2's mfLogScaleFactor / mnScaleLevels (MapPoint::PredictScale(dist, pKF), src/MapPoint.cc:402-417,
+ *       is called with the key frame searched).
+ *   s12 [B], R12 [B][9] row-major, t12 [B][3].
+ *   match12[b][i1] (in/out, stride of kf1): on entry -1 = vpMatches12[i1] is NULL; a value in [0, n2[b]) = GetIndexInKeyFrame(pKF2) of the point matched
+ *       before, which takes both key point i1 of pKF1 and that key point of pKF2 out of the search; any other value = matched, the point is not in pKF2,
+ *       which takes out i1 only (:1136-1146).  On exit i2 where the reference stores vpMapPoints2[i2]; every other entry keeps its value.
+ *   n_found[b]: the function's return value.
+ * Kept as the reference has them: 1.0 / z is a double division narrowed to float; dist3D is the norm of the CAMERA-frame point; the level gate is
+ * [level - 1, level]; bestDist starts at INT_MAX, the first best in KeyFrame::GetFeaturesInArea order wins, bestDist <= TH_HIGH decides; no ratio test, no
+ * orientation check.  A batch is over independent pairs; each problem has the semantics of one call on the state at entry.
+ * Defined where the reference is not: n[b] is clamped to [0, stride] and n == 0 on either side gives n_found[b] = 0; a predicted level cannot leave
+ * mvScaleFactors because n_levels above PLANAR_MAX_LEVELS is PLANAR_EINVAL, as are a stride above PLANAR_MAX_FRAME_KEYS, views of different B, a null
+ * array and log_scale_factor == 0; s12 == 0 gives infinite or NaN coordinates, which fail the image gate (the reference does the same).
+ * The _dev flavour keeps vnMatch1 / vnMatch2 in the context's scratch block. */
+int planar_search_by_sim3(planar_ctx* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, float log_scale_factor1, int n_levels1,
+                          const planar_frame_view* kf2, const planar_kf_points* mp2, float log_scale_factor2, int n_levels2, const float* s12, const float* R12,
+                          const float* t12, float th, int32_t* match12, int32_t* n_found);
+int planar_search_by_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, const planar_kf_points* d_mp1, float log_scale_factor1, int n_levels1,
+                              const planar_frame_view* d_kf2, const planar_kf_points* d_mp2, float log_scale_factor2, int n_levels2, const float* d_s12,
+                              const float* d_R12, const float* d_t12, float th, int32_t* d_match12, int32_t* d_n_found);
+
+/* ORBmatcher(nn_ratio, check_orientation)::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (src/ORBmatcher.cc:526-659), batched
+ * over B independent key-frame pairs (LoopClosing::ComputeSim3 calls it with ORBmatcher(0.75, true), once per candidate).  Both FeatureVectors are passed as one
+ * node id per feature (-1: in no node), as planar_search_by_bow takes them.  Probes are key frame 1's features in (node ascending, feature index ascending)
+ * order, which is the order of the reference's walk over the common nodes.
+ *   usable1[i] / usable2[i] = GetMapPointMatches()[i] != NULL && !isBad();  keys_un1 / keys_un2 = mvKeysUn (the angle is read);  desc = mDescriptors
+ *   match12[b][idx1] (stride1) = idx2 where the reference stores vpMapPoints2[idx2], else -1; entries at and beyond n1[b] keep their value
+ *   nmatches[b]: the function's return value.
+ * Kept as the reference has them: both sides need a usable map point; vbMatched2 is set at once and seen by later probes; bestDist1 < TH_LOW is strict here
+ * (the (KeyFrame*, Frame&) overload has <=); the float ratio test; the orientation histogram on the mvKeysUn angles of both sides, whose removal clears the
+ * match but not vbMatched2.  n[b] is clamped to [0, stride]; n == 0 on either side gives no match.  PLANAR_EINVAL: a null array, B < 1, a stride outside
+ * [1, PLANAR_MAX_FRAME_KEYS]. */
+int planar_search_by_bow_kf(planar_ctx* ctx, int B, const int32_t* n1, int stride1, const int32_t* node1, const uint8_t* usable1, const planar_keypoint* keys_un1,
+                            const uint8_t* desc1, const int32_t* n2, int stride2, const int32_t* node2, const uint8_t* usable2, const planar_keypoint* keys_un2,
+                            const uint8_t* desc2, float nn_ratio, int check_orientation, int32_t* match12, int32_t* nmatches);
+int planar_search_by_bow_kf_dev(planar_ctx* ctx, int B, const int32_t* d_n1, int stride1, const int32_t* d_node1, const uint8_t* d_usable1,
+                                const planar_keypoint* d_keys_un1, const uint8_t* d_desc1, const int32_t* d_n2, int stride2, const int32_t* d_node2,
+                                const uint8_t* d_usable2, const planar_keypoint* d_keys_un2, const uint8_t* d_desc2, float nn_ratio, int check_orientation,
+                                int32_t* d_match12, int32_t* d_nmatches);
+
+/* ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th)
+ * (src/ORBmatcher.cc:294-407): the loop map points projected into the current key frame under the similarity Scw, batched over B (key frame, Scw, list)
+ * problems.  The list has no length limit (mvpLoopMapPoints is the union over a loop key frame's covisibles); points_shared = 1: one list [1][stride] for all.
+ *   kf: n, keys_un, desc, bounds, grid, fx fy cx cy and scale_factors are read; blocked[b][idx] = vpMatched[idx] != NULL on entry (NULL = none); u_right and Tcw
+ *       are not read.  Scw [B][16] row-major.  log_scale_factor / n_levels = pKF->mfLogScaleFactor / mnScaleLevels.
+ *   usable[j] = !vpPoints[j]->isBad(); found[b][j] (always [B][stride]; NULL = none) = spAlreadyFound.count(vpPoints[j]), fixed on entry;
+ *   xw / normal / desc = GetWorldPos() / GetNormal() / GetDescriptor(); min_dist / max_dist = mfMinDistance / mfMaxDistance (0.8 / 1.2 applied here).
+ *   kf_match[b][idx] (in/out, stride of kf) = iMP where the reference stores vpMatched[idx] = vpPoints[iMP]; untouched where nothing new is stored.
+ *   nmatches[b]: the function's return value.
+ * Kept as the reference has them: scw = (float)sqrt(row0.dot(row0)), Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw.t() * tcw; the gates z < 0, IsInImage,
+ * 0.8 * min / 1.2 * max, PO.dot(Pn) < 0.5 * dist in double; 1 / z in float; radius = th * mvScaleFactors[level] with an int th; a candidate whose vpMatched
+ * entry is non-null NOW is skipped, so a match written earlier in the call blocks its key point; bestDist starts at 256 and bestDist <= TH_LOW decides; no
+ * ratio test, no orientation check.  Each problem has the semantics of one call on the state at entry.
+ * Defined where the reference is not: n[b] is clamped to [0, stride]; scw == 0 gives NaN coordinates, which fail the image gate: nothing matches.
+ * PLANAR_EINVAL: a null array, B < 1, kf->stride outside [1, PLANAR_MAX_FRAME_KEYS], stride < 1, n_levels outside [1, PLANAR_MAX_LEVELS] (a predicted level
+ * could leave mvScaleFactors), log_scale_factor == 0. */
+int planar_search_by_projection_sim3(planar_ctx* ctx, const planar_frame_view* kf, const float* Scw, float log_scale_factor, int n_levels, const int32_t* n, int stride,
+                                     int points_shared, const uint8_t* usable, const uint8_t* found, const float* xw, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* desc, int th, int32_t* kf_match, int32_t* nmatches);
+int planar_search_by_projection_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf, const float* d_Scw, float log_scale_factor, int n_levels, const int32_t* d_n,
+                                         int stride, int points_shared, const uint8_t* d_usable, const uint8_t* d_found, const float* d_xw, const float* d_normal,
+                                         const float* d_min_dist, const float* d_max_dist, const uint8_t* d_desc, int th, int32_t* d_kf_match, int32_t* d_nmatches);
+
+/* ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint) (src/ORBmatcher.cc:981-1104):
+ * the loop map points fused into a corrected key frame (LoopClosing::SearchAndFuse, ORBmatcher(0.8), th = 4), batched over B key frames.  Unlike
+ * planar_fuse_search this entry returns the WHOLE outcome, because the reference's edits feed back inside the call: AddMapPoint (:1097) fills a slot that a
+ * later point then finds occupied (:1088).  A point's best key point does not depend on that, so every point is evaluated on its own and the lowest j that
+ * chose an empty slot owns it.
+ *   kf, Scw, log_scale_factor, n_levels, the point arrays and points_shared: as planar_search_by_projection_sim3 (kf->blocked is not read);
+ *   usable[b][j] (always [B][stride]) = !isBad() && !pKF->GetMapPoints().count(vpPoints[j]), the set taken on entry;
+ *   kf_slot[b][idx] (stride of kf) = pKF->GetMapPoint(idx) on entry: 0 NULL, 1 a map point that is not bad, 2 a bad map point.
+ *   fuse_idx[b][j] = the slot chosen (bestDist <= TH_LOW), or -1 where nothing was fused.
+ *   owner[b][j], written where fuse_idx[b][j] >= 0 and untouched elsewhere:
+ *       -1       the slot held a point on entry: kf_slot 1 means vpReplacePoint[j] = that point; kf_slot 2 means nothing is recorded, yet it counts in nFused
+ *       j        the point took the empty slot: AddObservation / AddMapPoint
+ *       j' < j   an earlier point of this call took it: vpReplacePoint[j] = vpPoints[j']
+ *   n_fused[b]: the function's return value.  Entries at and beyond n[b] keep their value.
+ * Kept as the reference has them: the gates of the projection search minus "already matched"; 1.0 / z is a double division narrowed to float; bestDist starts at
+ * INT_MAX; no chi-square or stereo gates.  A batch is over INDEPENDENT maps and each problem has the semantics of one call on the state at entry:
+ * LoopClosing::SearchAndFuse applies the replacements between the key frames of one map, which is the caller's business, as with planar_fuse_search.
+ * Undefined input and PLANAR_EINVAL as for planar_search_by_projection_sim3. */
+int planar_fuse_sim3(planar_ctx* ctx, const planar_frame_view* kf, const float* Scw, const uint8_t* kf_slot, float log_scale_factor, int n_levels, const int32_t* n,
+                     int stride, int points_shared, const uint8_t* usable, const float* xw, const float* normal, const float* min_dist, const float* max_dist,
+                     const uint8_t* desc, float th, int32_t* fuse_idx, int32_t* owner, int32_t* n_fused);
+int planar_fuse_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf, const float* d_Scw, const uint8_t* d_kf_slot, float log_scale_factor, int n_levels,
+                         const int32_t* d_n, int stride, int points_shared, const uint8_t* d_usable, const float* d_xw, const float* d_normal, const float* d_min_dist,
+                         const float* d_max_dist, const uint8_t* d_desc, float th, int32_t* d_fuse_idx, int32_t* d_owner, int32_t* d_n_fused);
+
 /* PlaneMatcher::SearchMapByCoefficients(Frame&, const vector<MapPlane*>&) (src/PlaneMatcher.cpp:10-66) with
  * Frame::ComputePlaneWorldCoeff (src/Frame.cc:815-820) and PointDistanceFromPlane (:67-79).
  *   pl_coef [B][pl_stride][4]  mvPlaneCoefficients[i] (camera frame)      Tcw [B][16]

@@ -8,6 +8,7 @@
 //   ORBmatcher::Fuse / LSDmatcher::Fuse (search on the device, map edits as in the reference)         (PLANAR_ADAPTERS_WITH_FUSE, needs one accessor, see there)
 //   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
+//   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1297,3 +1298,195 @@ inline void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Ma
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_LOCAL_BA
 
+
+// ---- The loop thread's matchers (LoopClosing::ComputeSim3, SearchAndFuse): DEFINITIONS of the four ORBmatcher members with the reference's signatures
+//          int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12)                                        src/ORBmatcher.cc:526-659
+//          int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const cv::Mat& R12,
+//                           const cv::Mat& t12, const float th)                                                                        src/ORBmatcher.cc:1106-1330
+//          int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th)   :294-407
+//          int Fuse(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint)          :981-1104
+//      Enabled with PLANAR_ADAPTERS_WITH_LOOP_MATCHERS, after the reference's ORBmatcher.h, KeyFrame.h and MapPoint.h; leave src/ORBmatcher.cc's four bodies out.  Each
+//      call gathers the key frames and map points into arrays, runs the host flavour with B = 1 on the tracking context and performs the reference's own edit
+//      statements on its own objects: SearchBySim3 translates vpMatches12 through MapPoint::GetIndexInKeyFrame, Fuse performs AddObservation / AddMapPoint and fills
+//      vpReplacePoint in the order of the points from `owner`.  Needs MapPoint::GetDistanceRange, the accessor of PLANAR_ADAPTERS_WITH_FUSE.  A failing call returns 0
+//      and changes nothing.
+#ifdef PLANAR_ADAPTERS_WITH_LOOP_MATCHERS
+#include <set>
+namespace planar_adapter {
+
+// the key frame's side: key points, descriptors, bounds, grid constants, intrinsics, scale factors; the pose only where asked (GetPose())
+struct KeyFrameGather {
+    int32_t n;
+    std::vector<planar_keypoint> keys;
+    std::vector<uint8_t> desc;
+    float Tcw[16];
+    planar_frame_view view;
+    template <class KeyFrameT> KeyFrameGather(KeyFrameT* pKF, bool with_pose) {
+        n = pKF->N;
+        keys.resize(n > 0 ? n : 1); desc.assign(keys.size() * 32, 0);
+        for (int i = 0; i < n; i++) { std::memcpy(&keys[i], &pKF->mvKeysUn[i], sizeof(planar_keypoint)); std::memcpy(&desc[(size_t)i * 32], pKF->mDescriptors.ptr(i), 32); }
+        std::memset(&view, 0, sizeof(view));
+        view.B = 1; view.stride = (int32_t)keys.size(); view.n = &n; view.keys_un = keys.data(); view.desc = desc.data();
+        if (with_pose) { cv::Mat T = pKF->GetPose(); for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = T.template at<float>(r, c); view.Tcw = Tcw; }
+        view.min_x = pKF->mnMinX; view.max_x = pKF->mnMaxX; view.min_y = pKF->mnMinY; view.max_y = pKF->mnMaxY;
+        view.grid_w_inv = pKF->mfGridElementWidthInv; view.grid_h_inv = pKF->mfGridElementHeightInv;
+        view.fx = pKF->fx; view.fy = pKF->fy; view.cx = pKF->cx; view.cy = pKF->cy; view.bf = pKF->mbf; view.b = pKF->mb;
+        for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = pKF->mvScaleFactors[l];
+    }
+};
+
+// a list of map points as the arrays of the entries: usable = non-NULL && !isBad()
+struct PointGather {
+    std::vector<uint8_t> usable, desc;
+    std::vector<float> xw, nrm, mn, mx;
+    planar_kf_points kp;
+    template <class MapPointT> explicit PointGather(const std::vector<MapPointT*>& v, bool want_normal) {
+        const size_t M = v.size() ? v.size() : 1;
+        usable.assign(M, 0); desc.assign(M * 32, 0); xw.assign(M * 3, 0.f); nrm.assign(M * 3, 0.f); mn.assign(M, 0.f); mx.assign(M, 0.f);
+        for (size_t j = 0; j < v.size(); j++) {
+            MapPointT* p = v[j];
+            if (!p || p->isBad()) continue;
+            usable[j] = 1;
+            cv::Mat X = p->GetWorldPos(), d = p->GetDescriptor();
+            for (int k = 0; k < 3; k++) xw[3 * j + k] = X.template at<float>(k);
+            if (want_normal) { cv::Mat nv = p->GetNormal(); for (int k = 0; k < 3; k++) nrm[3 * j + k] = nv.template at<float>(k); }
+            std::memcpy(&desc[j * 32], d.ptr(0), 32);
+            p->GetDistanceRange(mn[j], mx[j]);
+        }
+        kp.usable = usable.data(); kp.xw = xw.data(); kp.min_dist = mn.data(); kp.max_dist = mx.data(); kp.desc = desc.data();
+    }
+};
+
+inline Runtime::Lane& loop_lane() { return Runtime::get().lane(TRACKING); }
+
+template <class KeyFrameT, class MapPointT>
+int SearchByBoWKF(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, float nn_ratio, bool check_orientation) {
+    KeyFrameT* kf[2] = {pKF1, pKF2};
+    std::vector<MapPointT*> mps[2] = {pKF1->GetMapPointMatches(), pKF2->GetMapPointMatches()};
+    KeyFrameGather g1(pKF1, false), g2(pKF2, false);
+    std::vector<int32_t> node[2];
+    std::vector<uint8_t> usable[2];
+    for (int s = 0; s < 2; s++) {
+        const size_t S = s ? g2.keys.size() : g1.keys.size();
+        node[s].assign(S, -1); usable[s].assign(S, 0);
+        for (auto it = kf[s]->mFeatVec.begin(); it != kf[s]->mFeatVec.end(); ++it)
+            for (size_t k = 0; k < it->second.size(); k++) if (it->second[k] < S) node[s][it->second[k]] = (int32_t)it->first;
+        for (size_t i = 0; i < mps[s].size() && i < S; i++) usable[s][i] = mps[s][i] && !mps[s][i]->isBad();
+    }
+    std::vector<int32_t> match(g1.keys.size(), -1);
+    int32_t nmatches = 0;
+    {
+        Runtime::Lane& L = loop_lane();
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_search_by_bow_kf(L.ctx, 1, &g1.n, g1.view.stride, node[0].data(), usable[0].data(), g1.keys.data(), g1.desc.data(), &g2.n, g2.view.stride, node[1].data(),
+                                        usable[1].data(), g2.keys.data(), g2.desc.data(), nn_ratio, check_orientation ? 1 : 0, match.data(), &nmatches), "planar_search_by_bow_kf"))
+            return 0;
+    }
+    vpMatches12 = std::vector<MapPointT*>(mps[0].size(), static_cast<MapPointT*>(NULL));
+    for (size_t i = 0; i < mps[0].size(); i++) if (match[i] >= 0) vpMatches12[i] = mps[1][match[i]];
+    return nmatches;
+}
+
+template <class KeyFrameT, class MapPointT>
+int SearchBySim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, float s12, const cv::Mat& R12, const cv::Mat& t12, float th) {
+    const std::vector<MapPointT*> mps1 = pKF1->GetMapPointMatches(), mps2 = pKF2->GetMapPointMatches();
+    const int N1 = (int)mps1.size(), N2 = (int)mps2.size();
+    KeyFrameGather g1(pKF1, true), g2(pKF2, true);
+    PointGather p1(mps1, false), p2(mps2, false);
+    const int32_t NOT_IN_KF2 = -2;                                                      // matched, index not in pKF2: blocks i1 only (:1143)
+    std::vector<int32_t> entry(g1.keys.size(), -1);
+    for (int i = 0; i < N1; i++)
+        if (vpMatches12[i]) { const int idx2 = vpMatches12[i]->GetIndexInKeyFrame(pKF2); entry[i] = idx2 >= 0 && idx2 < N2 ? idx2 : NOT_IN_KF2; }
+    std::vector<int32_t> match = entry;
+    float R[9], t[3];
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[3 * r + c] = R12.at<float>(r, c); t[r] = t12.at<float>(r); }
+    int32_t nFound = 0;
+    {
+        Runtime::Lane& L = loop_lane();
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_search_by_sim3(L.ctx, &g1.view, &p1.kp, pKF1->mfLogScaleFactor, pKF1->mnScaleLevels, &g2.view, &p2.kp, pKF2->mfLogScaleFactor, pKF2->mnScaleLevels, &s12, R, t,
+                                      th, match.data(), &nFound), "planar_search_by_sim3"))
+            return 0;
+    }
+    for (int i = 0; i < N1; i++) if (match[i] != entry[i]) vpMatches12[i] = mps2[match[i]];      // :1323
+    return nFound;
+}
+
+inline void scw_to_array(const cv::Mat& Scw, float* S) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) S[4 * r + c] = Scw.at<float>(r, c); }
+
+template <class KeyFrameT, class MapPointT>
+int SearchByProjectionScw(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched, int th) {
+    const int M = (int)vpPoints.size();
+    if (M == 0) return 0;
+    KeyFrameGather g(pKF, false);
+    std::vector<uint8_t> blocked(g.keys.size(), 0), found(M, 0);
+    for (size_t i = 0; i < vpMatched.size() && i < blocked.size(); i++) blocked[i] = vpMatched[i] != NULL;
+    g.view.blocked = blocked.data();
+    std::set<MapPointT*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+    spAlreadyFound.erase(static_cast<MapPointT*>(NULL));
+    PointGather pts(vpPoints, true);
+    for (int j = 0; j < M; j++) found[j] = spAlreadyFound.count(vpPoints[j]) ? 1 : 0;
+    float S[16];
+    scw_to_array(Scw, S);
+    std::vector<int32_t> match(g.keys.size(), -1);
+    int32_t m = M, nmatches = 0;
+    {
+        Runtime::Lane& L = loop_lane();
+        std::lock_guard<std::mutex> lk(L.mu);
+        if (!ok(planar_search_by_projection_sim3(L.ctx, &g.view, S, pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), found.data(), pts.xw.data(), pts.nrm.data(),
+                                                 pts.mn.data(), pts.mx.data(), pts.desc.data(), th, match.data(), &nmatches), "planar_search_by_projection_sim3"))
+            return 0;
+    }
+    for (size_t i = 0; i < vpMatched.size() && i < match.size(); i++) if (match[i] >= 0) vpMatched[i] = vpPoints[match[i]];   // :400
+    return nmatches;
+}
+
+template <class KeyFrameT, class MapPointT>
+int FuseScw(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
+    const int M = (int)vpPoints.size();
+    if (M == 0) return 0;
+    KeyFrameGather g(pKF, false);
+    const std::set<MapPointT*> spAlreadyFound = pKF->GetMapPoints();                     // :997
+    const std::vector<MapPointT*> inKF = pKF->GetMapPointMatches();
+    std::vector<uint8_t> slot(g.keys.size(), 0);
+    for (size_t i = 0; i < inKF.size() && i < slot.size(); i++) slot[i] = !inKF[i] ? 0 : inKF[i]->isBad() ? 2 : 1;
+    PointGather pts(vpPoints, true);
+    for (int j = 0; j < M; j++) if (pts.usable[j] && spAlreadyFound.count(vpPoints[j])) pts.usable[j] = 0;
+    float S[16];
+    scw_to_array(Scw, S);
+    std::vector<int32_t> idx(M, -1), owner(M, -1);
+    int32_t m = M, nFused = 0;
+    {
+        Runtime::Lane& L = loop_lane();
+        std::lock_guard<std::mutex> lk(L.mu);
+        if (!ok(planar_fuse_sim3(L.ctx, &g.view, S, slot.data(), pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), pts.xw.data(), pts.nrm.data(), pts.mn.data(),
+                                 pts.mx.data(), pts.desc.data(), th, idx.data(), owner.data(), &nFused), "planar_fuse_sim3"))
+            return 0;
+    }
+    for (int j = 0; j < M; j++) {                                                       // :1086-1100, in the order of the points
+        if (idx[j] < 0) continue;
+        MapPointT* pMP = vpPoints[j];
+        if (owner[j] == j) { pMP->AddObservation(pKF, idx[j]); pKF->AddMapPoint(pMP, idx[j]); }
+        else if (owner[j] >= 0) vpReplacePoint[j] = vpPoints[owner[j]];
+        else { MapPointT* pMPinKF = pKF->GetMapPoint(idx[j]); if (pMPinKF && !pMPinKF->isBad()) vpReplacePoint[j] = pMPinKF; }
+    }
+    return nFused;
+}
+
+}  // namespace planar_adapter
+
+namespace Planar_SLAM {
+inline int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12) {
+    return planar_adapter::SearchByBoWKF(pKF1, pKF2, vpMatches12, mfNNratio, mbCheckOrientation);
+}
+inline int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12, const float& s12, const cv::Mat& R12, const cv::Mat& t12, const float th) {
+    return planar_adapter::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th);
+}
+inline int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched, int th) {
+    return planar_adapter::SearchByProjectionScw(pKF, Scw, vpPoints, vpMatched, th);
+}
+inline int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint) {
+    return planar_adapter::FuseScw(pKF, Scw, vpPoints, th, vpReplacePoint);
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_LOOP_MATCHERS

@@ -81,6 +81,11 @@ class KeyframeProbes(C.Structure):
     _fields_ = [("stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n", "usable", "found", "xw", "min_dist", "max_dist", "angle", "desc")]
 
 
+class KfPoints(C.Structure):
+    """planar_kf_points: GetMapPointMatches() of the key frame a FrameView describes"""
+    _fields_ = [(n, C.c_void_p) for n in ("usable", "xw", "min_dist", "max_dist", "desc")]
+
+
 class TriCamera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
                 ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
@@ -239,6 +244,14 @@ _SIGS = {
     "planar_kfdb_detect_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(KfDatabase), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
     "planar_bow_score": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     "planar_bow_score_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
+    "planar_search_by_bow_kf": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_search_by_bow_kf_dev": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_search_by_projection_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_search_by_projection_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "planar_fuse_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3),
+    "planar_fuse_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 3),
+    "planar_search_by_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2),
+    "planar_search_by_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2),
     "planar_is_line_good": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_is_line_good_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_normals_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -27,6 +27,15 @@ __device__ inline float gemm_small_row_add(float a0, float a1, float a2, float x
     return (float)((double)t * 1.0 + (double)c * 1.0);
 }
 __device__ inline float gemm_small_row_add(const float* a, const float* x, float c) { return gemm_small_row_add(a[0], a[1], a[2], x[0], x[1], x[2], c); }
+// the row of a product with alpha = -1 and no "+ c": t21 = -sR21 * t12 (src/ORBmatcher.cc:1125).  -A is a lazy scale of A, so the product that follows is one
+// gemm with alpha = -1.0 on the small-matrix path; KeyFrame::SetPose's Ow = -Rwc * tcw below is the same expression written out
+__device__ inline float gemm_small_row_neg(float a0, float a1, float a2, float x0, float x1, float x2) {
+    return (float)((double)gemm_small_row(a0, a1, a2, x0, x1, x2) * -1.0);
+}
+
+// ---- the scaled copy alpha * A, A / s (convertTo with a scale = cvtScale32f): the double scale is cast to float, then one float multiply.
+// sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t() (src/ORBmatcher.cc:1123-1124) ----
+__device__ inline float scale32f(float a, double alpha) { return a * (float)alpha; }
 
 // ---- double accumulation: Mat::dot (ray1.dot(ray2), Rcw.row(i).dot(x3Dt): src/LocalMapping.cc:404, :448-483) and one row of cv::gemm's general
 // path, which a transposed operand forces (-mRcw.t() * mtcw, src/Frame.cc:305).  Both start from zero ... ----
@@ -73,6 +82,15 @@ __device__ inline void load_pose_frame(const float* T, Pose& p) {
 __device__ inline void load_pose_keyframe(const float* T, Pose& p) {
     load_Rt(T, p);
     for (int i = 0; i < 3; i++) p.Ow[i] = (float)((double)gemm_small_row(p.Rcw[i], p.Rcw[3 + i], p.Rcw[6 + i], p.tcw[0], p.tcw[1], p.tcw[2]) * -1.0);
+}
+
+// The decomposition of a similarity Scw (src/ORBmatcher.cc:303-307, :990-994): scw = sqrt(sRcw.row(0).dot(sRcw.row(0))), the dot in double and the root narrowed to
+// float; Rcw = sRcw / scw and tcw = Scw.rowRange(0, 3).col(3) / scw are scaled copies with alpha = 1.0 / scw; Ow = -Rcw.t() * tcw takes the general path.
+__device__ inline void load_pose_scw(const float* S, Pose& p) {
+    const float scw = (float)sqrt(dot3(S[0], S[1], S[2], S[0], S[1], S[2]));
+    const double inv = 1.0 / (double)scw;
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.Rcw[3 * r + c] = scale32f(S[4 * r + c], inv); p.tcw[r] = scale32f(S[4 * r + 3], inv); }
+    for (int i = 0; i < 3; i++) p.Ow[i] = gemm_general_neg(gemm_general_row(p.Rcw[i], p.Rcw[3 + i], p.Rcw[6 + i], p.tcw[0], p.tcw[1], p.tcw[2]));
 }
 
 // ---- ORB / LBD descriptors: the Hamming distance of two 256-bit descriptors (ORBmatcher::DescriptorDistance, src/ORBmatcher.cc:1712; cv::NORM_HAMMING) ----

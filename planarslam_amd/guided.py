@@ -5,6 +5,10 @@
     ORBmatcher.SearchByProjection(F, pKF, sAlreadyFound, th, ORBdist)    reference src/ORBmatcher.cc:1537 (include/ORBmatcher.h:57)
     ORBmatcher.SearchByBoW(pKF, F, vpMapPointMatches)                   reference src/ORBmatcher.cc:160  (include/ORBmatcher.h:59)
     ORBmatcher.Fuse(pKF, vpMapPoints, th), the search half              reference src/ORBmatcher.cc:829  (include/ORBmatcher.h:81)
+    ORBmatcher.SearchByBoW(pKF1, pKF2, vpMatches12)                     reference src/ORBmatcher.cc:526  (include/ORBmatcher.h:60)
+    ORBmatcher.SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) reference src/ORBmatcher.cc:1106 (include/ORBmatcher.h:78)
+    ORBmatcher.SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)    reference src/ORBmatcher.cc:294  (include/ORBmatcher.h:53)
+    ORBmatcher.Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)             reference src/ORBmatcher.cc:981  (include/ORBmatcher.h:84)
     LSDmatcher.SearchByProjection(F, vpMapLines, th)                    reference src/LSDmatcher.cpp:141
     LSDmatcher.Fuse(pKF, vpMapLines, th), the search half               reference src/LSDmatcher.cpp:884
     PlaneMatcher.SearchMapByCoefficients(pF, vpMapPlanes)               reference src/PlaneMatcher.cpp:10
@@ -17,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import KEYLINE_DTYPE, KP_DTYPE, MAX_LEVELS, Context, FrameView, KeyframeProbes, LastFrameView, MapProbes, check, lib
+from ._lib import KEYLINE_DTYPE, KP_DTYPE, MAX_LEVELS, Context, FrameView, KeyframeProbes, KfPoints, LastFrameView, MapProbes, check, lib
 
 
 def _c(a, dt):
@@ -80,6 +84,16 @@ def keyframe_probes(d: dict):
         keep["found"] = _c(d["found"], np.uint8)
     v = KeyframeProbes()
     v.stride = keep["usable"].shape[1]
+    for k, a in keep.items():
+        setattr(v, k, a.ctypes.data)
+    return v, keep
+
+
+def kf_points(d: dict):
+    """key-frame dict -> (planar_kf_points, keepalive): GetMapPointMatches() as usable[B,S], xw[B,S,3], min_dist, max_dist[B,S], mp_desc[B,S,32]"""
+    keep = dict(usable=_c(d["usable"], np.uint8), xw=_c(d["xw"], np.float32), min_dist=_c(d["min_dist"], np.float32), max_dist=_c(d["max_dist"], np.float32),
+                desc=_c(d["mp_desc"], np.uint8))
+    v = KfPoints()
     for k, a in keep.items():
         setattr(v, k, a.ctypes.data)
     return v, keep
@@ -172,6 +186,78 @@ class ORBmatcher:
                                        a["normal"].ctypes.data, a["min_dist"].ctypes.data, a["max_dist"].ctypes.data, a["desc"].ctypes.data, th,
                                        idx.ctypes.data, dist.ctypes.data, nf.ctypes.data))
         return idx, dist, nf
+
+
+    def SearchBySim3(self, kf1: dict, kf2: dict, match12, s12, R12, t12, th: float = 7.5):
+        """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) for B key-frame pairs.  kf1 / kf2: frame dicts with Tcw plus the map points of
+        kf_points; match12 [B,S1]: vpMatches12 on entry as GetIndexInKeyFrame(pKF2) of each point / -1 for NULL (see include/planar_abi.h).
+        Returns (match12 on exit, n_found [B])."""
+        v1, k1 = frame_view(kf1); v2, k2 = frame_view(kf2)
+        p1, k3 = kf_points(kf1); p2, k4 = kf_points(kf2)
+        s = _c(s12, np.float32); R = _c(R12, np.float32).reshape(v1.B, 9); t = _c(t12, np.float32).reshape(v1.B, 3)
+        m = _c(match12, np.int32).copy()
+        assert m.shape == (v1.B, v1.stride) and s.shape == (v1.B,)
+        nf = np.zeros(v1.B, np.int32)
+        check(lib().planar_search_by_sim3(self.ctx.h, C.byref(v1), C.byref(p1), _log_scale_factor(kf1), len(kf1["scale_factors"]), C.byref(v2), C.byref(p2),
+                                          _log_scale_factor(kf2), len(kf2["scale_factors"]), s.ctypes.data, R.ctypes.data, t.ctypes.data, th, m.ctypes.data,
+                                          nf.ctypes.data))
+        return m, nf
+
+
+    def SearchByBoWKF(self, kf1: dict, kf2: dict, match12=None):
+        """SearchByBoW(pKF1, pKF2, vpMatches12) for B key-frame pairs.  kf1 / kf2: n[B], node[B,S] (one vocabulary node per feature, -1 none), usable[B,S]
+        (a map point that is not bad), keys_un[B,S] (KP_DTYPE: the angle is read), desc[B,S,32].  match12: what rows at and beyond n1 hold (default -1).
+        Returns (match12 [B,S1] = the feature of pKF2 / -1, nmatches [B])."""
+        a = [dict(n=_c(k["n"], np.int32), node=_c(k["node"], np.int32), usable=_c(k["usable"], np.uint8), keys=_c(k["keys_un"], KP_DTYPE), desc=_c(k["desc"], np.uint8))
+             for k in (kf1, kf2)]
+        B, S1 = a[0]["node"].shape
+        m = np.full((B, S1), -1, np.int32) if match12 is None else _c(match12, np.int32).copy()
+        nm = np.zeros(B, np.int32)
+        args = []
+        for k in a:
+            args += [k["n"].ctypes.data, k["node"].shape[1], k["node"].ctypes.data, k["usable"].ctypes.data, k["keys"].ctypes.data, k["desc"].ctypes.data]
+        check(lib().planar_search_by_bow_kf(self.ctx.h, B, *args, self.mfNNratio, int(self.mbCheckOrientation), m.ctypes.data, nm.ctypes.data))
+        return m, nm
+
+    @staticmethod
+    def _scw_points(pts: dict):
+        a = dict(n=_c(pts["n"], np.int32), usable=_c(pts["usable"], np.uint8), xw=_c(pts["xw"], np.float32), normal=_c(pts["normal"], np.float32),
+                 min_dist=_c(pts["min_dist"], np.float32), max_dist=_c(pts["max_dist"], np.float32), desc=_c(pts["desc"], np.uint8))
+        return a, a["usable"].shape[-1]
+
+    def SearchByProjectionSim3(self, kf: dict, Scw, pts: dict, th: int = 10, found=None, shared: bool = False, kf_match=None):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) for B key frames.  kf: a frame dict whose blocked[B,S] = vpMatched[idx] != NULL on entry; Scw [B,16];
+        pts: n, usable (not bad), xw, normal, min_dist, max_dist, desc, [B,PS] or [1,PS] with shared; found [B,PS] = the point is in vpMatched on entry.
+        Returns (kf_match [B,S] = iMP where the reference stores vpPoints[iMP], untouched elsewhere (default -1), nmatches [B])."""
+        fv, keep = frame_view(kf)
+        a, PS = self._scw_points(pts)
+        S = _c(Scw, np.float32).reshape(fv.B, 16)
+        f = None if found is None else _c(found, np.uint8)
+        m = np.full((fv.B, fv.stride), -1, np.int32) if kf_match is None else _c(kf_match, np.int32).copy()
+        nm = np.zeros(fv.B, np.int32)
+        check(lib().planar_search_by_projection_sim3(self.ctx.h, C.byref(fv), S.ctypes.data, _log_scale_factor(kf), len(kf["scale_factors"]), a["n"].ctypes.data, PS,
+                                                     int(shared), a["usable"].ctypes.data, None if f is None else f.ctypes.data, a["xw"].ctypes.data,
+                                                     a["normal"].ctypes.data, a["min_dist"].ctypes.data, a["max_dist"].ctypes.data, a["desc"].ctypes.data, int(th),
+                                                     m.ctypes.data, nm.ctypes.data))
+        return m, nm
+
+    def FuseSim3(self, kf: dict, Scw, pts: dict, th: float = 4.0, usable=None, shared: bool = False, fuse_idx=None, owner=None):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) for B key frames of independent maps, the whole outcome.  kf: a frame dict with kf_slot[B,S] (0 NULL, 1 a map
+        point, 2 a bad one); usable [B,PS] = not bad and not in the key frame on entry (default pts["usable"]); fuse_idx / owner: what the entries the call does not
+        write hold (default -1).  Returns (fuse_idx [B,PS], owner [B,PS] (see include/planar_abi.h), n_fused [B])."""
+        fv, keep = frame_view(kf)
+        a, PS = self._scw_points(pts)
+        S = _c(Scw, np.float32).reshape(fv.B, 16)
+        slot = _c(kf["kf_slot"], np.uint8)
+        u = _c(a["usable"] if usable is None else usable, np.uint8)
+        assert u.shape == (fv.B, PS) and slot.shape == (fv.B, fv.stride)
+        fi = np.full((fv.B, PS), -1, np.int32) if fuse_idx is None else _c(fuse_idx, np.int32).copy()
+        ow = np.full((fv.B, PS), -1, np.int32) if owner is None else _c(owner, np.int32).copy()
+        nf = np.zeros(fv.B, np.int32)
+        check(lib().planar_fuse_sim3(self.ctx.h, C.byref(fv), S.ctypes.data, slot.ctypes.data, _log_scale_factor(kf), len(kf["scale_factors"]), a["n"].ctypes.data, PS,
+                                     int(shared), u.ctypes.data, a["xw"].ctypes.data, a["normal"].ctypes.data, a["min_dist"].ctypes.data, a["max_dist"].ctypes.data,
+                                     a["desc"].ctypes.data, th, fi.ctypes.data, ow.ctypes.data, nf.ctypes.data))
+        return fi, ow, nf
 
 
 class LSDmatcher:
