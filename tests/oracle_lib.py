@@ -64,7 +64,8 @@ class OrbOracle:
         self.L = lib()
         self.nlevels = nlevels
         self.h = self.L.orc_orb_create(nfeatures, scale, nlevels, ini, mn)
-        self.cap = max(4 * nfeatures, 64)
+        # a level returns up to 4 nodes per initial node (at most 64 of those) however small its share of nfeatures is
+        self.cap = max(4 * nfeatures, 64) + 4 * 64 * nlevels
 
     def __del__(self):
         if getattr(self, "h", None):

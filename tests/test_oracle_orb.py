@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from planarslam_amd.synth import gray_image
+import orb_cases as oc
 
 
 def _params(z):
@@ -37,19 +37,57 @@ def test_oracle_matches_reference_golden(path):
     assert np.array_equal(o.level(o.nlevels - 1), z["last_level"])
 
 
+def _live_case(case):
+    """(image, parameters) of a seeded frame at the default parameters, or of a named case of tests/orb_cases.py"""
+    if isinstance(case, str):
+        return oc.BY_NAME[case].image(), oc.BY_NAME[case].params
+    seed, w, h = case
+    return oc.noisy(seed, w, h, 25), dict(oc.DEFAULTS)
+
+
 @pytest.mark.skipif(not os.path.exists(ol.ref_orb_path()), reason="oracle/_ref/ref_orb not built")
-@pytest.mark.parametrize("seed,w,h", [(21, 640, 480), (22, 400, 300), (23, 333, 257)])
-def test_oracle_matches_live_reference(seed, w, h):
-    img = gray_image(seed, w, h)
-    rng = np.random.default_rng(seed)
-    img = np.clip(img.astype(np.int32) + rng.integers(-25, 26, img.shape), 0, 255).astype(np.uint8)
-    o = ol.OrbOracle()
-    kps, desc = o.extract(img)
-    rk, rd, pyr = ol.run_ref_orb(img)
+@pytest.mark.parametrize("case", [(21, 640, 480), (22, 400, 300), (23, 333, 257)] + oc.NAMES,
+                         ids=lambda c: c if isinstance(c, str) else "-".join(map(str, c)))
+def test_oracle_matches_live_reference(case):
+    """The pin of every case of the table: keypoints as bytes, descriptors and every pyramid level of the real ORBextractor."""
+    img, p = _live_case(case)
+    if isinstance(case, str):
+        f = oc.facts(case)
+        kps, desc, levels = f.kps, f.desc, f.levels
+    else:
+        o = ol.OrbOracle(**p)
+        kps, desc = o.extract(img)
+        levels = [o.level(l) for l in range(p["nlevels"])]
+    rk, rd, pyr = ol.run_ref_orb(img, **p)
+    assert len(kps) == len(rk)
     assert kps.tobytes() == rk.tobytes()
     assert np.array_equal(desc, rd)
-    for l in range(8):
-        assert np.array_equal(o.level(l), pyr[l])
+    assert len(pyr) == p["nlevels"]
+    for l in range(p["nlevels"]):
+        assert np.array_equal(levels[l], pyr[l]), f"pyramid level {l}"
+
+
+@pytest.mark.parametrize("name", oc.NAMES)
+def test_case_self_checks(name):
+    """Every case of tests/orb_cases.py still reaches the path it exists for (oracle-side facts only)."""
+    f = oc.facts(name)
+    oc.BY_NAME[name].check(f)
+    assert f.kps.tobytes() == ol.OrbOracle(**oc.BY_NAME[name].params).extract(f.image)[0].tobytes()      # the shared reference is what a fresh oracle gives
+
+
+def test_golden_fixtures_of_the_table_are_the_table_cases():
+    """orb_wide960 / orb_strip2049 / orb_strip_few hold the image and parameters of their case, so the reference-made anchor and the table cannot drift apart."""
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    for key, name in oc.GOLDEN.items():
+        z = np.load(os.path.join(here, f"orb_{key}.npz"))
+        assert np.array_equal(z["image"], oc.BY_NAME[name].image()) and _params(z) == oc.BY_NAME[name].params
+        assert os.path.getsize(os.path.join(here, f"orb_{key}.npz")) < 500_000
+
+
+def test_oracle_returns_more_keypoints_than_four_times_nfeatures():
+    """A level returns 4 keypoints per initial node even when its share of nfeatures is smaller: 172 keypoints for nfeatures = 30 on the 2049 x 129 strip."""
+    f = oc.facts("strip_fewer_than_ini")
+    assert len(f.kps) == 172 > 4 * 30
 
 
 def test_constructor_tables():
