@@ -34,6 +34,12 @@ void set_error(const char* fmt, ...);
 template <typename T>
 static inline T align_up(T v, T a) { return (v + a - 1) / a * a; }
 
+// Argument checks of the matcher entry points (guided.hip, loopmatch.hip): a level count, and what every kernel with the key-point grid in LDS needs of a frame
+// view (its sizes, then n, keys_un and desc; the other arrays are the entry point's to ask for).
+static inline bool n_levels_ok(int n) { return n >= 1 && n <= PLANAR_MAX_LEVELS; }
+static inline bool frame_view_sizes_ok(const planar_frame_view* f) { return f->B >= 1 && f->stride >= 1 && f->stride <= PLANAR_MAX_FRAME_KEYS; }
+static inline bool frame_view_ok(const planar_frame_view* f) { return frame_view_sizes_ok(f) && f->n && f->keys_un && f->desc; }
+
 // Device memory owner (no exceptions).
 struct DevBuf {
     void* p = nullptr;

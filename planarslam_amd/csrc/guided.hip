@@ -22,130 +22,16 @@
 // The chunk size adapts to the LDS list capacity, so there is no overflow path.  One workgroup per frame
 // (pair); the batch dimension fills the GPU.  Integer / float32 work, bit-exact with the oracle.
 #include "common.h"
+#include "match_chunk.h"
 #include "ref_arith.h"
 
 namespace planar {
 namespace guided {
 
-using ref::HISTO_LENGTH;
+using namespace chunk;
 using ref::Pose;
 
-constexpr int NT = 256;
-constexpr int NCELL = PLANAR_GRID_COLS * PLANAR_GRID_ROWS;
-constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
-constexpr int CAND_CAP = 8192;       // candidates of one chunk of probes; with it the workgroup needs 61 KB of LDS (two per CU)
-constexpr int TH_HIGH = 100, TH_LOW = 50;   // src/ORBmatcher.cc:38-39
-
 enum { MODE_FRAME = 0, MODE_MAP = 1, MODE_BOW = 2, MODE_KF = 3 };
-
-struct Lds {
-    uint32_t cand[CAND_CAP];       // dist << 16 | octave << 12 | index ; doubles as scratch while the grid is built
-    uint16_t cell_start[NCELL + 1];
-    uint16_t items[MAXN];
-    uint32_t blocked[MAXN / 32];
-    int pid[NT];
-    int poff[NT + 1];
-    uint16_t ev_idx[MAXN];
-    uint8_t ev_bin[MAXN];
-    int hist[HISTO_LENGTH];
-    int keep[3];
-    int n_ev, nmatches, m_fit, wsum[NT / 64];
-};
-
-// a shuffle butterfly; planar::wave_min_u32 (wave_ops.h) is a DPP ladder.  Swapping one for the other changes the benchmarked path: a change of its own.
-__device__ inline uint32_t wave_min_u32_shfl(uint32_t v) {
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
-// Frame::AssignFeaturesToGrid (src/Frame.cc:155-166, PosInGrid :526-535) into cell_start / items.
-template <typename L>
-__device__ void build_grid(L& s, const planar_frame_view& f, const planar_keypoint* keys, int N) {
-    const int tid = threadIdx.x;
-    uint32_t* cnt = s.cand;            // [NCELL] counters, then cursors
-    for (int c = tid; c < NCELL; c += NT) cnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < N; i += NT) {
-        const int px = (int)roundf((keys[i].x - f.min_x) * f.grid_w_inv);
-        const int py = (int)roundf((keys[i].y - f.min_y) * f.grid_h_inv);
-        if (px < 0 || px >= PLANAR_GRID_COLS || py < 0 || py >= PLANAR_GRID_ROWS) continue;
-        atomicAdd(&cnt[px * PLANAR_GRID_ROWS + py], 1u);
-    }
-    __syncthreads();
-    constexpr int PER = NCELL / NT;    // 12 consecutive cells per thread
-    int local = 0;
-    for (int k = 0; k < PER; k++) local += (int)cnt[tid * PER + k];
-    int total;
-    int run = ref::block_exscan<NT / 64>(local, s.wsum, &total);
-    for (int k = 0; k < PER; k++) {
-        const int c = tid * PER + k, n = (int)cnt[c];
-        s.cell_start[c] = (uint16_t)run;
-        cnt[c] = (uint32_t)run;        // cursor
-        run += n;
-    }
-    if (tid == NT - 1) s.cell_start[NCELL] = (uint16_t)run;
-    __syncthreads();
-    for (int i = tid; i < N; i += NT) {
-        const int px = (int)roundf((keys[i].x - f.min_x) * f.grid_w_inv);
-        const int py = (int)roundf((keys[i].y - f.min_y) * f.grid_h_inv);
-        if (px < 0 || px >= PLANAR_GRID_COLS || py < 0 || py >= PLANAR_GRID_ROWS) continue;
-        const uint32_t pos = atomicAdd(&cnt[px * PLANAR_GRID_ROWS + py], 1u);
-        s.items[pos] = (uint16_t)i;
-    }
-    __syncthreads();
-    // push_back order inside a cell is ascending keypoint index: insertion-sort each (tiny) cell list
-    for (int k = 0; k < PER; k++) {
-        const int c = tid * PER + k;
-        const int a = s.cell_start[c], e = s.cell_start[c + 1];
-        for (int i = a + 1; i < e; i++) {
-            const uint16_t v = s.items[i];
-            int j = i - 1;
-            while (j >= a && s.items[j] > v) { s.items[j + 1] = s.items[j]; j--; }
-            s.items[j + 1] = v;
-        }
-    }
-    __syncthreads();
-}
-
-// Frame::GetFeaturesInArea (src/Frame.cc:440-489) + the per-candidate gates of the two SearchByProjection
-// loops that do not depend on the assignment state.  emit(idx, octave) is called in the reference's order.
-// STEREO = false: no mvuRight gate (the key-frame overload); uR / ur are then not read.
-template <bool STEREO = true, typename L, typename Emit>
-__device__ inline void walk_window(const L& s, const planar_frame_view& f, const planar_keypoint* keys, const float* uR, float x, float y,
-                                   float r, int minLevel, int maxLevel, float ur, Emit emit) {
-    const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.grid_w_inv));
-    if (nMinCellX >= PLANAR_GRID_COLS) return;
-    const int nMaxCellX = min(PLANAR_GRID_COLS - 1, (int)ceilf((x - f.min_x + r) * f.grid_w_inv));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.grid_h_inv));
-    if (nMinCellY >= PLANAR_GRID_ROWS) return;
-    const int nMaxCellY = min(PLANAR_GRID_ROWS - 1, (int)ceilf((y - f.min_y + r) * f.grid_h_inv));
-    if (nMaxCellY < 0) return;
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-        if (nMinCellY > nMaxCellY) break;
-        // cells (ix, nMinCellY..nMaxCellY) are contiguous in the column-major cell order
-        const int a = s.cell_start[ix * PLANAR_GRID_ROWS + nMinCellY], e = s.cell_start[ix * PLANAR_GRID_ROWS + nMaxCellY + 1];
-        for (int k = a; k < e; k++) {
-            const int idx = s.items[k];
-            const planar_keypoint kp = keys[idx];
-            if (bCheckLevels) {
-                if (kp.octave < minLevel) continue;
-                if (maxLevel >= 0 && kp.octave > maxLevel) continue;
-            }
-            const float distx = kp.x - x, disty = kp.y - y;
-            if (!(fabsf(distx) < r && fabsf(disty) < r)) continue;
-            if (STEREO) {
-                const float u2 = uR[idx];
-                if (u2 > 0) {
-                    const float er = fabsf(ur - u2);
-                    if (er > r) continue;
-                }
-            }
-            emit(idx, kp.octave);
-        }
-    }
-}
 
 struct Args {
     planar_frame_view f;
@@ -164,7 +50,7 @@ struct Args {
 //   MODE_FRAME: best only, TH_HIGH;  MODE_MAP: best + second with the same-level ratio test;  MODE_BOW: TH_LOW + ratio;
 //   MODE_KF: best only, ORBdist, and the match itself blocks the keypoint for later probes (src/ORBmatcher.cc:1609, :1623).
 template <int MODE>
-__device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int b, const float* from_angle, const float* to_angle_f,
+__device__ void resolve_chunk(ChunkLds& s, int m, const Args& a, int32_t* match, int b, const float* from_angle, const float* to_angle_f,
                               const planar_keypoint* keys, const uint8_t* observed) {
     const int lane = threadIdx.x;
     volatile uint32_t* blk = s.blocked;
@@ -174,13 +60,7 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
         if (id < 0 || cnt == 0) continue;
         uint32_t k1 = 0xffffffffu;
         for (int base = 0; base < cnt; base += 64) {
-            const int k = base + lane;
-            uint32_t key = 0xffffffffu;
-            if (k < cnt) {
-                const uint32_t e = s.cand[off + k];
-                const int idx = e & 0xfff;
-                if (!((blk[idx >> 5] >> (idx & 31)) & 1u)) key = ((e >> 16) << 16) | (uint32_t)k;
-            }
+            const uint32_t key = unblocked_key(s, off, cnt, base + lane, -1);
             k1 = min(k1, key);
         }
         k1 = wave_min_u32_shfl(k1);
@@ -192,13 +72,7 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
         if (MODE != MODE_FRAME && MODE != MODE_KF) {
             uint32_t k2 = 0xffffffffu;
             for (int base = 0; base < cnt; base += 64) {
-                const int k = base + lane;
-                uint32_t key = 0xffffffffu;
-                if (k < cnt && k != bestK) {
-                    const uint32_t e = s.cand[off + k];
-                    const int idx = e & 0xfff;
-                    if (!((blk[idx >> 5] >> (idx & 31)) & 1u)) key = ((e >> 16) << 16) | (uint32_t)k;
-                }
+                const uint32_t key = unblocked_key(s, off, cnt, base + lane, bestK);
                 k2 = min(k2, key);
             }
             k2 = wave_min_u32_shfl(k2);
@@ -230,69 +104,10 @@ __device__ void resolve_chunk(Lds& s, int m, const Args& a, int32_t* match, int 
     }
 }
 
-// rotation-consistency post-step shared by MODE_FRAME and MODE_BOW.  rotation_filter_ranked computes the same another way; merging them changes the
-// benchmarked MODE_FRAME instruction stream, so that is a measured change of its own.
-__device__ void rotation_filter(Lds& s, int32_t* match) {
-    const int tid = threadIdx.x;
-    if (tid < HISTO_LENGTH) s.hist[tid] = 0;
-    __syncthreads();
-    const int n = s.n_ev;
-    for (int i = tid; i < n; i += NT) atomicAdd(&s.hist[s.ev_bin[i]], 1);
-    __syncthreads();
-    if (tid == 0) {
-        int i1, i2, i3;
-        ref::three_maxima(s.hist, i1, i2, i3);
-        s.keep[0] = i1; s.keep[1] = i2; s.keep[2] = i3;
-        int removed = 0;
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != i1 && i != i2 && i != i3) removed += s.hist[i];
-        s.nmatches -= removed;
-    }
-    __syncthreads();
-    const int k1 = s.keep[0], k2 = s.keep[1], k3 = s.keep[2];
-    for (int i = tid; i < n; i += NT) {
-        const int bin = s.ev_bin[i];
-        if (bin != k1 && bin != k2 && bin != k3) match[s.ev_idx[i]] = -1;
-    }
-}
-
-// rotation_filter with ComputeThreeMaxima ranked on the lanes (MODE_KF).  Its strict-'>' insertion keeps the three largest non-empty bins in
-// stable order, which is rank < 3 under (count descending, bin ascending); the serial ind1..ind3 form lives in scratch.
-__device__ void rotation_filter_ranked(Lds& s, int32_t* match) {
-    const int tid = threadIdx.x;
-    if (tid < HISTO_LENGTH) s.hist[tid] = 0;
-    if (tid < 3) s.keep[tid] = -1;
-    __syncthreads();
-    const int n = s.n_ev;
-    for (int i = tid; i < n; i += NT) atomicAdd(&s.hist[s.ev_bin[i]], 1);
-    __syncthreads();
-    if (tid < HISTO_LENGTH && s.hist[tid] > 0) {
-        const int h = s.hist[tid];
-        int rank = 0;
-        for (int j = 0; j < HISTO_LENGTH; j++) { const int hj = s.hist[j]; rank += (hj > h || (hj == h && j < tid)) ? 1 : 0; }
-        if (rank < 3) s.keep[rank] = tid;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int i1 = s.keep[0], i2 = s.keep[1], i3 = s.keep[2];
-        const int max1 = i1 >= 0 ? s.hist[i1] : 0, max2 = i2 >= 0 ? s.hist[i2] : 0, max3 = i3 >= 0 ? s.hist[i3] : 0;
-        const bool k2 = !((float)max2 < 0.1f * (float)max1), k3 = k2 && !((float)max3 < 0.1f * (float)max1);
-        if (!k2) s.keep[1] = -1;
-        if (!k3) s.keep[2] = -1;
-        s.nmatches -= n - (max1 + (k2 ? max2 : 0) + (k3 ? max3 : 0));     // every event sits in one bin; max1..3 read 0 for a missing bin
-    }
-    __syncthreads();
-    const int k1 = s.keep[0], k2 = s.keep[1], k3 = s.keep[2];
-    for (int i = tid; i < n; i += NT) {
-        const int bin = s.ev_bin[i];
-        if (bin != k1 && bin != k2 && bin != k3) match[s.ev_idx[i]] = -1;
-    }
-}
-
 template <int MODE>
 __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
-    Lds& s = *(Lds*)lds_raw;
+    ChunkLds& s = *(ChunkLds*)lds_raw;
     const int b = blockIdx.x, tid = threadIdx.x;
     const planar_frame_view& f = a.f;
     const int N = f.n[b];
@@ -405,7 +220,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             }
         }
         int cnt = 0;
-        if (valid) walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
+        if (valid) frame_features_in_area<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
         int total;
         const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
         if (tid == 0) s.m_fit = 0;
@@ -421,7 +236,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             uint32_t d[8];
             ref::load_desc(d, probe_desc + (size_t)p * 32);
             int k = off;
-            walk_window<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int idx, int oct) {
+            frame_features_in_area<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int idx, int oct) {
                 const int dist = ref::hamming256(d, desc + (size_t)idx * 32);
                 s.cand[k++] = ((uint32_t)dist << 16) | ((uint32_t)(oct & 0xf) << 12) | (uint32_t)idx;
             });
@@ -448,30 +263,14 @@ struct BowArgs {
 };
 
 struct BowLds {
-    Lds base;
+    ChunkLds base;
     unsigned long long kkey[MAXN], fkey[MAXN];   // node << 12 | feature index, ascending
 };
-
-__device__ void bitonic_sort_u64(unsigned long long* key, int n_pow2) {
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < n_pow2; i += NT) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long x = key[i], y = key[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((x > y) == up) { key[i] = y; key[ixj] = x; }
-                }
-            }
-        }
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
     BowLds& L = *(BowLds*)lds_raw;
-    Lds& s = L.base;
+    ChunkLds& s = L.base;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int NK = g.n_kf[b], NF = g.n_f[b];
     const size_t ko = (size_t)b * g.kf_stride, fo = (size_t)b * g.f_stride;
@@ -816,7 +615,8 @@ __global__ __launch_bounds__(NT) void fuse_kernel(FuseArgs a) {
                         const float radius = a.th * f.scale_factors[lvl];
                         uint32_t d[8];
                         ref::load_desc(d, a.desc + (po + j) * 32);
-                        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678): the frame's window walk without level bounds
+                        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678): keyframe_features_in_area (match_chunk.h) written out.  Calling it with the gates
+                        // below in a lambda changes this kernel's instruction stream (two fewer spilt SGPRs among the rest): a measured change of its own.
                         const int nMinCellX = max(0, (int)floorf((u - f.min_x - radius) * f.grid_w_inv));
                         const int nMaxCellX = min(PLANAR_GRID_COLS - 1, (int)ceilf((u - f.min_x + radius) * f.grid_w_inv));
                         const int nMinCellY = max(0, (int)floorf((v - f.min_y - radius) * f.grid_h_inv));
@@ -939,8 +739,8 @@ __global__ __launch_bounds__(64) void lsd_fuse_kernel(LineFuseArgs a) {
 }
 
 static int check_view(const planar_frame_view* f) {
-    PLANAR_REQUIRE(f->B >= 1 && f->stride >= 1 && f->stride <= MAXN, PLANAR_EINVAL, "frame view: B >= 1 and 1 <= stride <= PLANAR_MAX_FRAME_KEYS required");
-    PLANAR_REQUIRE(f->n && f->keys_un && f->u_right && f->desc, PLANAR_EINVAL, "frame view: null array");
+    PLANAR_REQUIRE(frame_view_sizes_ok(f), PLANAR_EINVAL, "frame view: B >= 1 and 1 <= stride <= PLANAR_MAX_FRAME_KEYS required");
+    PLANAR_REQUIRE(frame_view_ok(f) && f->u_right, PLANAR_EINVAL, "frame view: null array");
     return PLANAR_OK;
 }
 
@@ -948,10 +748,10 @@ template <int MODE>
 static int launch_projection(planar_ctx* ctx, const Args& a) {
     static bool attr_set = false;
     if (!attr_set) {
-        PLANAR_HIP_CHECK(hipFuncSetAttribute((const void*)projection_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Lds)));
+        PLANAR_HIP_CHECK(hipFuncSetAttribute((const void*)projection_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(ChunkLds)));
         attr_set = true;
     }
-    hipLaunchKernelGGL(projection_kernel<MODE>, dim3(a.f.B), dim3(NT), sizeof(Lds), ctx->stream, a);
+    hipLaunchKernelGGL(projection_kernel<MODE>, dim3(a.f.B), dim3(NT), sizeof(ChunkLds), ctx->stream, a);
     PLANAR_HIP_CHECK(hipGetLastError());
     return PLANAR_OK;
 }
@@ -963,8 +763,6 @@ using namespace planar;
 using guided::Args;
 
 // ---- one argument check per entry-point pair: the host-pointer form calls it before it touches the device, the _dev form before it launches ----
-static bool n_levels_ok(int n) { return n >= 1 && n <= PLANAR_MAX_LEVELS; }
-
 static int check_frame_args(const void* ctx, const planar_frame_view* cur, const planar_last_frame_view* last, const void* match, const void* nmatches) {
     PLANAR_REQUIRE(ctx && cur && last && match && nmatches, PLANAR_EINVAL, "null argument");
     if (int rc = guided::check_view(cur)) return rc;

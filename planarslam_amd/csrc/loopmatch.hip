@@ -15,17 +15,13 @@
 // KeyFrame::GetFeaturesInArea order.  A second kernel, one workgroup per pair, is the agreement pass vnMatch2[vnMatch1[i1]] == i1.
 // Integer / float32 / double work on the paths of ref_arith.h, bit-exact with the reference compiled where it lies (tools/gen_golden_loop_match.py).
 #include "common.h"
+#include "match_chunk.h"
 #include "ref_arith.h"
 
 namespace planar {
 namespace loopmatch {
 
-constexpr int NT = 256;
-constexpr int NCELL = PLANAR_GRID_COLS * PLANAR_GRID_ROWS;
-constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
-constexpr int TH_HIGH = 100, TH_LOW = 50;   // src/ORBmatcher.cc:38-39
-constexpr int CAND_CAP = 8192;              // candidates of one chunk of probes
-using ref::HISTO_LENGTH;
+using namespace chunk;
 
 struct GridLds {
     uint32_t cand[NCELL];          // build_grid's counters / cursors
@@ -34,56 +30,6 @@ struct GridLds {
     uint32_t already[MAXN / 32];   // vbAlreadyMatched2 (direction 2 -> 1 only)
     int wsum[NT / 64];
 };
-
-// Frame::AssignFeaturesToGrid (src/Frame.cc:155-166, PosInGrid :526-535) into cell_start / items.  The text of guided.hip's build_grid: that file is on
-// the benchmarked path and its device code is held identical to its parent's, so the template is not moved out of it.
-template <typename L>
-__device__ void build_grid(L& s, const planar_frame_view& f, const planar_keypoint* keys, int N) {
-    const int tid = threadIdx.x;
-    uint32_t* cnt = s.cand;            // [NCELL] counters, then cursors
-    for (int c = tid; c < NCELL; c += NT) cnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < N; i += NT) {
-        const int px = (int)roundf((keys[i].x - f.min_x) * f.grid_w_inv);
-        const int py = (int)roundf((keys[i].y - f.min_y) * f.grid_h_inv);
-        if (px < 0 || px >= PLANAR_GRID_COLS || py < 0 || py >= PLANAR_GRID_ROWS) continue;
-        atomicAdd(&cnt[px * PLANAR_GRID_ROWS + py], 1u);
-    }
-    __syncthreads();
-    constexpr int PER = NCELL / NT;    // 12 consecutive cells per thread
-    int local = 0;
-    for (int k = 0; k < PER; k++) local += (int)cnt[tid * PER + k];
-    int total;
-    int run = ref::block_exscan<NT / 64>(local, s.wsum, &total);
-    for (int k = 0; k < PER; k++) {
-        const int c = tid * PER + k, n = (int)cnt[c];
-        s.cell_start[c] = (uint16_t)run;
-        cnt[c] = (uint32_t)run;        // cursor
-        run += n;
-    }
-    if (tid == NT - 1) s.cell_start[NCELL] = (uint16_t)run;
-    __syncthreads();
-    for (int i = tid; i < N; i += NT) {
-        const int px = (int)roundf((keys[i].x - f.min_x) * f.grid_w_inv);
-        const int py = (int)roundf((keys[i].y - f.min_y) * f.grid_h_inv);
-        if (px < 0 || px >= PLANAR_GRID_COLS || py < 0 || py >= PLANAR_GRID_ROWS) continue;
-        const uint32_t pos = atomicAdd(&cnt[px * PLANAR_GRID_ROWS + py], 1u);
-        s.items[pos] = (uint16_t)i;
-    }
-    __syncthreads();
-    // push_back order inside a cell is ascending keypoint index: insertion-sort each (tiny) cell list
-    for (int k = 0; k < PER; k++) {
-        const int c = tid * PER + k;
-        const int a = s.cell_start[c], e = s.cell_start[c + 1];
-        for (int i = a + 1; i < e; i++) {
-            const uint16_t v = s.items[i];
-            int j = i - 1;
-            while (j >= a && s.items[j] > v) { s.items[j + 1] = s.items[j]; j--; }
-            s.items[j + 1] = v;
-        }
-    }
-    __syncthreads();
-}
 
 struct Sim3Args {
     planar_frame_view kf1, kf2;
@@ -161,7 +107,8 @@ __global__ __launch_bounds__(NT) void sim3_search_kernel(Sim3Args a) {
                         const float radius = a.th * T.scale_factors[lvl];
                         uint32_t d[8];
                         ref::load_desc(d, mp.desc + (so + i) * 32);
-                        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678), the window walk as guided.hip's fuse_kernel writes it
+                        // KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678): keyframe_features_in_area (match_chunk.h) written out.  Calling it with a lambda
+                        // allocates this kernel's registers differently: a measured change of its own.
                         const int nMinCellX = max(0, (int)floorf((u - T.min_x - radius) * T.grid_w_inv));
                         const int nMaxCellX = min(PLANAR_GRID_COLS - 1, (int)ceilf((u - T.min_x + radius) * T.grid_w_inv));
                         const int nMinCellY = max(0, (int)floorf((v - T.min_y - radius) * T.grid_h_inv));
@@ -208,26 +155,7 @@ __global__ __launch_bounds__(NT) void sim3_agree_kernel(const int32_t* __restric
 
 
 // ---- the order-bound pair: SearchByBoW(KeyFrame*, KeyFrame*) and SearchByProjection(KeyFrame*, Scw, ...) ----------------------------------------------
-struct ChunkLds {
-    uint32_t cand[CAND_CAP];       // dist << 16 | index ; doubles as build_grid's counters
-    uint16_t cell_start[NCELL + 1];
-    uint16_t items[MAXN];
-    uint32_t blocked[MAXN / 32];
-    int pid[NT];
-    int poff[NT + 1];
-    uint16_t ev_idx[MAXN];
-    uint8_t ev_bin[MAXN];
-    int hist[HISTO_LENGTH];
-    int keep[3];
-    int n_ev, nmatches, m_fit, wsum[NT / 64];
-};
-
 static_assert(sizeof(ChunkLds) == 62120, "DESIGN.md 4.12 states the dynamic LDS of projection_scw_kernel");
-
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
 
 // guided.hip's resolve_chunk for these two: wavefront 0 resolves probes [0, m) of the chunk in order; min over (dist, list position) is the stable order of the
 // reference's `<`.  BOW: best and second best, bestDist1 < TH_LOW (strict, :602) and the float ratio test, match12[idx1] = idx2; otherwise (Scw projection)
@@ -242,16 +170,10 @@ __device__ void resolve_chunk(ChunkLds& s, int m, float nn_ratio, int check_orie
         if (id < 0 || cnt == 0) continue;
         uint32_t k1 = 0xffffffffu;
         for (int base = 0; base < cnt; base += 64) {
-            const int k = base + lane;
-            uint32_t key = 0xffffffffu;
-            if (k < cnt) {
-                const uint32_t e = s.cand[off + k];
-                const int idx = e & 0xfff;
-                if (!((blk[idx >> 5] >> (idx & 31)) & 1u)) key = ((e >> 16) << 16) | (uint32_t)k;
-            }
+            const uint32_t key = unblocked_key(s, off, cnt, base + lane, -1);
             k1 = min(k1, key);
         }
-        k1 = wave_min_u32(k1);
+        k1 = wave_min_u32_shfl(k1);
         if (k1 == 0xffffffffu) continue;
         const int bestDist = (int)(k1 >> 16), bestK = (int)(k1 & 0xffff);
         const int bestIdx = s.cand[off + bestK] & 0xfff;
@@ -259,16 +181,10 @@ __device__ void resolve_chunk(ChunkLds& s, int m, float nn_ratio, int check_orie
         if (BOW) {
             uint32_t k2 = 0xffffffffu;
             for (int base = 0; base < cnt; base += 64) {
-                const int k = base + lane;
-                uint32_t key = 0xffffffffu;
-                if (k < cnt && k != bestK) {
-                    const uint32_t e = s.cand[off + k];
-                    const int idx = e & 0xfff;
-                    if (!((blk[idx >> 5] >> (idx & 31)) & 1u)) key = ((e >> 16) << 16) | (uint32_t)k;
-                }
+                const uint32_t key = unblocked_key(s, off, cnt, base + lane, bestK);
                 k2 = min(k2, key);
             }
-            k2 = wave_min_u32(k2);
+            k2 = wave_min_u32_shfl(k2);
             const int bestDist2 = k2 != 0xffffffffu ? (int)(k2 >> 16) : 256;
             take = bestDist < TH_LOW && (float)bestDist < nn_ratio * (float)bestDist2;
         } else {
@@ -289,40 +205,6 @@ __device__ void resolve_chunk(ChunkLds& s, int m, float nn_ratio, int check_orie
     }
 }
 
-// the rotation check of :638-656, guided.hip's rotation_filter_ranked: ComputeThreeMaxima (:1666-1708) ranked on the lanes.  Its strict-'>' insertion keeps the three
-// largest non-empty bins in stable order, which is rank < 3 under (count descending, bin ascending); the serial ind1..ind3 form would live in scratch.  The removal
-// clears the match, not the key point's "matched" flag, which nothing reads afterwards.
-__device__ void rotation_filter(ChunkLds& s, int32_t* match) {
-    const int tid = threadIdx.x;
-    if (tid < HISTO_LENGTH) s.hist[tid] = 0;
-    if (tid < 3) s.keep[tid] = -1;
-    __syncthreads();
-    const int n = s.n_ev;
-    for (int i = tid; i < n; i += NT) atomicAdd(&s.hist[s.ev_bin[i]], 1);
-    __syncthreads();
-    if (tid < HISTO_LENGTH && s.hist[tid] > 0) {
-        const int h = s.hist[tid];
-        int rank = 0;
-        for (int j = 0; j < HISTO_LENGTH; j++) { const int hj = s.hist[j]; rank += (hj > h || (hj == h && j < tid)) ? 1 : 0; }
-        if (rank < 3) s.keep[rank] = tid;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int i1 = s.keep[0], i2 = s.keep[1], i3 = s.keep[2];
-        const int max1 = i1 >= 0 ? s.hist[i1] : 0, max2 = i2 >= 0 ? s.hist[i2] : 0, max3 = i3 >= 0 ? s.hist[i3] : 0;
-        const bool k2 = !((float)max2 < 0.1f * (float)max1), k3 = k2 && !((float)max3 < 0.1f * (float)max1);
-        if (!k2) s.keep[1] = -1;
-        if (!k3) s.keep[2] = -1;
-        s.nmatches -= n - (max1 + (k2 ? max2 : 0) + (k3 ? max3 : 0));     // every event sits in one bin; max1..3 read 0 for a missing bin
-    }
-    __syncthreads();
-    const int k1 = s.keep[0], k2 = s.keep[1], k3 = s.keep[2];
-    for (int i = tid; i < n; i += NT) {
-        const int bin = s.ev_bin[i];
-        if (bin != k1 && bin != k2 && bin != k3) match[s.ev_idx[i]] = -1;
-    }
-}
-
 struct BowKfArgs {
     const int32_t *n1, *node1, *n2, *node2;
     const uint8_t *usable1, *desc1, *usable2, *desc2;
@@ -338,22 +220,6 @@ struct BowKfLds {
 };
 
 static_assert(sizeof(BowKfLds) == 127656, "DESIGN.md 4.12 states the dynamic LDS of bow_kf_kernel");
-
-__device__ void bitonic_sort_u64(unsigned long long* key, int n_pow2) {
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < n_pow2; i += NT) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long x = key[i], y = key[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((x > y) == up) { key[i] = y; key[ixj] = x; }
-                }
-            }
-        }
-    __syncthreads();
-}
 
 // probes: the features of key frame 1 in (node, feature index) order; the lower_bound walk of :554-636 is the merge-join over the common nodes
 __global__ __launch_bounds__(NT) void bow_kf_kernel(BowKfArgs g) {
@@ -426,7 +292,7 @@ __global__ __launch_bounds__(NT) void bow_kf_kernel(BowKfArgs g) {
         __syncthreads();
         base += m;
     }
-    if (g.check_orientation) rotation_filter(s, match_b);
+    if (g.check_orientation) rotation_filter_ranked(s, match_b);
     __syncthreads();
     if (tid == 0) g.nmatches[b] = s.nmatches;
 }
@@ -461,26 +327,6 @@ __device__ inline bool scw_project(const planar_frame_view& f, const ref::Pose& 
     if (lvl < 0) lvl = 0; else if (lvl >= n_levels) lvl = n_levels - 1;
     radius = th * f.scale_factors[lvl];
     return true;
-}
-
-// KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:639-678) with the level gate [lvl - 1, lvl] of :384 / :1071; emit(idx) in the reference's order
-template <typename L, typename Emit>
-__device__ inline void walk_window(const L& s, const planar_frame_view& f, const planar_keypoint* keys, float u, float v, float radius, int lvl, Emit emit) {
-    const int nMinCellX = max(0, (int)floorf((u - f.min_x - radius) * f.grid_w_inv));
-    const int nMaxCellX = min(PLANAR_GRID_COLS - 1, (int)ceilf((u - f.min_x + radius) * f.grid_w_inv));
-    const int nMinCellY = max(0, (int)floorf((v - f.min_y - radius) * f.grid_h_inv));
-    const int nMaxCellY = min(PLANAR_GRID_ROWS - 1, (int)ceilf((v - f.min_y + radius) * f.grid_h_inv));
-    if (!(nMinCellX < PLANAR_GRID_COLS && nMaxCellX >= 0 && nMinCellY < PLANAR_GRID_ROWS && nMaxCellY >= 0 && nMinCellY <= nMaxCellY)) return;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-        const int c0 = s.cell_start[ix * PLANAR_GRID_ROWS + nMinCellY], c1 = s.cell_start[ix * PLANAR_GRID_ROWS + nMaxCellY + 1];
-        for (int k = c0; k < c1; k++) {
-            const int idx = s.items[k];
-            const planar_keypoint kp = keys[idx];
-            if (!(fabsf(kp.x - u) < radius && fabsf(kp.y - v) < radius)) continue;
-            if (kp.octave < lvl - 1 || kp.octave > lvl) continue;
-            emit(idx);
-        }
-    }
 }
 
 struct ScwArgs {
@@ -525,7 +371,7 @@ __global__ __launch_bounds__(NT) void projection_scw_kernel(ScwArgs a) {
         int lvl = 0;
         if (p < NP && a.pt.usable[po + p] && !(a.found && a.found[fo + p])) valid = scw_project(f, P, a.pt, po + p, a.lsf, a.n_levels, a.th, false, u, v, r, lvl);
         int cnt = 0;
-        if (valid) walk_window(s, f, keys, u, v, r, lvl, [&](int) { cnt++; });
+        if (valid) keyframe_features_in_area(s, f, keys, u, v, r, lvl, [&](int) { cnt++; });
         int total;
         const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
         if (tid == 0) s.m_fit = 0;
@@ -541,7 +387,7 @@ __global__ __launch_bounds__(NT) void projection_scw_kernel(ScwArgs a) {
             uint32_t d[8];
             ref::load_desc(d, a.pt.desc + (po + p) * 32);
             int k = off;
-            walk_window(s, f, keys, u, v, r, lvl, [&](int idx) {
+            keyframe_features_in_area(s, f, keys, u, v, r, lvl, [&](int idx) {
                 const int dist = ref::hamming256(d, kdesc + (size_t)idx * 32);
                 s.cand[k++] = ((uint32_t)dist << 16) | (uint32_t)idx;
             });
@@ -585,7 +431,7 @@ __global__ __launch_bounds__(NT) void fuse_scw_kernel(ScwArgs a) {
         if (a.pt.usable[oo + j] && scw_project(f, P, a.pt, po + j, a.lsf, a.n_levels, a.th, true, u, v, r, lvl)) {
             uint32_t d[8];
             ref::load_desc(d, a.pt.desc + (po + j) * 32);
-            walk_window(s, f, keys, u, v, r, lvl, [&](int idx) {
+            keyframe_features_in_area(s, f, keys, u, v, r, lvl, [&](int idx) {
                 const int dist = ref::hamming256(d, kdesc + (size_t)idx * 32);
                 if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
             });
@@ -612,18 +458,14 @@ __global__ __launch_bounds__(NT) void fuse_scw_kernel(ScwArgs a) {
 
 using namespace planar;
 
-static bool view_ok(const planar_frame_view* f) {
-    return f->B >= 1 && f->stride >= 1 && f->stride <= loopmatch::MAXN && f->n && f->keys_un && f->desc && f->Tcw;
-}
 static int check_sim3_args(const void* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, float lsf1, int n_levels1, const planar_frame_view* kf2,
                            const planar_kf_points* mp2, float lsf2, int n_levels2, bool arrays) {
     PLANAR_REQUIRE(ctx && kf1 && mp1 && kf2 && mp2 && arrays, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(view_ok(kf1) && view_ok(kf2) && kf1->B == kf2->B, PLANAR_EINVAL,
+    PLANAR_REQUIRE(frame_view_ok(kf1) && kf1->Tcw && frame_view_ok(kf2) && kf2->Tcw && kf1->B == kf2->B, PLANAR_EINVAL,
                    "key-frame views: the same B >= 1, 1 <= stride <= PLANAR_MAX_FRAME_KEYS, n, keys_un, desc and Tcw required");
     PLANAR_REQUIRE(mp1->usable && mp1->xw && mp1->min_dist && mp1->max_dist && mp1->desc && mp2->usable && mp2->xw && mp2->min_dist && mp2->max_dist && mp2->desc,
                    PLANAR_EINVAL, "null array in the map points");
-    PLANAR_REQUIRE(n_levels1 >= 1 && n_levels1 <= PLANAR_MAX_LEVELS && n_levels2 >= 1 && n_levels2 <= PLANAR_MAX_LEVELS, PLANAR_EINVAL,
-                   "1 <= n_levels <= PLANAR_MAX_LEVELS required");
+    PLANAR_REQUIRE(n_levels_ok(n_levels1) && n_levels_ok(n_levels2), PLANAR_EINVAL, "1 <= n_levels <= PLANAR_MAX_LEVELS required");
     PLANAR_REQUIRE(lsf1 != 0.0f && lsf2 != 0.0f, PLANAR_EINVAL, "log_scale_factor == 0");
     return PLANAR_OK;
 }
@@ -635,8 +477,6 @@ static void stage_kf(Stager& s, planar_frame_view& d, planar_kf_points& p) {
     s.in_field(p.usable, n); s.in_field(p.xw, n * 3); s.in_field(p.min_dist, n); s.in_field(p.max_dist, n); s.in_field(p.desc, n * 32);
 }
 
-static bool levels_ok(int n) { return n >= 1 && n <= PLANAR_MAX_LEVELS; }
-
 static int check_bow_kf_args(const void* ctx, int B, int stride1, int stride2, bool arrays) {
     PLANAR_REQUIRE(ctx && arrays, PLANAR_EINVAL, "null argument");
     PLANAR_REQUIRE(B >= 1 && stride1 >= 1 && stride1 <= loopmatch::MAXN && stride2 >= 1 && stride2 <= loopmatch::MAXN, PLANAR_EINVAL,
@@ -645,9 +485,9 @@ static int check_bow_kf_args(const void* ctx, int B, int stride1, int stride2, b
 }
 static int check_scw_args(const void* ctx, const planar_frame_view* kf, int n_levels, float lsf, int stride, bool arrays) {
     PLANAR_REQUIRE(ctx && kf && arrays, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(kf->B >= 1 && kf->stride >= 1 && kf->stride <= loopmatch::MAXN && kf->n && kf->keys_un && kf->desc, PLANAR_EINVAL,
+    PLANAR_REQUIRE(frame_view_ok(kf), PLANAR_EINVAL,
                    "key-frame view: B >= 1, 1 <= stride <= PLANAR_MAX_FRAME_KEYS, n, keys_un and desc required");
-    PLANAR_REQUIRE(stride >= 1 && levels_ok(n_levels) && lsf != 0.0f, PLANAR_EINVAL, "stride >= 1, 1 <= n_levels <= PLANAR_MAX_LEVELS and log_scale_factor != 0 required");
+    PLANAR_REQUIRE(stride >= 1 && n_levels_ok(n_levels) && lsf != 0.0f, PLANAR_EINVAL, "stride >= 1, 1 <= n_levels <= PLANAR_MAX_LEVELS and log_scale_factor != 0 required");
     return PLANAR_OK;
 }
 static void stage_scw_view(Stager& s, planar_frame_view& d, bool with_blocked) {
