@@ -815,6 +815,9 @@ typedef struct planar_ba_result {
  * stop_flag (or NULL) is the reference's `bool* pbStopFlag` (one byte; the host samples it when LM steps are enqueued - with a flag at most two steps per chunk, so
  * a flag raised while the GPU is solving is seen at most two LM steps later - and once more between optimize(its1) and optimize(its2), as the reference's bDoMore
  * does; with several ranks every decision is taken on the all-reduced value).  comm may be NULL (single GPU).  Synchronous.
+ * With the flag already up on entry nothing is optimised (lm_iterations == 0, stopped == 1): the poses and landmarks come back as given (poses through a quaternion,
+ * planes normalised) and e_outlier holds the verdicts of :2471-2575 on the errors of that entry estimate, computed once.  (The reference leaves these verdicts
+ * undefined there: with the flag up g2o never calls computeActiveErrors.)
  * Non-fixed key frames: any number up to 128 (PLANAR_ECAPACITY above); up to 20 the reduced camera system stays in LDS, above that it is accumulated and
  * factorised in global memory (slower per LM step, same results): Optimizer::LocalBundleAdjustment has no cap on the covisible key frames. */
 int planar_local_ba(planar_ctx* ctx, const planar_ba_problem* problem, const planar_pose_params* params, int its1, int its2,

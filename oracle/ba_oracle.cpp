@@ -49,6 +49,7 @@ struct BA {
     std::vector<Edge> edges;
     std::vector<int> active;
     int lm_iters = 0;
+    std::vector<int> trials;                      // LM trials (1 + rejected ones) of every iteration, both optimize() calls in order
 
     void error(Edge& e, const State& s) const {
         const SE3& T = s.T[e.kf];
@@ -296,6 +297,7 @@ struct BA {
                 } else { lambda *= ni; ni *= 2; st = backup; }
                 qmax++;
             } while (rho < 0 && qmax < 10);
+            trials.push_back(qmax);
             if (std::getenv("ORC_BA_TRACE")) std::fprintf(stderr, "oracle it %d chi2 %.6f lambda %.6f trials %d edges %zu\n", it, currentChi, lambda, qmax, active.size());
             if (qmax == 10 || rho == 0) break;
             if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
@@ -380,18 +382,24 @@ int orc_ba_reduced_system(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed
 // Flat layout == include/planar_abi.h planar_ba_problem.  e_meas: [n_edges][4] = (u, v, ur, -) | line (a, b, c, -) | plane coefficients.
 // Outputs: kf_out [n_kf][16] float32, lm_out [n_lm][4] double (xyz,0 | plane coefficients), e_outlier [n_edges] = the reference's
 // "to erase" lists (:2471-2575); returns total LM iterations.
-int orc_local_ba(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_lm, const uint8_t* lm_type, const double* lm_init,
-                 int n_edges, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* e_type, const double* e_meas,
-                 const float* e_inv_sigma2, const orc::PoseParams* prm, int its1, int its2, float* kf_out, double* lm_out,
-                 uint8_t* e_outlier, double* chi2_out) {
+// trials_out (or null): [its1 + its2] the number of LM trials of each iteration run (1 = the first trial was accepted), n_first_out: how
+// many of them belong to optimize(its1).
+// entry_only: no optimisation; the errors of the entry estimate are computed once and classified as :2471-2575 do.  This is what the
+// device returns when the stop flag is up on entry.  (The reference leaves these flags undefined there: g2o never calls computeActiveErrors.)
+static int local_ba_core(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_lm, const uint8_t* lm_type, const double* lm_init,
+                         int n_edges, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* e_type, const double* e_meas,
+                         const float* e_inv_sigma2, const orc::PoseParams* prm, int its1, int its2, float* kf_out, double* lm_out,
+                         uint8_t* e_outlier, double* chi2_out, int32_t* trials_out, int32_t* n_first_out, bool entry_only) {
     using namespace orc;
     using namespace orc::geom;
     BA ba;
     ba_setup(ba, n_kf, kf_Tcw, kf_fixed, n_lm, lm_type, lm_init, n_edges, e_kf, e_lm, e_type, e_meas, e_inv_sigma2, prm);
     auto thr = [&](const Edge& e) { return e.type == BE_MONO ? 5.991 : (e.type <= BE_LINE ? 7.815 : (e.type == BE_PLANE ? prm->plane_chi : prm->vp_chi)); };
     auto depth_ok = [&](const Edge& e) { return e.type > BE_STEREO || se3_map(ba.st.T[e.kf], ba.st.lm[e.lm].X).z > 0.0; };
+    if (entry_only) { ba.compute_active_errors(); its1 = its2 = 0; }
     ba.optimize(its1);                                            // :2355
-    for (size_t k = 0; k < ba.edges.size(); k++) {                // :2363-2462
+    if (n_first_out) *n_first_out = (int32_t)ba.trials.size();
+    for (size_t k = 0; k < ba.edges.size() && !entry_only; k++) { // :2363-2462
         Edge& e = ba.edges[k];
         bool bad = BA::chi2(e) > thr(e) || !depth_ok(e);
         if (e.type == BE_LINE) {   // start/end edges of a line are consecutive and share their fate (:2399-2412)
@@ -431,6 +439,28 @@ int orc_local_ba(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_l
         else for (int i = 0; i < 4; i++) lm_out[4 * l + i] = L.P.c[i];
     }
     if (chi2_out) { ba.compute_active_errors(); *chi2_out = ba.active_robust_chi2(); }
+    if (trials_out) for (size_t i = 0; i < ba.trials.size(); i++) trials_out[i] = ba.trials[i];
     return ba.lm_iters;
+}
+
+int orc_local_ba(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_lm, const uint8_t* lm_type, const double* lm_init,
+                 int n_edges, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* e_type, const double* e_meas,
+                 const float* e_inv_sigma2, const orc::PoseParams* prm, int its1, int its2, float* kf_out, double* lm_out,
+                 uint8_t* e_outlier, double* chi2_out) {
+    return local_ba_core(n_kf, kf_Tcw, kf_fixed, n_lm, lm_type, lm_init, n_edges, e_kf, e_lm, e_type, e_meas, e_inv_sigma2, prm, its1, its2,
+                         kf_out, lm_out, e_outlier, chi2_out, nullptr, nullptr, false);
+}
+int orc_local_ba_trials(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_lm, const uint8_t* lm_type, const double* lm_init,
+                        int n_edges, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* e_type, const double* e_meas,
+                        const float* e_inv_sigma2, const orc::PoseParams* prm, int its1, int its2, float* kf_out, double* lm_out,
+                        uint8_t* e_outlier, double* chi2_out, int32_t* trials_out, int32_t* n_first_out) {
+    return local_ba_core(n_kf, kf_Tcw, kf_fixed, n_lm, lm_type, lm_init, n_edges, e_kf, e_lm, e_type, e_meas, e_inv_sigma2, prm, its1, its2,
+                         kf_out, lm_out, e_outlier, chi2_out, trials_out, n_first_out, false);
+}
+int orc_local_ba_entry(int n_kf, const float* kf_Tcw, const uint8_t* kf_fixed, int n_lm, const uint8_t* lm_type, const double* lm_init,
+                       int n_edges, const int32_t* e_kf, const int32_t* e_lm, const uint8_t* e_type, const double* e_meas,
+                       const float* e_inv_sigma2, const orc::PoseParams* prm, float* kf_out, double* lm_out, uint8_t* e_outlier) {
+    return local_ba_core(n_kf, kf_Tcw, kf_fixed, n_lm, lm_type, lm_init, n_edges, e_kf, e_lm, e_type, e_meas, e_inv_sigma2, prm, 0, 0,
+                         kf_out, lm_out, e_outlier, nullptr, nullptr, nullptr, true);
 }
 }

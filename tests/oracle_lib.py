@@ -239,19 +239,38 @@ def peac_run(depth: np.ndarray, fx=535.4, fy=539.2, cx=320.1, cy=247.6, factor=1
     return planes[:min(n, max_planes)].copy(), labels
 
 
-def local_ba(prob, params, its1=5, its2=10):
-    """CPU oracle of the numerical core of Optimizer::LocalBundleAdjustment on a synth.ba_problem()."""
-    L = lib()
-    K, NL, NE = len(prob["kf_fixed"]), len(prob["lm_type"]), len(prob["e_kf"])
+def _ba_call_args(prob, params):
+    a = {k: np.ascontiguousarray(prob[k]) for k in ("kf_Tcw", "kf_fixed", "lm_type", "lm_init", "e_kf", "e_lm", "e_type", "e_meas", "e_inv_sigma2")}
+    K, NL, NE = len(a["kf_fixed"]), len(a["lm_type"]), len(a["e_kf"])
     res = dict(kf_Tcw=np.zeros((K, 16), np.float32), lm=np.zeros((NL, 4), np.float64), e_outlier=np.zeros(NE, np.uint8))
-    chi = C.c_double()
     prm = pose_params(params)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    L.orc_local_ba.restype = C.c_int
-    res["lm_iters"] = L.orc_local_ba(C.c_int(K), p(prob["kf_Tcw"]), p(prob["kf_fixed"]), C.c_int(NL), p(prob["lm_type"]), p(prob["lm_init"]), C.c_int(NE),
-                                     p(prob["e_kf"]), p(prob["e_lm"]), p(prob["e_type"]), p(prob["e_meas"]), p(prob["e_inv_sigma2"]), C.byref(prm),
-                                     C.c_int(its1), C.c_int(its2), p(res["kf_Tcw"]), p(res["lm"]), p(res["e_outlier"]), C.byref(chi))
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    head = (C.c_int(K), p(a["kf_Tcw"]), p(a["kf_fixed"]), C.c_int(NL), p(a["lm_type"]), p(a["lm_init"]), C.c_int(NE), p(a["e_kf"]), p(a["e_lm"]),
+            p(a["e_type"]), p(a["e_meas"]), p(a["e_inv_sigma2"]), C.byref(prm))
+    return a, prm, res, head, (p(res["kf_Tcw"]), p(res["lm"]), p(res["e_outlier"]))
+
+
+def local_ba(prob, params, its1=5, its2=10):
+    """CPU oracle of the numerical core of Optimizer::LocalBundleAdjustment on a synth.ba_problem().
+    'trials': LM trials of every iteration run (1 = first trial accepted), 'trials_first' of them belong to optimize(its1)."""
+    L = lib()
+    keep, prm, res, head, outs = _ba_call_args(prob, params)
+    chi = C.c_double()
+    trials = np.zeros(max(its1 + its2, 1), np.int32); nfirst = C.c_int32()
+    L.orc_local_ba_trials.restype = C.c_int
+    res["lm_iters"] = L.orc_local_ba_trials(*head, C.c_int(its1), C.c_int(its2), *outs, C.byref(chi), trials.ctypes.data_as(C.c_void_p), C.byref(nfirst))
     res["chi2"] = chi.value
+    res["trials"], res["trials_first"] = trials[:res["lm_iters"]].copy(), int(nfirst.value)
+    return res
+
+
+def local_ba_entry(prob, params):
+    """The entry estimate as planar_local_ba returns it when the stop flag is up on entry: poses through a quaternion and back, normalised
+    landmarks, and the erase flags of :2471-2575 on errors computed once (no optimisation)."""
+    L = lib()
+    keep, prm, res, head, outs = _ba_call_args(prob, params)
+    L.orc_local_ba_entry.restype = C.c_int
+    L.orc_local_ba_entry(*head, *outs)
     return res
 
 

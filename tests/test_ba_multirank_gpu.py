@@ -23,11 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKER = textwrap.dedent('''
     import json, os, sys
-    sys.path.insert(0, %r)
+    sys.path.insert(0, %r); sys.path.insert(0, %r)
     import numpy as np, torch, torch.distributed as dist
     from planarslam_amd import Communicator, Context, HostedCommunicator, local_bundle_adjustment, shard_problem
     from planarslam_amd.synth import TUM3, ba_problem
-    transport, stop_rank = sys.argv[1], int(sys.argv[2])
+    transport, stop_rank, case = sys.argv[1], int(sys.argv[2]), sys.argv[3]
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dist.init_process_group("gloo")
     dev = rank if transport == "rccl" else 0
@@ -38,7 +38,11 @@ WORKER = textwrap.dedent('''
         comm = Communicator(ctx, box[0], world, rank)
     else:
         comm = HostedCommunicator.torch(ctx)
-    prob = ba_problem(seed=5, n_points=300, n_lines=60, n_planes=12)
+    if case:                                 # a case of opt_cases.BA_REGIME_CASES (rejected LM trials: every rank must reject the same ones)
+        import opt_cases
+        prob = opt_cases.BA_REGIME_CASES[case][0]()
+    else:
+        prob = ba_problem(seed=5, n_points=300, n_lines=60, n_planes=12)
     sh = shard_problem(prob, rank, world)
     stop = None
     if stop_rank >= 0:                       # only ONE rank's caller raises the flag: the others must still leave the loop with it
@@ -53,17 +57,17 @@ WORKER = textwrap.dedent('''
     print("RESULT " + json.dumps(out))
     comm.close()
     dist.destroy_process_group()
-''') % ROOT
+''') % (ROOT, os.path.join(ROOT, "tests"))
 
 
-def _run(tmp_path, world, transport, stop_rank=-1):
+def _run(tmp_path, world, transport, stop_rank=-1, case=""):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     script = tmp_path / "w.py"
     script.write_text(WORKER)
     procs = []
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script), transport, str(stop_rank)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+        procs.append(subprocess.Popen([sys.executable, str(script), transport, str(stop_rank), case], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
         try:
@@ -90,6 +94,18 @@ def _check(outs):
 @pytest.mark.parametrize("world", [2, 3])
 def test_partitioned_ba_hosted_transport_processes_share_one_gpu(tmp_path, world):
     _check(_run(tmp_path, world, "hosted"))
+
+
+def test_partitioned_ba_rejects_the_same_trials_on_every_rank(tmp_path):
+    """reject_robust (a trial rejected twice in the robust optimisation) on two ranks: the restore and the retry on the kept linearisation are taken from
+    the all-reduced gain ratio, so both ranks take them, and end where the single-GPU solve ends, after as many LM iterations."""
+    import oracle_lib as ol
+    import opt_cases
+    from planarslam_amd.synth import TUM3
+    outs = _run(tmp_path, 2, "hosted", case="reject_robust")
+    _check(outs)
+    want = ol.local_ba(opt_cases.BA_REGIME_CASES["reject_robust"][0](), TUM3)
+    assert want["trials"].max() > 1 and len({d["lm_iters"] for d in outs}) == 1 and abs(outs[0]["full_iters"] - want["lm_iters"]) <= 1
 
 
 def test_stop_flag_raised_on_one_rank_stops_all_ranks(tmp_path):

@@ -1,4 +1,4 @@
-"""Generate tests/golden/opt_ref.npz from the REAL reference optimiser: oracle/_ref/ref_opt = src/Optimizer.cc + src/Converter.cc + the
+"""Generate tests/golden/opt_ref.npz and tests/golden/opt_ba_regimes.npz (argument "ref" or "regimes": only that file) from the REAL reference optimiser: oracle/_ref/ref_opt = src/Optimizer.cc + src/Converter.cc + the
 vendored g2o + g2oAddition/*.h + include/EdgeLine.h compiled where they lie (recipe: oracle/Makefile).  Inputs are regenerated from seeds
 (tests/opt_cases.py); only the reference's outputs are stored."""
 import os
@@ -12,6 +12,28 @@ import oracle_lib as O  # noqa: E402
 import opt_cases as cases  # noqa: E402
 from planarslam_amd import synth  # noqa: E402
 
+which = sys.argv[1:] or ["ref", "regimes"]
+
+
+def save(fname, arrays):
+    path = os.path.join(ROOT, "tests", "golden", fname)
+    np.savez_compressed(path, **arrays)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(arrays), "arrays")
+
+
+def ba_outputs(out, table):
+    for name, (build, cur) in table.items():
+        pr = build()
+        r = O.run_ref_local_ba(pr, synth.TUM3, cur)
+        out[f"ba/{name}/kf_Tcw"] = r["kf_Tcw"]; out[f"ba/{name}/lm"] = r["lm"]; out[f"ba/{name}/e_outlier"] = np.packbits(r["e_outlier"])
+
+
+if "regimes" in which:
+    out = {}
+    ba_outputs(out, cases.BA_REGIME_CASES)
+    save("opt_ba_regimes.npz", out)
+if "ref" not in which:
+    sys.exit(0)
 out = {}
 for name, (build, modes) in cases.POSE_CASES.items():
     b = build()
@@ -21,13 +43,8 @@ for name, (build, modes) in cases.POSE_CASES.items():
             out[f"pose/{name}/{mode}/{k}"] = r[k]
         for k in ("pt_outlier", "ln_outlier", "pl_outlier"):
             out[f"pose/{name}/{mode}/{k}"] = np.packbits(r[k])
-for name, (build, cur) in cases.BA_CASES.items():
-    pr = build()
-    r = O.run_ref_local_ba(pr, synth.TUM3, cur)
-    out[f"ba/{name}/kf_Tcw"] = r["kf_Tcw"]; out[f"ba/{name}/lm"] = r["lm"]; out[f"ba/{name}/e_outlier"] = np.packbits(r["e_outlier"])
+ba_outputs(out, cases.BA_CASES)
 n, seed = cases.EDGE_CASES
 e, H = O.run_ref_edges(O._edge_cases(n, seed), synth.TUM3)
 out["edges/rec"] = e; out["edges/H"] = H
-path = os.path.join(ROOT, "tests", "golden", "opt_ref.npz")
-np.savez_compressed(path, **out)
-print("wrote", path, os.path.getsize(path), "bytes,", len(out), "arrays")
+save("opt_ref.npz", out)
