@@ -16,9 +16,13 @@
 //     (Frame::GetFeaturesInArea order: column-major cells, ascending keypoint index inside a cell), level /
 //     window / stereo gates and the 256-bit Hamming distance of every surviving candidate.  Candidates of a
 //     chunk of up to 256 consecutive probes are packed (dist | octave | index) into an LDS list;
-//   * order-bound, one wavefront: for each probe in order, lanes read its candidate list, drop the ones whose
-//     "blocked" bit is set NOW, take best / second best by a wave-wide min over (dist, list position) — the
-//     stable order the reference's `<` comparisons induce — and update the blocked bits.
+//   * order-bound: a probe's outcome is a function of the "blocked" bits on its own candidate list NOW, and best / second best are the minimum over
+//     (dist, list position) — the stable order the reference's `<` comparisons induce.  Two resolvers compute it:
+//       - resolve_chunk_spec, all 256 threads, a thread per probe, in rounds (the scheme and its proof stand at the function): every
+//         uncommitted probe scans its own list under the committed blocked bits and claims what it would take; the probes before the first one whose
+//         best (or second best) entry an earlier probe claimed commit together; the next round starts at that probe;
+//       - resolve_chunk, one wavefront, probe after probe with a wave-wide minimum per probe: for chunks with a list longer than SPEC_MAX_LIST, or whose
+//         lists leave no room for the claim table behind them.
 // The chunk size adapts to the LDS list capacity, so there is no overflow path.  One workgroup per frame
 // (pair); the batch dimension fills the GPU.  Integer / float32 work, bit-exact with the oracle.
 #include "common.h"
@@ -32,6 +36,29 @@ using namespace chunk;
 using ref::Pose;
 
 enum { MODE_FRAME = 0, MODE_MAP = 1, MODE_BOW = 2, MODE_KF = 3 };
+
+// -DPLANAR_GUIDED_SPLIT (make split; never the product): thread 0 of every frame adds the wall_clock64 ticks between the kernel's barriers to per-mode sums,
+// which tools/guided_split.py reads through planar_guided_split_read.
+enum { SPLIT_GRID = 0, SPLIT_COUNT, SPLIT_FILL, SPLIT_RESOLVE, SPLIT_ROTATION, SPLIT_FRAMES, SPLIT_CHUNKS, SPLIT_ROUNDS, SPLIT_SERIAL_CHUNKS, SPLIT_N };
+#ifdef PLANAR_GUIDED_SPLIT
+__device__ unsigned long long g_split[4][SPLIT_N];
+struct SplitClock {
+    unsigned long long t, acc[SPLIT_N] = {};
+    __device__ SplitClock() : t(wall_clock64()) {}
+    __device__ void mark(int bucket) { const unsigned long long n = wall_clock64(); acc[bucket] += n - t; t = n; }
+    __device__ void add(int bucket, int v) { acc[bucket] += (unsigned long long)v; }
+    __device__ void flush(int mode) {
+        if (threadIdx.x == 0)
+            for (int i = 0; i < SPLIT_N; i++) atomicAdd(&g_split[mode][i], acc[i]);
+    }
+};
+#else
+struct SplitClock {
+    __device__ void mark(int) {}
+    __device__ void add(int, int) {}
+    __device__ void flush(int) {}
+};
+#endif
 
 struct Args {
     planar_frame_view f;
@@ -104,6 +131,93 @@ __device__ void resolve_chunk(ChunkLds& s, int m, const Args& a, int32_t* match,
     }
 }
 
+// Order-bound part, a thread per probe of the chunk, in rounds.  Entering a round, the probes below `start` are committed: match, blocked bits, nmatches and
+// events are what the sequential pass leaves after them.
+//   1. speculate: every probe q in [start, m) scans its own list under these blocked bits, applies the mode's take rule and, if it takes key point x, lowers
+//      claim[x] to q (an LDS atomicMin; the table lies behind the chunk's lists in s.cand and holds 0xffffffff between rounds);
+//   2. verify: q is in conflict if a key point its outcome was read from is claimed by a probe before q.  c = the first probe in conflict, m if none;
+//   3. commit [start, c), clear the claims, go on at c.
+// The baseline rule (SPEC_WHOLE_LIST) reads the outcome from the whole list: q rescans it, blocked entries too, and any claim below q is a conflict.
+// Proof, by induction over q in [start, c): the sequential pass resolves q under the blocked bits left by the probes before q.  Those below start are
+// committed.  Those in [start, q) resolve, by the induction hypothesis, as they speculated, so each changes at most the bit of the key point it claimed; q is not
+// in conflict, so none of these lies on q's list, and a probe's outcome reads the bits of its own list only: q resolves as it speculated.  Two probes of
+// [start, c) never take the same key point (the later one would find the earlier one's claim on its list, where its own best is), so their commits touch
+// distinct match entries and distinct bits and may run in any order.  The probe at `start` has no earlier probe in the round, so c > start and every round commits.
+// The rule in use reads less: the best entry where the mode takes by the best alone (FRAME, KF), the best and the second best where the ratio test reads both
+// (MAP, BOW).  Proof of the step: a take only sets bits (below), so the probes of [start, q) can only remove entries from q's unblocked set U, and only the
+// ones they claimed.  Best and second best are the two smallest keys of U.  If neither is claimed below q they stay in U, and the two smallest of a subset that
+// keeps them are the same two; a missing second best stays missing, an empty U stays empty.  So the outcome, a function of these two, is unchanged.  In the
+// best-only modes the same holds with the best alone, and a probe that does not take never conflicts: its best is above the threshold or missing, and the
+// smallest key of a subset of U is no smaller.
+// A take leaves the key point's bit set for an observed probe and, for an unobserved one, as it was: the probe took it, so the bit was clear, and the
+// sequential pass's "clear" writes what is there.  nmatches is a count, and both rotation filters read the multiset of events, not their order.
+template <int MODE>
+__device__ int resolve_chunk_spec(ChunkLds& s, int m, int nkeys, const Args& a, int32_t* match, const float* from_angle, const float* to_angle_f,
+                                  const planar_keypoint* keys, const uint8_t* observed) {
+    const int q = threadIdx.x;
+    uint32_t* const claim = spec_claims(s, nkeys);
+    const int id = q < m ? s.pid[q] : -1;
+    const int off = s.poff[q], cnt = id >= 0 ? s.poff[q + 1] - off : 0;
+    bool open = cnt > 0;                                                  // not yet committed, and with something to resolve
+    int rounds = 0;
+    for (int start = 0; start < m; rounds++) {
+        if (q == 0) s.m_fit = m;                                          // the chunk's size is in every thread's m by now: the field holds c
+        bool take = false;
+        int bestIdx = -1, secondIdx = -1;
+        if (open) {
+            uint32_t k1, k2;
+            spec_scan<MODE != MODE_FRAME && MODE != MODE_KF>(s, off, cnt, k1, k2);
+            if (k1 != 0xffffffffu) {
+                const int bestDist = (int)(k1 >> 16);
+                const uint32_t e1 = s.cand[off + (k1 & 0xffff)];
+                const int bestLevel = (e1 >> 12) & 0xf;
+                bestIdx = e1 & 0xfff;
+                int bestDist2 = 256, bestLevel2 = -1;
+                if (k2 != 0xffffffffu) {
+                    const uint32_t e2 = s.cand[off + (k2 & 0xffff)];
+                    bestDist2 = (int)(k2 >> 16);
+                    bestLevel2 = (e2 >> 12) & 0xf;
+                    secondIdx = e2 & 0xfff;
+                }
+                if (MODE == MODE_FRAME) take = bestDist <= TH_HIGH;
+                else if (MODE == MODE_MAP) take = bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > a.nn_ratio * (float)bestDist2);
+                else if (MODE == MODE_KF) take = bestDist <= a.orb_dist;
+                else take = bestDist <= TH_LOW && (float)bestDist < a.nn_ratio * (float)bestDist2;
+                if (take) atomicMin(&claim[bestIdx], (uint32_t)q);
+            }
+        }
+        __syncthreads();
+        if (open) {
+            bool conflict;
+            if (SPEC_WHOLE_LIST) conflict = spec_conflict(s, claim, off, cnt, q);
+            else if (MODE == MODE_FRAME || MODE == MODE_KF) conflict = take && claim[bestIdx] < (uint32_t)q;
+            else conflict = (bestIdx >= 0 && claim[bestIdx] < (uint32_t)q) || (secondIdx >= 0 && claim[secondIdx] < (uint32_t)q);
+            if (conflict) atomicMin(&s.m_fit, q);
+        }
+        __syncthreads();
+        const int c = s.m_fit;
+        if (take) claim[bestIdx] = 0xffffffffu;
+        if (open && q < c) {
+            open = false;
+            if (take) {
+                match[bestIdx] = id;
+                const bool now_blocked = (MODE == MODE_BOW || MODE == MODE_KF) ? true : (observed[id] != 0);
+                if (now_blocked) atomicOr(&s.blocked[bestIdx >> 5], 1u << (bestIdx & 31));
+                atomicAdd(&s.nmatches, 1);
+                if (MODE != MODE_MAP && a.check_orientation) {
+                    const float to = MODE == MODE_BOW ? to_angle_f[bestIdx] : keys[bestIdx].angle;
+                    const int n = atomicAdd(&s.n_ev, 1);
+                    s.ev_idx[n] = (uint16_t)bestIdx;
+                    s.ev_bin[n] = (uint8_t)ref::rot_bin(from_angle[id], to);
+                }
+            }
+        }
+        __syncthreads();
+        start = c;
+    }
+    return rounds;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
@@ -116,6 +230,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     const uint8_t* desc = f.desc + (size_t)b * f.stride * 32;
     int32_t* const match_b = a.match + (size_t)b * f.stride;     // (the by-value argument struct is never written: a modified copy would live in scratch)
 
+    SplitClock clk;
     for (int w = tid; w < MAXN / 32; w += NT) s.blocked[w] = 0;
     if (tid == 0) { s.n_ev = 0; s.nmatches = 0; }
     build_grid(s, f, keys, N);
@@ -155,6 +270,7 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
     }
     const bool bFactor = a.th != 1.0f;
     __syncthreads();
+    clk.mark(SPLIT_GRID);
 
     for (int base = 0; base < NP;) {
         // ---- order-free: parameters of probe base + tid
@@ -223,15 +339,20 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
         if (valid) frame_features_in_area<MODE != MODE_KF>(s, f, keys, uR, u, v, r, minL, maxL, ur, [&](int, int) { cnt++; });
         int total;
         const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
-        if (tid == 0) s.m_fit = 0;
+        if (tid == 0) { s.m_fit = 0; s.keep[0] = 0; }
         __syncthreads();
         const bool fits = p < NP && off + cnt <= CAND_CAP;
         if (fits) atomicAdd(&s.m_fit, 1);   // prefix property: fits is monotone in tid
+        if (fits && cnt > SPEC_MAX_LIST) s.keep[0] = 1;
         s.pid[tid] = valid ? p : -1;
         s.poff[tid] = off;
         if (tid == NT - 1) s.poff[NT] = total;
         __syncthreads();
         const int m = s.m_fit;
+        const bool spec = s.keep[0] == 0 && spec_room(s, m, N);
+        clk.mark(SPLIT_COUNT);
+        if (spec)
+            for (int i = tid; i < N; i += NT) spec_claims(s, N)[i] = 0xffffffffu;
         if (fits && valid && cnt > 0) {
             uint32_t d[8];
             ref::load_desc(d, probe_desc + (size_t)p * 32);
@@ -242,16 +363,24 @@ __global__ __launch_bounds__(NT) void projection_kernel(Args a) {
             });
         }
         __syncthreads();
+        clk.mark(SPLIT_FILL);
         // ---- order-bound
         const float* from_angle = MODE == MODE_FRAME ? a.last.angle + po : MODE == MODE_KF ? a.kf.angle + po : nullptr;
-        if (tid < 64) resolve_chunk<MODE>(s, m, a, match_b, b, from_angle, nullptr, keys, observed);
+        if (spec) clk.add(SPLIT_ROUNDS, resolve_chunk_spec<MODE>(s, m, N, a, match_b, from_angle, nullptr, keys, observed));
+        else if (tid < 64) resolve_chunk<MODE>(s, m, a, match_b, b, from_angle, nullptr, keys, observed);
         __syncthreads();
+        clk.mark(SPLIT_RESOLVE);
+        clk.add(SPLIT_CHUNKS, 1);
+        clk.add(SPLIT_SERIAL_CHUNKS, spec ? 0 : 1);
         base += m;
     }
     if (MODE == MODE_FRAME && a.check_orientation) rotation_filter(s, match_b);
     if (MODE == MODE_KF && a.check_orientation) rotation_filter_ranked(s, match_b);
     __syncthreads();
     if (tid == 0) a.nmatches[b] = s.nmatches;
+    clk.mark(SPLIT_ROTATION);
+    clk.add(SPLIT_FRAMES, 1);
+    clk.flush(MODE);
 }
 
 // ---- a22: SearchByBoW -----------------------------------------------------------------------------
@@ -266,6 +395,11 @@ struct BowLds {
     ChunkLds base;
     unsigned long long kkey[MAXN], fkey[MAXN];   // node << 12 | feature index, ascending
 };
+
+// the dynamic LDS of projection_kernel / bow_kernel: two workgroups of the former per CU (160 KB).  The speculating resolver's claim table and its two flags live
+// in fields the chunk does not use meanwhile, so neither struct grew with it (tests/test_guided_resources.py).
+static_assert(sizeof(ChunkLds) == 62120, "projection_kernel: two workgroups per CU");
+static_assert(sizeof(BowLds) == 127656, "bow_kernel: one workgroup per CU");
 
 __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
     extern __shared__ __align__(16) uint8_t lds_raw[];
@@ -312,15 +446,19 @@ __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
         const int cnt = valid ? hi - lo : 0;
         int total;
         const int off = ref::block_exscan<NT / 64>(cnt, s.wsum, &total);
-        if (tid == 0) s.m_fit = 0;
+        if (tid == 0) { s.m_fit = 0; s.keep[0] = 0; }
         __syncthreads();
         const bool fits = p < NK && off + cnt <= CAND_CAP;
         if (fits) atomicAdd(&s.m_fit, 1);
+        if (fits && cnt > SPEC_MAX_LIST) s.keep[0] = 1;
         s.pid[tid] = valid ? kf : -1;
         s.poff[tid] = off;
         if (tid == NT - 1) s.poff[NT] = total;
         __syncthreads();
         const int m = s.m_fit;
+        const bool spec = s.keep[0] == 0 && spec_room(s, m, NF);
+        if (spec)
+            for (int i = tid; i < NF; i += NT) spec_claims(s, NF)[i] = 0xffffffffu;
         if (fits && cnt > 0) {
             uint32_t d[8];
             ref::load_desc(d, g.kf_desc + (ko + kf) * 32);
@@ -331,7 +469,8 @@ __global__ __launch_bounds__(NT) void bow_kernel(BowArgs g, Args a) {
             }
         }
         __syncthreads();
-        if (tid < 64) resolve_chunk<MODE_BOW>(s, m, a, match_b, b, g.kf_angle + ko, g.f_angle + fo, nullptr, nullptr);
+        if (spec) resolve_chunk_spec<MODE_BOW>(s, m, NF, a, match_b, g.kf_angle + ko, g.f_angle + fo, nullptr, nullptr);
+        else if (tid < 64) resolve_chunk<MODE_BOW>(s, m, a, match_b, b, g.kf_angle + ko, g.f_angle + fo, nullptr, nullptr);
         __syncthreads();
         base += m;
     }
@@ -1190,3 +1329,13 @@ int planar_plane_search_by_coefficients(planar_ctx* ctx, int B, const int32_t* n
 }
 
 }  // extern "C"
+
+#ifdef PLANAR_GUIDED_SPLIT
+// developer build only: out[4][SPLIT_N] = the sums since the last reset, by mode (FRAME, MAP, BOW, KF); the caller has synchronised the device
+extern "C" int planar_guided_split_read(unsigned long long* out, int reset) {
+    static const unsigned long long zero[4][guided::SPLIT_N] = {};
+    if (out) PLANAR_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(guided::g_split), sizeof(zero)));
+    if (reset) PLANAR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(guided::g_split), zero, sizeof(zero)));
+    return PLANAR_OK;
+}
+#endif

@@ -16,6 +16,17 @@ constexpr int NCELL = PLANAR_GRID_COLS * PLANAR_GRID_ROWS;
 constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
 constexpr int CAND_CAP = 8192;       // candidates of one chunk of probes; with it the workgroup needs 61 KB of LDS (two per CU)
 constexpr int TH_HIGH = 100, TH_LOW = 50;   // src/ORBmatcher.cc:38-39
+// A chunk whose longest list is at most this is resolved a thread per probe (guided.hip resolve_chunk_spec), where a round costs the longest list's serial scans;
+// beyond it the wave-wide pass, which reads 64 entries of a list at once.  DESIGN.md §4.13 has the measurements.
+#ifndef PLANAR_SPEC_MAX_LIST
+#define PLANAR_SPEC_MAX_LIST 64
+#endif
+constexpr int SPEC_MAX_LIST = PLANAR_SPEC_MAX_LIST;
+// -DPLANAR_SPEC_WHOLE_LIST=1: the speculating resolver's baseline conflict rule (any claimed entry of the list), to measure the rule in use against
+#ifndef PLANAR_SPEC_WHOLE_LIST
+#define PLANAR_SPEC_WHOLE_LIST 0
+#endif
+constexpr bool SPEC_WHOLE_LIST = PLANAR_SPEC_WHOLE_LIST != 0;
 
 struct ChunkLds {
     uint32_t cand[CAND_CAP];       // dist << 16 | octave << 12 | index ; doubles as scratch while the grid is built
@@ -27,8 +38,8 @@ struct ChunkLds {
     uint16_t ev_idx[MAXN];
     uint8_t ev_bin[MAXN];
     int hist[HISTO_LENGTH];
-    int keep[3];
-    int n_ev, nmatches, m_fit, wsum[NT / 64];
+    int keep[3];                   // the rotation filters' bins; while the chunks run, keep[0] != 0: the chunk has a list longer than SPEC_MAX_LIST
+    int n_ev, nmatches, m_fit, wsum[NT / 64];   // m_fit: the chunk's size; the speculating resolver keeps its first probe in conflict there once every thread read the size
 };
 
 // a shuffle butterfly; planar::wave_min_u32 (wave_ops.h) is a DPP ladder.  Swapping one for the other changes the benchmarked path: a change of its own.
@@ -161,6 +172,32 @@ __device__ inline uint32_t unblocked_key(const ChunkLds& s, int off, int cnt, in
     return key;
 }
 
+// ---- the speculating resolver's pieces (guided.hip resolve_chunk_spec) ----
+// The claim table, one word per key point: the last nkeys words of s.cand.  The chunk's lists end at s.poff[m], so it is there when spec_room says so.
+__device__ inline uint32_t* spec_claims(ChunkLds& s, int nkeys) { return s.cand + (CAND_CAP - nkeys); }
+__device__ inline bool spec_room(const ChunkLds& s, int m, int nkeys) { return s.poff[m] + nkeys <= CAND_CAP; }
+
+// One thread's serial scan of its own list: k1 / k2 = the smallest and second smallest (dist << 16 | list position) among the entries whose key point is not
+// blocked, 0xffffffff where there is none.  The keys are distinct, so these are unblocked_key's wave-wide minima without and with skip = the best.
+template <bool SECOND>
+__device__ inline void spec_scan(const ChunkLds& s, int off, int cnt, uint32_t& k1, uint32_t& k2) {
+    k1 = k2 = 0xffffffffu;
+    for (int k = 0; k < cnt; k++) {
+        const uint32_t e = s.cand[off + k];
+        const int idx = e & 0xfff;
+        const uint32_t key = ((s.blocked[idx >> 5] >> (idx & 31)) & 1u) ? 0xffffffffu : (e & 0xffff0000u) | (uint32_t)k;
+        if (SECOND) k2 = min(k2, max(k1, key));
+        k1 = min(k1, key);
+    }
+}
+
+// true if a key point of the list, blocked or not, is claimed by a probe before q
+__device__ inline bool spec_conflict(const ChunkLds& s, const uint32_t* claim, int off, int cnt, int q) {
+    bool hit = false;
+    for (int k = 0; k < cnt; k++) hit |= claim[s.cand[off + k] & 0xfff] < (uint32_t)q;
+    return hit;
+}
+
 // rotation-consistency post-step of MODE_FRAME and MODE_BOW.  rotation_filter_ranked computes the same another way; merging them changes the benchmarked
 // MODE_FRAME instruction stream, so that is a measured change of its own.  Neither filter nor bitonic_sort_u64 is `inline`: projection_kernel<MODE_FRAME> and
 // bow_kernel call rotation_filter out of line, and a file that does not call one of the three does not emit it.
@@ -172,8 +209,19 @@ __device__ void rotation_filter(ChunkLds& s, int32_t* match) {
     for (int i = tid; i < n; i += NT) atomicAdd(&s.hist[s.ev_bin[i]], 1);
     __syncthreads();
     if (tid == 0) {
-        int i1, i2, i3;
-        ref::three_maxima(s.hist, i1, i2, i3);
+        // ref::three_maxima (ComputeThreeMaxima, src/ORBmatcher.cc:1666-1708) with its if / else-if insertions as selects: max1 >= max2 >= max3, so g1 implies g2
+        // implies g3.  Through the int& form the three indices live in scratch.
+        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+#pragma unroll 1
+        for (int i = 0; i < HISTO_LENGTH; i++) {
+            const int sz = s.hist[i];
+            const bool g1 = sz > max1, g2 = sz > max2, g3 = sz > max3;
+            i3 = g2 ? i2 : g3 ? i : i3;    max3 = g2 ? max2 : g3 ? sz : max3;
+            i2 = g1 ? i1 : g2 ? i : i2;    max2 = g1 ? max1 : g2 ? sz : max2;
+            i1 = g1 ? i : i1;              max1 = g1 ? sz : max1;
+        }
+        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+        else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
         s.keep[0] = i1; s.keep[1] = i2; s.keep[2] = i3;
         int removed = 0;
         for (int i = 0; i < HISTO_LENGTH; i++)
