@@ -589,6 +589,28 @@ int planar_search_by_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, c
                               const planar_frame_view* d_kf2, const planar_kf_points* d_mp2, float log_scale_factor2, int n_levels2, const float* d_s12,
                               const float* d_R12, const float* d_t12, float th, int32_t* d_match12, int32_t* d_n_found);
 
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:3739-3934), batched over B independent key-frame pairs: step 4 of
+ * LoopClosing::ComputeSim3, after planar_search_by_sim3 and with its views, so the calls chain on the device.  One free VertexSim3Expmap, an EdgeSim3ProjectXYZ and
+ * an EdgeInverseSim3ProjectXYZ per correspondence with g2o's numeric Jacobians, Huber with delta = sqrt(th2), Levenberg on the dense 7x7: optimize(5), classify,
+ * optimize(nBad > 0 ? 10 : 5) on the inliers, classify.
+ *   kf1, kf2: n, keys_un (pt and octave), Tcw, fx fy cx cy (each view's own: K1 and K2) and scale_factors (mvInvLevelSigma2[octave] = 1.0f / (sf * sf)) are read;
+ *       mp1, mp2: usable and xw.  Nothing else is read and may be NULL.  Both views have the same B.
+ *   S12 [B][8] (in/out, double): quaternion x, y, z, w, then t, then s: g2o::Sim3::operator[] order.  The quaternion is taken as it is (g2o does not normalise it).
+ *   th2, fix_scale: th2 and bFixScale.
+ *   match12[b][i] (in/out, stride of kf1), with the entry meaning planar_search_by_sim3 documents: -1 = vpMatches1[i] is NULL; a value in [0, n2[b]) = i2 =
+ *       GetIndexInKeyFrame(pKF2) of the matched point; any other value = a match whose point is not in pKF2 (i2 < 0), which is skipped and keeps its value.  i is a
+ *       correspondence where usable1[i] and usable2[i2] are set too.  On exit -1 exactly where the reference sets vpMatches1[i] = NULL: the outliers of the first pass
+ *       (also on the early return) and those of the second.
+ *   n_inliers[b]: the function's return value.   lm_iters[b][2] (may be NULL): the Levenberg iterations the two optimize calls ran.
+ * Kept as the reference has them: P3D1c / P3D2c are float products widened to double; a classification reads chi2() of g2o's last evaluation, which may be a
+ * rejected trial; fewer than 10 correspondences left after the first pass returns 0 with S12 untouched.
+ * Defined where the reference is not: n[b] is clamped to [0, stride]; a pair without a correspondence returns 0 with S12 untouched; an octave outside the levels is
+ * taken modulo PLANAR_MAX_LEVELS.  PLANAR_EINVAL: a null array, views of different B, B < 1, a stride outside [1, PLANAR_MAX_FRAME_KEYS]. */
+int planar_optimize_sim3(planar_ctx* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2,
+                         double* S12, float th2, int fix_scale, int32_t* match12, int32_t* n_inliers, int32_t* lm_iters);
+int planar_optimize_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, const planar_kf_points* d_mp1, const planar_frame_view* d_kf2,
+                             const planar_kf_points* d_mp2, double* d_S12, float th2, int fix_scale, int32_t* d_match12, int32_t* d_n_inliers, int32_t* d_lm_iters);
+
 /* ORBmatcher(nn_ratio, check_orientation)::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (src/ORBmatcher.cc:526-659), batched
  * over B independent key-frame pairs (LoopClosing::ComputeSim3 calls it with ORBmatcher(0.75, true), once per candidate).  Both FeatureVectors are passed as one
  * node id per feature (-1: in no node), as planar_search_by_bow takes them.  Probes are key frame 1's features in (node ascending, feature index ascending)

@@ -9,6 +9,7 @@
 //   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
+//   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1490,3 +1491,83 @@ inline int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoi
 }
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_LOOP_MATCHERS
+
+
+// ---- Optimizer::OptimizeSim3: the DEFINITION of the static member with the reference's signature
+//          int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2, const bool bFixScale)   src/Optimizer.cc:3739-3934
+//      Enabled with PLANAR_ADAPTERS_WITH_SIM3_OPT, after the reference's Optimizer.h, KeyFrame.h, MapPoint.h and g2o's types/sim3.h; leave that body of src/Optimizer.cc out.
+//      The call gathers what the function reads (mK, GetRotation() / GetTranslation(), mvKeysUn, mvScaleFactors, GetMapPointMatches(), isBad(), GetWorldPos(),
+//      GetIndexInKeyFrame) with the packing of the loop matchers above, runs planar_optimize_sim3 with B = 1 on the tracking context, sets vpMatches1[i] = NULL where the
+//      entry cleared the match and writes g2oS12 through g2o::Sim3::operator[].  A failing call returns 0 and changes nothing.
+#ifdef PLANAR_ADAPTERS_WITH_SIM3_OPT
+namespace planar_adapter {
+
+struct Sim3OptSide {
+    int32_t n;
+    std::vector<planar_keypoint> keys;
+    std::vector<uint8_t> usable;
+    std::vector<float> xw;
+    float Tcw[16];
+    planar_frame_view view;
+    planar_kf_points kp;
+    template <class KeyFrameT, class MapPointT> Sim3OptSide(KeyFrameT* pKF, const std::vector<MapPointT*>& mps) {
+        n = (int32_t)pKF->mvKeysUn.size();
+        const size_t S = n > 0 ? (size_t)n : 1;
+        keys.resize(S); usable.assign(S, 0); xw.assign(S * 3, 0.f);
+        for (int i = 0; i < n; i++) {
+            std::memcpy(&keys[i], &pKF->mvKeysUn[i], sizeof(planar_keypoint));
+            MapPointT* p = (size_t)i < mps.size() ? mps[i] : NULL;
+            if (!p || p->isBad()) continue;
+            usable[i] = 1;
+            cv::Mat X = p->GetWorldPos();
+            for (int k = 0; k < 3; k++) xw[3 * i + k] = X.template at<float>(k);
+        }
+        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Tcw[4 * r + c] = R.template at<float>(r, c); Tcw[4 * r + 3] = t.template at<float>(r); }
+        Tcw[12] = Tcw[13] = Tcw[14] = 0.f; Tcw[15] = 1.f;
+        std::memset(&view, 0, sizeof(view)); std::memset(&kp, 0, sizeof(kp));
+        view.B = 1; view.stride = (int32_t)S; view.n = &n; view.keys_un = keys.data(); view.Tcw = Tcw;
+        view.fx = pKF->mK.template at<float>(0, 0); view.fy = pKF->mK.template at<float>(1, 1); view.cx = pKF->mK.template at<float>(0, 2); view.cy = pKF->mK.template at<float>(1, 2);
+        for (int l = 0; l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = 1.f;
+        for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = pKF->mvScaleFactors[l];
+        kp.usable = usable.data(); kp.xw = xw.data();
+    }
+};
+
+template <class KeyFrameT, class MapPointT, class Sim3T>
+int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, float th2, bool bFixScale) {
+    const std::vector<MapPointT*> mps1 = pKF1->GetMapPointMatches(), mps2 = pKF2->GetMapPointMatches();
+    Sim3OptSide s1(pKF1, mps1), s2(pKF2, mps2);
+    if (s1.n > PLANAR_MAX_FRAME_KEYS || s2.n > PLANAR_MAX_FRAME_KEYS) return 0;
+    const int N = (int)vpMatches1.size() < s1.n ? (int)vpMatches1.size() : s1.n;
+    const int32_t NOT_IN_KF2 = -2;                                                      // i2 < 0: skipped (:3807)
+    std::vector<int32_t> match((size_t)s1.view.stride, -1);
+    for (int i = 0; i < N; i++) {
+        if (!vpMatches1[i]) continue;
+        const int i2 = vpMatches1[i]->GetIndexInKeyFrame(pKF2);
+        // usable2 describes pKF2's own slot: the matched point itself must be the one that is not bad
+        match[i] = (i2 >= 0 && i2 < s2.n && !vpMatches1[i]->isBad()) ? i2 : NOT_IN_KF2;
+        if (match[i] >= 0) { s2.usable[i2] = 1; cv::Mat X = vpMatches1[i]->GetWorldPos(); for (int k = 0; k < 3; k++) s2.xw[3 * i2 + k] = X.template at<float>(k); }
+    }
+    const std::vector<int32_t> entry = match;
+    double S[8];
+    for (int k = 0; k < 8; k++) S[k] = g2oS12[k];
+    int32_t nIn = 0;
+    {
+        Runtime::Lane& L = Runtime::get().lane(TRACKING);
+        std::lock_guard<std::mutex> g(L.mu);
+        if (!ok(planar_optimize_sim3(L.ctx, &s1.view, &s1.kp, &s2.view, &s2.kp, S, th2, bFixScale ? 1 : 0, match.data(), &nIn, NULL), "planar_optimize_sim3")) return 0;
+    }
+    for (int i = 0; i < N; i++) if (match[i] != entry[i]) vpMatches1[i] = static_cast<MapPointT*>(NULL);
+    for (int k = 0; k < 8; k++) g2oS12[k] = S[k];      // untouched on the early return: the entry leaves S as it was
+    return nIn;
+}
+
+}  // namespace planar_adapter
+
+namespace Planar_SLAM {
+inline int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2, const bool bFixScale) {
+    return planar_adapter::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale);
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_SIM3_OPT

@@ -2,7 +2,13 @@
 // Restates the Eigen kernels g2o relies on (quaternion product / rotate / matrix conversions, AngleAxis), g2o's SE3Quat
 // (Thirdparty/g2o/g2o/types/se3quat.h) and PlanarSLAM's Plane3D (g2oAddition/Plane3D.h).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else   // a host compiler (tests/host_shim/sim3_opt_host.cpp builds sim3_arith.h for the CPU): the same functions, plain
+#include <math.h>
+#define __device__
+#define __forceinline__ inline
+#endif
 
 namespace planar {
 namespace geomd {

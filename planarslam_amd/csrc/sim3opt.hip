@@ -1,0 +1,159 @@
+// planarslam_amd/csrc/sim3opt.hip — Optimizer::OptimizeSim3 (reference src/Optimizer.cc:3739-3934) for a batch of B independent key-frame pairs on MI355X (gfx950):
+// step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:331), between planar_search_by_sim3 and planar_search_by_projection_sim3, with their views and their match12.
+//
+// One 256-thread workgroup per pair runs the whole two-pass protocol on chip, in the manner of pose_opt_kernel (pose.hip):
+//   * threads stride over the correspondences; each evaluates its two edges in FP64 with g2o's numeric central-difference Jacobians and accumulates
+//     J^T W J (28 unique) + J^T W e (7) + the robust chi2 in registers; a wave shuffle + LDS reduction makes the 7x7 system;
+//   * the 14 estimates Sim3(+-1e-9 e_d) * S12 and their inverses are the same for every edge: threads 0..13 compute them once per linearisation into LDS, so a
+//     correspondence costs 2 x 15 error evaluations and no exp;
+//   * the Levenberg control, the pivoted 7x7 LDLT and the Sim3 exponential update are computed by every thread from the reduced system, so control flow is
+//     workgroup-uniform;
+//   * the errors are never stored: a classification reads chi2() of g2o's LAST evaluation, possibly a rejected trial, so the estimate of that evaluation is kept
+//     (Shared::S_eval) and the errors are evaluated again.
+// All arithmetic and the protocol itself are sim3_arith.h, which the CPU test compiles too.  No MFMA: there is no dense contraction here (7x7 per pair).
+#include "common.h"
+#include "sim3_arith.h"
+
+namespace planar {
+namespace sim3 {
+
+constexpr int NT = 256;
+constexpr int MAXN = PLANAR_MAX_FRAME_KEYS;
+
+struct Args {
+    planar_frame_view kf1, kf2;
+    planar_kf_points mp1, mp2;
+    double* S12;            // [B][8] in/out
+    int32_t* match12;       // [B][stride1] in/out
+    int32_t* n_inliers;     // [B]
+    int32_t* lm_iters;      // [B][2] or null
+    float th2;
+    int fix_scale;
+};
+
+struct Lds {
+    Shared sh;
+    double red[NT / 64][ACC_DOUBLES];
+    float sf1[PLANAR_MAX_LEVELS], sf2[PLANAR_MAX_LEVELS];   // mvScaleFactors of the two views (indexed by the octave: out of the kernel arguments, which a
+                                                           // dynamic index would send to scratch)
+    uint8_t lvl[MAXN];
+};
+static_assert(sizeof(Lds) == 7520, "DESIGN.md 4.14 states the LDS of optimize_sim3_kernel");
+
+struct Workgroup {   // Par of optimize_pair
+    Lds* l;
+    __device__ __forceinline__ int tid() const { return threadIdx.x; }
+    __device__ __forceinline__ int nt() const { return NT; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    // the sum over the workgroup, in every thread, by the same association in every thread: lanes by xor-shuffle, then the four waves
+    template <int N> __device__ __forceinline__ void reduce(double (&v)[N]) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            double x = v[k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+            v[k] = x;
+        }
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < N; k++) l->red[wave][k] = v[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = (l->red[0][k] + l->red[1][k]) + (l->red[2][k] + l->red[3][k]);
+    }
+    // the same sums by the same association, left in dst (LDS) for every thread to read
+    template <int N> __device__ __forceinline__ void reduce_to(const double (&v)[N], double* dst) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            double x = v[k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+            if (lane == 0) l->red[wave][k] = x;
+        }
+        __syncthreads();
+        if (threadIdx.x < N) { const int k = threadIdx.x; dst[k] = (l->red[0][k] + l->red[1][k]) + (l->red[2][k] + l->red[3][k]); }
+        __syncthreads();
+    }
+};
+
+__global__ __launch_bounds__(NT) void optimize_sim3_kernel(Args a) {
+    __shared__ Lds lds;
+    const int b = blockIdx.x;
+    Pair P;
+    P.n1 = a.kf1.n[b]; P.n1 = P.n1 < 0 ? 0 : (P.n1 > a.kf1.stride ? a.kf1.stride : P.n1);
+    P.n2 = a.kf2.n[b]; P.n2 = P.n2 < 0 ? 0 : (P.n2 > a.kf2.stride ? a.kf2.stride : P.n2);
+    const size_t o1 = (size_t)b * a.kf1.stride, o2 = (size_t)b * a.kf2.stride;
+    P.keys1 = (const Key*)(a.kf1.keys_un + o1); P.keys2 = (const Key*)(a.kf2.keys_un + o2);
+    P.usable1 = a.mp1.usable + o1; P.usable2 = a.mp2.usable + o2;
+    P.xw1 = a.mp1.xw + 3 * o1; P.xw2 = a.mp2.xw + 3 * o2;
+    P.T1 = a.kf1.Tcw + (size_t)b * 16; P.T2 = a.kf2.Tcw + (size_t)b * 16;
+    P.K1 = Cam{(double)a.kf1.fx, (double)a.kf1.fy, (double)a.kf1.cx, (double)a.kf1.cy};
+    P.K2 = Cam{(double)a.kf2.fx, (double)a.kf2.fy, (double)a.kf2.cx, (double)a.kf2.cy};
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int l = 0; l < PLANAR_MAX_LEVELS; l++) { lds.sf1[l] = a.kf1.scale_factors[l]; lds.sf2[l] = a.kf2.scale_factors[l]; }
+    }
+    __syncthreads();
+    P.sf1 = lds.sf1; P.sf2 = lds.sf2;
+    P.match12 = a.match12 + o1;
+    Workgroup wg{&lds};
+    const int nIn = optimize_pair(wg, P, a.S12 + (size_t)b * 8, a.th2, a.fix_scale != 0, lds.lvl, lds.sh, a.lm_iters ? a.lm_iters + 2 * (size_t)b : nullptr, (Events*)nullptr);
+    if (threadIdx.x == 0) a.n_inliers[b] = nIn;
+}
+
+}  // namespace sim3
+}  // namespace planar
+
+using namespace planar;
+
+static int check_opt_args(const void* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2, bool arrays) {
+    PLANAR_REQUIRE(ctx && kf1 && mp1 && kf2 && mp2 && arrays, PLANAR_EINVAL, "null argument");
+    PLANAR_REQUIRE(frame_view_sizes_ok(kf1) && frame_view_sizes_ok(kf2) && kf1->B == kf2->B, PLANAR_EINVAL,
+                   "key-frame views: the same B >= 1 and 1 <= stride <= PLANAR_MAX_FRAME_KEYS required");
+    PLANAR_REQUIRE(kf1->n && kf1->keys_un && kf1->Tcw && kf2->n && kf2->keys_un && kf2->Tcw, PLANAR_EINVAL, "n, keys_un and Tcw of both key-frame views required");
+    PLANAR_REQUIRE(mp1->usable && mp1->xw && mp2->usable && mp2->xw, PLANAR_EINVAL, "usable and xw of both key frames' map points required");
+    return PLANAR_OK;
+}
+
+extern "C" {
+
+int planar_optimize_sim3_dev(planar_ctx* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2,
+                             double* d_S12, float th2, int fix_scale, int32_t* d_match12, int32_t* d_n_inliers, int32_t* d_lm_iters) {
+    if (int rc = check_opt_args(ctx, kf1, mp1, kf2, mp2, d_S12 && d_match12 && d_n_inliers)) return rc;
+    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
+    sim3::Args a{};
+    a.kf1 = *kf1; a.kf2 = *kf2; a.mp1 = *mp1; a.mp2 = *mp2;
+    a.S12 = d_S12; a.match12 = d_match12; a.n_inliers = d_n_inliers; a.lm_iters = d_lm_iters; a.th2 = th2; a.fix_scale = fix_scale;
+    hipLaunchKernelGGL(sim3::optimize_sim3_kernel, dim3(kf1->B), dim3(sim3::NT), 0, ctx->stream, a);
+    PLANAR_HIP_CHECK(hipGetLastError());
+    return PLANAR_OK;
+}
+
+int planar_optimize_sim3(planar_ctx* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2,
+                         double* S12, float th2, int fix_scale, int32_t* match12, int32_t* n_inliers, int32_t* lm_iters) {
+    if (int rc = check_opt_args(ctx, kf1, mp1, kf2, mp2, S12 && match12 && n_inliers)) return rc;
+    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
+    Stager s;
+    planar_frame_view d1 = *kf1, d2 = *kf2;
+    planar_kf_points p1 = *mp1, p2 = *mp2;
+    for (planar_frame_view* d : {&d1, &d2}) {
+        const size_t B = (size_t)d->B, n = B * d->stride;
+        d->u_right = nullptr; d->desc = nullptr; d->blocked = nullptr;             // not read
+        s.in_field(d->n, B); s.in_field(d->keys_un, n); s.in_field(d->Tcw, B * 16);
+    }
+    const size_t B = (size_t)kf1->B;
+    { const size_t n = B * d1.stride; p1.min_dist = p1.max_dist = nullptr; p1.desc = nullptr; s.in_field(p1.usable, n); s.in_field(p1.xw, n * 3); }
+    { const size_t n = B * d2.stride; p2.min_dist = p2.max_dist = nullptr; p2.desc = nullptr; s.in_field(p2.usable, n); s.in_field(p2.xw, n * 3); }
+    const auto d_S = s.inout(S12, B * 8);
+    const auto d_m = s.inout(match12, B * kf1->stride);
+    const auto d_ni = s.out(n_inliers, B);
+    const auto d_it = s.out(lm_iters, B * 2);
+    return s.run(ctx->stream, [&] { return planar_optimize_sim3_dev(ctx, &d1, &p1, &d2, &p2, d_S, th2, fix_scale, d_m, d_ni, d_it); });
+}
+
+}  // extern "C"
