@@ -611,6 +611,52 @@ int planar_optimize_sim3(planar_ctx* ctx, const planar_frame_view* kf1, const pl
 int planar_optimize_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, const planar_kf_points* d_mp1, const planar_frame_view* d_kf2,
                              const planar_kf_points* d_mp2, double* d_S12, float th2, int fix_scale, int32_t* d_match12, int32_t* d_n_inliers, int32_t* d_lm_iters);
 
+/* Sim3Solver (src/Sim3Solver.cc), batched over B independent key-frame pairs: step 2 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:274-301), between
+ * planar_search_by_bow_kf and planar_search_by_sim3 and on the views of the latter, so the calls chain on the device.  Each pair has the semantics of one
+ * Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale), SetRansacParameters(prob, min_inliers, max_its) and ONE iterate(n_iterations, bNoMore, vbInliers, nInliers); the
+ * solver's state is passed in and out, so a later call is the same solver's next iterate.
+ *   kf1, kf2: n, keys_un (the octave), Tcw, fx fy cx cy (each view's own: mK1 and mK2) and scale_factors (mvLevelSigma2[octave] = sf * sf) are read; mp1, mp2:
+ *       usable and xw.  Nothing else is read and may be NULL.  Both views have the same B.
+ *   match12[b][i1] (stride of kf1; not written, and not the array match12_inl), with the entry meaning planar_search_by_sim3 documents: -1 = vpMatched12[i1] is
+ *       NULL; a value in [0, n2[b]) = i2 = GetIndexInKeyFrame(pKF2); any other value = a point that is not in pKF2, skipped as indexKF2 < 0 is (:82).  i1 is a
+ *       correspondence where usable1[i1] and usable2[i2] are set too.  Correspondences are numbered in ascending i1: that order decides what a draw picks.
+ *   prob, min_inliers, max_its, fix_scale: the arguments of SetRansacParameters and bFixScale.  n_iterations: that of iterate.
+ *   seeds[b]: the pair's draws are glibc's rand() after srand(seeds[b]).  The reference's stream is process-global and shared by every solver; a stream per item is
+ *       the rule planar_is_line_good set.  Iteration k (counted from the solver's construction) uses draws 3k .. 3k + 2, so the place in the stream follows from
+ *       its_done.  A draw is DUtils::Random::RandomInt(0, size - 1) = int(((double)rand() / ((double)RAND_MAX + 1.0)) * size) (Random.cpp:47-50), and the three picks
+ *       follow the swap-with-back rule of :170-181.
+ *   State of the solver, [B] each, in/out (zero for a new solver): its_done = mnIterations; best_inliers = mnBestInliers; best_R [B][9], best_t [B][3], best_s [B] =
+ *       mBestRotation, mBestTranslation, mBestScale, written whenever mnInliersi >= mnBestInliers, so the last such iteration wins.
+ *   found[b]: 1 where the reference returns a non-empty mBestT12.  no_more[b]: bNoMore.  n_inliers[b]: nInliers.  inliers[b][i1] (stride of kf1): vbInliers.
+ *   R12 [B][9] row-major, t12 [B][3], s12 [B]: GetEstimatedRotation / Translation / Scale of a pair that was found, in the layout planar_search_by_sim3 takes; zero
+ *       where found is 0.
+ *   match12_inl[b][i1] (may be NULL): match12 with every entry that is no inlier set to -1, as LoopClosing.cc:313-318 builds vpMapPointMatches before SearchBySim3.
+ *   S12 [B][8] (may be NULL, double): g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) as LoopClosing.cc:325 builds gScm, in
+ *       g2o::Sim3::operator[] order (quaternion x y z w, t, s): what planar_optimize_sim3 takes.  Eigen's matrix-to-quaternion rule; that constructor does not
+ *       normalise (sim3.h:64-67).  Zero where found is 0.
+ * mRansacMaxIts = max(1, min(ceil(log(1 - prob) / log(1 - pow((float)min_inliers / N, 3))), max_its)), and 1 where min_inliers == N, is host libm arithmetic that a
+ * ceil can tip: the library evaluates the reference's expression on the host for every N, keeps the table in the context per (prob, min_inliers, max_its) and the
+ * kernel reads it.  Where the double is no int (NaN, overflow) the reference's conversion is undefined; x86-64 gives INT_MIN, hence 1, and so does the table.
+ * Kept as the reference has them: iterate clears vbInliers and nInliers on every call; N < mRansacMinInliers is tested before a draw; the rotation angle is
+ * atan2(norm(vec), w) in double; vec = 2 * ang * vec / norm(vec) is NaN when the imaginary part of the eigenvector is exactly zero (two identical point sets),
+ * every comparison of CheckInliers then fails and the hypothesis has 0 inliers; 1 / z has no positivity gate; mvnMaxError1 / 2 are std::vector<size_t>
+ * (Sim3Solver.h:78-79), so 9.210 * sigma2 is a double product TRUNCATED to an integer and compared as a float; ms12i = nom / den is a double quotient narrowed to
+ * float.  A hypothesis of 0 inliers still replaces the best of a new solver (0 >= 0).
+ * Defined where the reference is not: n[b] is clamped to [0, stride]; an octave outside the levels is taken modulo PLANAR_MAX_LEVELS; N < max(min_inliers, 3) gives
+ * no_more = 1, found = 0 and leaves the state untouched; a negative its_done counts as 0.
+ * PLANAR_EINVAL, before any device call: a null required array, views of different B, B < 1, a stride outside [1, PLANAR_MAX_FRAME_KEYS], n_iterations < 1, max_its
+ * outside [1, PLANAR_HORN_MAX_ITS] (the draws and counts of one call are kept on chip; the reference passes 300), prob outside (0, 1).
+ * The _dev flavour keeps the correspondences of key frames above 512 key points in the context's scratch block. */
+#define PLANAR_HORN_MAX_ITS 1024
+int planar_horn_ransac(planar_ctx* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2,
+                       const int32_t* match12, double prob, int min_inliers, int max_its, int fix_scale, int n_iterations, const uint32_t* seeds, int32_t* its_done,
+                       int32_t* best_inliers, float* best_R, float* best_t, float* best_s, int32_t* found, int32_t* no_more, int32_t* n_inliers, uint8_t* inliers,
+                       float* R12, float* t12, float* s12, int32_t* match12_inl, double* S12);
+int planar_horn_ransac_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, const planar_kf_points* d_mp1, const planar_frame_view* d_kf2, const planar_kf_points* d_mp2,
+                           const int32_t* d_match12, double prob, int min_inliers, int max_its, int fix_scale, int n_iterations, const uint32_t* d_seeds,
+                           int32_t* d_its_done, int32_t* d_best_inliers, float* d_best_R, float* d_best_t, float* d_best_s, int32_t* d_found, int32_t* d_no_more,
+                           int32_t* d_n_inliers, uint8_t* d_inliers, float* d_R12, float* d_t12, float* d_s12, int32_t* d_match12_inl, double* d_S12);
+
 /* ORBmatcher(nn_ratio, check_orientation)::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (src/ORBmatcher.cc:526-659), batched
  * over B independent key-frame pairs (LoopClosing::ComputeSim3 calls it with ORBmatcher(0.75, true), once per candidate).  Both FeatureVectors are passed as one
  * node id per feature (-1: in no node), as planar_search_by_bow takes them.  Probes are key frame 1's features in (node ascending, feature index ascending)

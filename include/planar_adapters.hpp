@@ -10,6 +10,7 @@
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
+//   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -30,6 +31,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <tuple>
@@ -1499,10 +1501,10 @@ inline int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoi
 //      The call gathers what the function reads (mK, GetRotation() / GetTranslation(), mvKeysUn, mvScaleFactors, GetMapPointMatches(), isBad(), GetWorldPos(),
 //      GetIndexInKeyFrame) with the packing of the loop matchers above, runs planar_optimize_sim3 with B = 1 on the tracking context, sets vpMatches1[i] = NULL where the
 //      entry cleared the match and writes g2oS12 through g2o::Sim3::operator[].  A failing call returns 0 and changes nothing.
-#ifdef PLANAR_ADAPTERS_WITH_SIM3_OPT
+#if defined(PLANAR_ADAPTERS_WITH_SIM3_OPT) || defined(PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
 namespace planar_adapter {
 
-struct Sim3OptSide {
+struct Sim3OptSide {   // one key frame as planar_optimize_sim3 and planar_horn_ransac read it
     int32_t n;
     std::vector<planar_keypoint> keys;
     std::vector<uint8_t> usable;
@@ -1533,6 +1535,12 @@ struct Sim3OptSide {
         kp.usable = usable.data(); kp.xw = xw.data();
     }
 };
+
+}  // namespace planar_adapter
+#endif
+
+#ifdef PLANAR_ADAPTERS_WITH_SIM3_OPT
+namespace planar_adapter {
 
 template <class KeyFrameT, class MapPointT, class Sim3T>
 int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, float th2, bool bFixScale) {
@@ -1571,3 +1579,98 @@ inline int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<M
 }
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_SIM3_OPT
+
+// ---- Sim3Solver (reference include/Sim3Solver.h, src/Sim3Solver.cc): the class LoopClosing::ComputeSim3 constructs per candidate (src/LoopClosing.cc:274-301), with the
+//      reference's signatures.  Enabled with PLANAR_ADAPTERS_WITH_SIM3_SOLVER, after the reference's KeyFrame.h and MapPoint.h and INSTEAD of its Sim3Solver.h; leave
+//      src/Sim3Solver.cc out.  The constructor gathers what Optimizer::OptimizeSim3's adapter gathers (mK, GetRotation() / GetTranslation(), mvKeysUn, mvScaleFactors,
+//      GetMapPointMatches(), isBad(), GetWorldPos(), GetIndexInKeyFrame); iterate() runs planar_horn_ransac with B = 1 on the tracking context and carries the state
+//      (mnIterations, mnBestInliers, the best R, t, s) in the object.  The draws come from this solver's own glibc stream, srand(seed) with the seed of SetSeed (0 unless
+//      set): the reference's solvers share the process's rand().  A failing call returns an empty matrix with bNoMore set.
+#ifdef PLANAR_ADAPTERS_WITH_SIM3_SOLVER
+namespace Planar_SLAM {
+
+class Sim3Solver {
+public:
+    Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale = true)
+        : mnIterations(0), mnBestInliers(0), mBestScale(0.f), mbFixScale(bFixScale), mSeed(0) {
+        mN1 = (int)vpMatched12.size();
+        mpSide1.reset(new planar_adapter::Sim3OptSide(pKF1, pKF1->GetMapPointMatches()));
+        mpSide2.reset(new planar_adapter::Sim3OptSide(pKF2, pKF2->GetMapPointMatches()));
+        planar_adapter::Sim3OptSide &s1 = *mpSide1, &s2 = *mpSide2;
+        const int N = mN1 < s1.n ? mN1 : s1.n;
+        const int32_t NOT_IN_KF2 = -2;                                                      // indexKF2 < 0: skipped (:82)
+        mvMatch.assign((size_t)s1.view.stride, -1);
+        for (int i = 0; i < N; i++) {
+            if (!vpMatched12[i]) continue;
+            const int i2 = vpMatched12[i]->GetIndexInKeyFrame(pKF2);
+            // usable2 describes pKF2's own slot: the matched point itself must be the one that is not bad, and its position the one that is read
+            mvMatch[i] = (i2 >= 0 && i2 < s2.n && !vpMatched12[i]->isBad()) ? i2 : NOT_IN_KF2;
+            if (mvMatch[i] >= 0) { s2.usable[i2] = 1; cv::Mat X = vpMatched12[i]->GetWorldPos(); for (int k = 0; k < 3; k++) s2.xw[3 * i2 + k] = X.at<float>(k); }
+        }
+        for (int k = 0; k < 9; k++) mBestR[k] = 0.f;
+        for (int k = 0; k < 3; k++) mBestt[k] = 0.f;
+        SetRansacParameters();
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations;
+        mnIterations = 0;
+    }
+    void SetSeed(unsigned seed) { mSeed = seed; }
+    cv::Mat find(std::vector<bool>& vbInliers12, int& nInliers) {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+    }
+    cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        using namespace planar_adapter;
+        Sim3OptSide &s1 = *mpSide1, &s2 = *mpSide2;
+        bNoMore = true;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = 0;
+        if (s1.n > PLANAR_MAX_FRAME_KEYS || s2.n > PLANAR_MAX_FRAME_KEYS) return cv::Mat();
+        int32_t found = 0, no_more = 1, n_inl = 0;
+        std::vector<uint8_t> inl((size_t)s1.view.stride, 0);
+        float R[9], t[3], s = 0.f;
+        {
+            Runtime::Lane& L = Runtime::get().lane(TRACKING);
+            std::lock_guard<std::mutex> g(L.mu);
+            if (!ok(planar_horn_ransac(L.ctx, &s1.view, &s1.kp, &s2.view, &s2.kp, mvMatch.data(), mRansacProb, mRansacMinInliers, mRansacMaxIts, mbFixScale ? 1 : 0,
+                                       nIterations, &mSeed, &mnIterations, &mnBestInliers, mBestR, mBestt, &mBestScale, &found, &no_more, &n_inl, inl.data(), R, t, &s,
+                                       NULL, NULL), "planar_horn_ransac")) return cv::Mat();
+        }
+        bNoMore = no_more != 0;
+        if (!found) return cv::Mat();
+        nInliers = n_inl;
+        for (int i = 0; i < mN1 && i < s1.n; i++) vbInliers[i] = inl[i] != 0;
+        cv::Mat T(4, 4, CV_32F);                                                            // mBestT12: [s R | t]
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T.at<float>(r, c) = R[3 * r + c] * s; T.at<float>(r, 3) = t[r]; }
+        T.at<float>(3, 0) = T.at<float>(3, 1) = T.at<float>(3, 2) = 0.f; T.at<float>(3, 3) = 1.f;
+        return T;
+    }
+    cv::Mat GetEstimatedRotation() {
+        if (mnIterations <= 0) return cv::Mat();                                            // mBestRotation is empty until an iteration has run
+        cv::Mat R(3, 3, CV_32F);
+        for (int k = 0; k < 9; k++) R.at<float>(k / 3, k % 3) = mBestR[k];
+        return R;
+    }
+    cv::Mat GetEstimatedTranslation() {
+        if (mnIterations <= 0) return cv::Mat();
+        cv::Mat t(3, 1, CV_32F);
+        for (int k = 0; k < 3; k++) t.at<float>(k, 0) = mBestt[k];
+        return t;
+    }
+    float GetEstimatedScale() { return mBestScale; }
+
+protected:
+    int mN1;
+    std::shared_ptr<planar_adapter::Sim3OptSide> mpSide1, mpSide2;                           // (shared: the views point into them, and the reference copies nothing here)
+    std::vector<int32_t> mvMatch;
+    int32_t mnIterations, mnBestInliers;
+    float mBestR[9], mBestt[3], mBestScale;
+    bool mbFixScale;
+    uint32_t mSeed;
+    double mRansacProb;
+    int mRansacMinInliers, mRansacMaxIts;
+};
+
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_SIM3_SOLVER

@@ -197,6 +197,11 @@ struct planar_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;   // the stream work is enqueued on (own_stream unless overridden)
     planar::DevBuf scratch;         // grow-only device scratch for entry points that need temporaries
+    // planar_horn_ransac: mRansacMaxIts over N in [0, PLANAR_MAX_FRAME_KEYS], host libm arithmetic, kept per (prob, min_inliers, max_its) (hornransac.hip)
+    planar::DevBuf horn_table;
+    std::vector<int32_t> horn_table_host;
+    double horn_prob = -1;
+    int horn_min_inliers = 0, horn_max_its = 0;
     // Optional side stream for the one-wavefront-per-frame kernels of the extractors (PEAC clustering, LSD region growing): planar_ctx_set_seq_stream.  Such a kernel
     // is latency-bound and occupies a CU for tens of milliseconds with four wavefronts; on a CU-masked stream (planar_cu_stream_create) it stays on a subset of the
     // CUs while the wide kernels of `stream` keep the rest.  seq_begin() / seq_end() bracket the launch: fork by event from `stream`, join back into it.

@@ -1,0 +1,127 @@
+// tests/host_shim/horn_ransac_host.cpp — TEST INFRASTRUCTURE: the product's Sim3Solver arithmetic (planarslam_amd/csrc/horn_arith.h) compiled by g++ and driven by one
+// thread, so that tests/test_horn_ransac_oracle.py can hold it to the real reference's outputs (tests/golden/horn_ransac_ref.npz) without a GPU, read the inlier
+// count of every iteration, and tools/horn_ransac_bench.py can time the CPU side.  Built with -ffp-contract=off.  With -DHORN_RANSAC_HOST_MAIN it is a program of its
+// own (a sanitizer build runs that, never code loaded into python).
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../planarslam_amd/csrc/horn_arith.h"
+
+using namespace planar::horn;
+
+namespace {
+struct Serial {   // Par of ransac_pair: one thread is every group
+    int tid() const { return 0; }
+    int nt() const { return 1; }
+    void sync() const {}
+    int rank(bool f, int& total) const { total = f; return 0; }
+    int group() const { return 0; }
+    int ngroups() const { return 1; }
+    int lane() const { return 0; }
+    int lanes() const { return 1; }
+    int count(bool f) const { return f; }
+};
+}  // namespace
+
+extern "C" {
+
+struct horn_host_kf {
+    int32_t n, stride;
+    const void* keys; const uint8_t* usable; const float* xw; const float* Tcw;
+    float K[4];                // fx fy cx cy
+    float scale_factors[16];
+};
+
+// One pair, one iterate(n_iterations).  The arrays have the meaning and the sizes planar_horn_ransac documents for B = 1 (inliers and match12_inl: kf1->stride
+// entries).  counts (may be NULL, [max_its]): mnInliersi of the iterations this call ran, n_counts of them.  Returns N, or -1 for arguments planar_horn_ransac refuses.
+int horn_ransac_host(const horn_host_kf* kf1, const horn_host_kf* kf2, const int32_t* match12, double prob, int min_inliers, int max_its, int fix_scale,
+                     int n_iterations, uint32_t seed, int32_t* its_done, int32_t* best_inliers, float* best_R, float* best_t, float* best_s, int32_t* found,
+                     int32_t* no_more, int32_t* n_inliers, uint8_t* inliers, float* R12, float* t12, float* s12, int32_t* match12_inl, double* S12, int32_t* counts,
+                     int32_t* n_counts) {
+    if (n_iterations < 1 || max_its < 1 || max_its > MAX_ITS_CAP || !(prob > 0.0 && prob < 1.0) || kf1->stride < 1) return -1;
+    Pair P;
+    P.stride1 = kf1->stride;
+    P.n1 = kf1->n < 0 ? 0 : (kf1->n > kf1->stride ? kf1->stride : kf1->n);
+    P.n2 = kf2->n < 0 ? 0 : (kf2->n > kf2->stride ? kf2->stride : kf2->n);
+    P.keys1 = (const Key*)kf1->keys; P.keys2 = (const Key*)kf2->keys;
+    P.usable1 = kf1->usable; P.usable2 = kf2->usable;
+    P.xw1 = kf1->xw; P.xw2 = kf2->xw;
+    P.T1 = kf1->Tcw; P.T2 = kf2->Tcw;
+    P.K1 = Cam{kf1->K[0], kf1->K[1], kf1->K[2], kf1->K[3]};
+    P.K2 = Cam{kf2->K[0], kf2->K[1], kf2->K[2], kf2->K[3]};
+    float sig1[MAX_LEVELS], sig2[MAX_LEVELS];
+    for (int l = 0; l < MAX_LEVELS; l++) { sig1[l] = kf1->scale_factors[l] * kf1->scale_factors[l]; sig2[l] = kf2->scale_factors[l] * kf2->scale_factors[l]; }
+    P.sig1 = sig1; P.sig2 = sig2;
+    P.match12 = match12;
+    std::vector<int32_t> table((size_t)P.stride1 + 1);
+    for (int N = 0; N <= P.stride1; N++) table[N] = ransac_max_its(prob, min_inliers, max_its, N);
+    const Params prm{min_inliers, n_iterations, fix_scale, seed, table.data()};
+    const State st{its_done, best_inliers, best_R, best_t, best_s};
+    const Out out{found, no_more, n_inliers, inliers, R12, t12, s12, match12_inl, S12};
+    std::vector<float> corr((size_t)CORR_ROWS * P.stride1);
+    std::vector<int32_t> draws(3 * MAX_ITS_CAP), cnt(MAX_ITS_CAP, -1);
+    float hyp[HYP_FLOATS];
+    uint32_t ring[31];
+    const Work w{corr.data(), P.stride1, draws.data(), cnt.data(), hyp, 1, ring};
+    Serial par;
+    const int before = *its_done < 0 ? 0 : *its_done;
+    const int N = ransac_pair(par, P, prm, st, out, w);
+    const int ran = *its_done - before;   // 0 where the state was left untouched
+    if (n_counts) *n_counts = ran;
+    if (counts) memcpy(counts, cnt.data(), sizeof(int32_t) * (size_t)(ran > 0 ? ran : 0));
+    return N;
+}
+
+// the picks of `its` iterations of a solver over N >= 3 correspondences after srand(seed): idx [its][3]
+void horn_host_draws(uint32_t seed, int N, int its, int32_t* idx) {
+    uint32_t ring[31];
+    planar::GlibcRand g = planar::glibc_srand(ring, seed);
+    for (int k = 0; k < its; k++) {
+        const int r0 = planar::glibc_rand(g), r1 = planar::glibc_rand(g), r2 = planar::glibc_rand(g);
+        int p[3];
+        pick3(r0, r1, r2, N, p);
+        idx[3 * k] = p[0]; idx[3 * k + 1] = p[1]; idx[3 * k + 2] = p[2];
+    }
+}
+
+int horn_host_max_its(double prob, int min_inliers, int max_its, int N) { return ransac_max_its(prob, min_inliers, max_its, N); }
+
+}  // extern "C"
+
+#ifdef HORN_RANSAC_HOST_MAIN
+#include <cstdio>
+// a small fixed problem: 40 points seen by two cameras one similarity apart, every fourth match wrong
+int main() {
+    const int n = 40;
+    std::vector<Key> k1(n), k2(n);
+    std::vector<uint8_t> us(n, 1), inl(n);
+    std::vector<float> x1(3 * n), x2(3 * n);
+    std::vector<int32_t> m(n), mi(n);
+    const float T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    horn_host_kf a{}, b{};
+    const float K[4] = {535.4f, 539.2f, 320.1f, 247.6f};
+    unsigned r = 12345;
+    auto rnd = [&] { r = r * 1664525u + 1013904223u; return (float)(r >> 8) / 16777216.0f; };
+    for (int i = 0; i < n; i++) {
+        const float z = 1.0f + 3.0f * rnd(), x = (rnd() - 0.5f) * z, y = (rnd() - 0.5f) * z;
+        x1[3 * i] = x; x1[3 * i + 1] = y; x1[3 * i + 2] = z;
+        const float s = 1.1f, tx = 0.05f;                                  // P1 = s * P2 + t
+        x2[3 * i] = (x - tx) / s; x2[3 * i + 1] = y / s; x2[3 * i + 2] = z / s;
+        if (i % 4 == 3) x2[3 * i] += 0.4f;
+        k1[i] = Key{0, 0, 31, 0, 0, i % 3, -1};
+        k2[i] = Key{0, 0, 31, 0, 0, i % 2, -1};
+        m[i] = i;
+    }
+    for (horn_host_kf* f : {&a, &b}) { f->n = n; f->stride = n; f->usable = us.data(); f->Tcw = T; memcpy(f->K, K, sizeof K); float s = 1; for (int l = 0; l < 16; l++, s *= 1.2f) f->scale_factors[l] = s; }
+    a.keys = k1.data(); a.xw = x1.data(); b.keys = k2.data(); b.xw = x2.data();
+    int32_t its = 0, best = 0, found, no_more, nin, ncnt;
+    float bR[9] = {}, bt[3] = {}, bs = 0, R[9], t[3], s;
+    double S[8];
+    std::vector<int32_t> counts(300);
+    const int N = horn_ransac_host(&a, &b, m.data(), 0.99, 20, 300, 0, 300, 7u, &its, &best, bR, bt, &bs, &found, &no_more, &nin, inl.data(), R, t, &s, mi.data(), S,
+                                   counts.data(), &ncnt);
+    printf("N %d found %d its %d inliers %d s %.6f t %.6f %.6f %.6f\n", N, found, its, nin, s, t[0], t[1], t[2]);
+    return found && nin >= 25 ? 0 : 1;
+}
+#endif
