@@ -159,7 +159,7 @@ typedef struct planar_pose_batch {
     float* Tcw_out;                /* [B][16]              pose passed to Frame::SetPose                 */
     uint8_t* pt_outlier;           /* [B][max_points]      mvbOutlier      (written only where pt_valid) */
     uint8_t* ln_outlier;           /* [B][max_lines]       mvbLineOutlier  (written only where ln_valid) */
-    uint8_t* pl_outlier;           /* [B][max_planes][3]   mvbPlaneOutlier / mvbParPlaneOutlier / mvbVerPlaneOutlier */
+    uint8_t* pl_outlier;           /* [B][max_planes][3]   mvbPlaneOutlier / mvbParPlaneOutlier / mvbVerPlaneOutlier (written only where pl_valid, see below) */
     int32_t* n_inliers;            /* [B]                  the reference function's return value         */
     int32_t* lm_iters;             /* [B] or NULL          LM iterations run (diagnostic)                */
 } planar_pose_batch;
@@ -167,7 +167,20 @@ typedef struct planar_pose_batch {
 /* rounds = 4, its = 10 reproduce the reference protocol (4 x optimize(10) with outlier
  * re-classification, src/Optimizer.cc:990-1000).  All pointers in `batch` are HOST pointers for
  * planar_pose_opt (synchronous) and DEVICE pointers for planar_pose_opt_dev (enqueue only; the
- * struct itself is always host memory, passed by value to the kernel). */
+ * struct itself is always host memory, passed by value to the kernel).
+ *
+ * What is written when (the reference's own statements, src/Optimizer.cc:593-985 / :3034-3270): a flag is written only where its valid byte is
+ * set and its index is below the frame's count; every other entry keeps the caller's value.  pl_outlier[i][kind] is written only where
+ * pl_valid[i][kind]; kinds 1 and 2 (parallel, vertical) never in translation mode, whose edges for them are commented out (:3370, :3413); and no
+ * plane flag at all when TranslationOptimization returns early (fewer than 3 valid points, :3199, which stands before the plane edges are built;
+ * point and line flags are already cleared where valid by then).  PoseOptimization's early return (:985) comes after all flags are cleared.
+ * n_inliers may be negative in translation mode: planes count towards the outliers subtracted but not towards the correspondences.
+ *
+ * Defined where the reference is not: n_points[b] is clamped to [0, max_points] and n_lines[b] to [0, max_lines]; a negative n_planes[b] is 0;
+ * n_planes[b] > max_planes gives n_inliers[b] = -1, Tcw_out = Tcw_in and lm_iters[b] = 0, with point and line flags as an early return leaves
+ * them (cleared where valid) and no plane array of that frame read or written.  Nothing outside a frame's own rows is touched.
+ * PLANAR_EINVAL (nothing launched): a null argument or array whose stride is > 0, B < 1, a negative stride, max_planes > 32, a mode other than
+ * the two above, rounds outside [1, 4], its < 1, or strides that need more than 160 KiB of LDS per frame. */
 int planar_pose_opt(planar_ctx* ctx, const planar_pose_batch* batch, const planar_pose_params* params, int mode, int rounds, int its);
 int planar_pose_opt_dev(planar_ctx* ctx, const planar_pose_batch* d_batch, const planar_pose_params* params, int mode, int rounds, int its);
 

@@ -79,17 +79,23 @@ int orc_cv_round_d(double v) { return cv_round(v); }
 // ---- pose optimisation oracle (pose_oracle.cpp) ----
 #include "pose_oracle.h"
 extern "C" {
-// Flat batch layout == include/planar_abi.h planar_pose_batch (per-frame strides max_*).
-int orc_pose_optimize_batch(int B, int max_points, int max_lines, int max_planes, const int32_t* n_points,
-                            const int32_t* n_lines, const int32_t* n_planes, const uint8_t* pt_valid, const float* pt_xw,
-                            const float* pt_obs, const float* pt_inv_sigma2, const uint8_t* ln_valid, const double* ln_obs,
-                            const double* ln_xw, const float* pl_meas, const uint8_t* pl_valid, const float* pl_world,
-                            const float* Tcw_in, const orc::PoseParams* prm, int mode, int rounds, int its, float* Tcw_out,
-                            uint8_t* pt_outlier, uint8_t* ln_outlier, uint8_t* pl_outlier, int32_t* n_inliers, int32_t* lm_iters,
-                            double* final_chi2) {
+// Flat batch layout == include/planar_abi.h planar_pose_batch (per-frame strides max_*), and its rule for counts outside their strides: points and
+// lines clamped to [0, stride], a negative plane count is 0, more planes than the stride gives -1 with the pose copied, point and line flags as an
+// early return leaves them and no plane entry touched.
+}
+static void pose_batch_run(int B, int max_points, int max_lines, int max_planes, const int32_t* n_points,
+                           const int32_t* n_lines, const int32_t* n_planes, const uint8_t* pt_valid, const float* pt_xw,
+                           const float* pt_obs, const float* pt_inv_sigma2, const uint8_t* ln_valid, const double* ln_obs,
+                           const double* ln_xw, const float* pl_meas, const uint8_t* pl_valid, const float* pl_world,
+                           const float* Tcw_in, const orc::PoseParams* prm, int mode, int rounds, int its, float* Tcw_out,
+                           uint8_t* pt_outlier, uint8_t* ln_outlier, uint8_t* pl_outlier, int32_t* n_inliers, int32_t* lm_iters,
+                           double* final_chi2, int32_t* trials, int32_t* n_trials, int32_t* empty_rounds, uint8_t* ended_rejected) {
+    auto clamp = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
     for (int b = 0; b < B; b++) {
         orc::PoseProblem p;
-        p.n_points = n_points[b]; p.n_lines = n_lines[b]; p.n_planes = n_planes[b];
+        p.n_points = clamp(n_points[b], max_points); p.n_lines = clamp(n_lines[b], max_lines);
+        const bool too_many = n_planes[b] > max_planes;
+        p.n_planes = too_many ? 0 : clamp(n_planes[b], max_planes);
         p.pt_valid = pt_valid + (size_t)b * max_points; p.pt_xw = pt_xw + (size_t)b * max_points * 3;
         p.pt_obs = pt_obs + (size_t)b * max_points * 3; p.pt_inv_sigma2 = pt_inv_sigma2 + (size_t)b * max_points;
         p.ln_valid = ln_valid + (size_t)b * max_lines; p.ln_obs = ln_obs + (size_t)b * max_lines * 3;
@@ -101,12 +107,49 @@ int orc_pose_optimize_batch(int B, int max_points, int max_lines, int max_planes
         r.pt_outlier = pt_outlier + (size_t)b * max_points; r.ln_outlier = ln_outlier + (size_t)b * max_lines;
         r.pl_outlier = pl_outlier + (size_t)b * max_planes * 3;
         r.n_inliers = 0; r.lm_iterations = 0; r.final_chi2 = 0;
-        orc::pose_optimize(p, *prm, mode, rounds, its, r);
+        if (trials) r.trials = trials + (size_t)b * rounds * its;
+        if (too_many) {
+            for (int i = 0; i < p.n_points; i++) if (p.pt_valid[i]) r.pt_outlier[i] = 0;
+            for (int i = 0; i < p.n_lines; i++) if (p.ln_valid[i]) r.ln_outlier[i] = 0;
+            std::memcpy(r.Tcw, p.Tcw, sizeof(r.Tcw));
+            r.n_inliers = -1;
+        } else {
+            orc::pose_optimize(p, *prm, mode, rounds, its, r);
+        }
         std::memcpy(Tcw_out + (size_t)b * 16, r.Tcw, sizeof(r.Tcw));
         n_inliers[b] = r.n_inliers;
         if (lm_iters) lm_iters[b] = r.lm_iterations;
         if (final_chi2) final_chi2[b] = r.final_chi2;
+        if (n_trials) n_trials[b] = r.n_trials;
+        if (empty_rounds) empty_rounds[b] = r.empty_rounds;
+        if (ended_rejected) ended_rejected[b] = (uint8_t)r.ended_rejected;
     }
+}
+extern "C" {
+int orc_pose_optimize_batch(int B, int max_points, int max_lines, int max_planes, const int32_t* n_points,
+                            const int32_t* n_lines, const int32_t* n_planes, const uint8_t* pt_valid, const float* pt_xw,
+                            const float* pt_obs, const float* pt_inv_sigma2, const uint8_t* ln_valid, const double* ln_obs,
+                            const double* ln_xw, const float* pl_meas, const uint8_t* pl_valid, const float* pl_world,
+                            const float* Tcw_in, const orc::PoseParams* prm, int mode, int rounds, int its, float* Tcw_out,
+                            uint8_t* pt_outlier, uint8_t* ln_outlier, uint8_t* pl_outlier, int32_t* n_inliers, int32_t* lm_iters,
+                            double* final_chi2) {
+    pose_batch_run(B, max_points, max_lines, max_planes, n_points, n_lines, n_planes, pt_valid, pt_xw, pt_obs, pt_inv_sigma2, ln_valid, ln_obs, ln_xw,
+                   pl_meas, pl_valid, pl_world, Tcw_in, prm, mode, rounds, its, Tcw_out, pt_outlier, ln_outlier, pl_outlier, n_inliers, lm_iters, final_chi2,
+                   nullptr, nullptr, nullptr, nullptr);
+    return 0;
+}
+// The same run with the LM driver's diagnostics per frame: trials [B][rounds * its] (the trial count of every LM iteration run, n_trials[b] of them),
+// empty_rounds [B] (rounds entered with an empty active set), ended_rejected [B] (some round's last evaluation was a rejected trial).
+int orc_pose_optimize_batch_diag(int B, int max_points, int max_lines, int max_planes, const int32_t* n_points,
+                                 const int32_t* n_lines, const int32_t* n_planes, const uint8_t* pt_valid, const float* pt_xw,
+                                 const float* pt_obs, const float* pt_inv_sigma2, const uint8_t* ln_valid, const double* ln_obs,
+                                 const double* ln_xw, const float* pl_meas, const uint8_t* pl_valid, const float* pl_world,
+                                 const float* Tcw_in, const orc::PoseParams* prm, int mode, int rounds, int its, float* Tcw_out,
+                                 uint8_t* pt_outlier, uint8_t* ln_outlier, uint8_t* pl_outlier, int32_t* n_inliers, int32_t* lm_iters,
+                                 double* final_chi2, int32_t* trials, int32_t* n_trials, int32_t* empty_rounds, uint8_t* ended_rejected) {
+    pose_batch_run(B, max_points, max_lines, max_planes, n_points, n_lines, n_planes, pt_valid, pt_xw, pt_obs, pt_inv_sigma2, ln_valid, ln_obs, ln_xw,
+                   pl_meas, pl_valid, pl_world, Tcw_in, prm, mode, rounds, its, Tcw_out, pt_outlier, ln_outlier, pl_outlier, n_inliers, lm_iters, final_chi2,
+                   trials, n_trials, empty_rounds, ended_rejected);
     return 0;
 }
 // n cases x 12 edge classes, same record layout as `ref_opt edges`: err[3], chi2, J[3][6] (22 doubles per class)

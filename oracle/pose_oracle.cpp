@@ -214,6 +214,9 @@ struct Problem {
     Ctx c;
     SE3 T;
     int lm_iters = 0;
+    std::vector<int> trials;       // trial count of every LM iteration run
+    int empty_rounds = 0;          // optimize() calls without an active edge
+    bool ended_rejected = false;   // some optimize() call ended on a rejected trial
 };
 
 void compute_active_errors(Problem& P) { for (int k : P.active) compute_error(P.edges[k], P.T, P.c); }
@@ -229,7 +232,8 @@ double active_robust_chi2(const Problem& P) {   // sparse_optimizer.cpp:100-113
 
 // SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg
 void optimize(Problem& P, int iterations) {
-    if (P.active.empty()) return;   // _ivMap empty -> optimize() returns -1 without touching the vertex
+    if (P.active.empty()) { P.empty_rounds++; return; }   // _ivMap empty -> optimize() returns -1 without touching the vertex
+    bool rejected = false;
     double lambda = -1, ni = 2;
     int nBad = 0;
     for (int it = 0; it < iterations; it++) {
@@ -282,17 +286,20 @@ void optimize(Problem& P, int iterations) {
                 double alpha = 1. - std::pow((2 * rho - 1), 3);
                 alpha = std::min(alpha, 2. / 3.);
                 const double scaleFactor = std::max(1. / 3., alpha);
-                lambda *= scaleFactor; ni = 2; currentChi = tempChi;
+                lambda *= scaleFactor; ni = 2; currentChi = tempChi; rejected = false;
             } else {
                 lambda *= ni; ni *= 2; P.T = backup;   // pop
+                rejected = true;
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
+        P.trials.push_back(qmax);
         if (std::getenv("ORC_POSE_TRACE")) std::fprintf(stderr, "oracle it %d chi2 %.6f lambda %.6f trials %d edges %zu\n", it, currentChi, lambda, qmax, P.active.size());
         if (qmax == 10 || rho == 0) break;                       // Terminate
         if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
         if (nBad >= 3) break;                                    // Terminate
     }
+    if (rejected) P.ended_rejected = true;
 }
 
 // Converter::toSE3Quat (src/Converter.cc:37-47)
@@ -469,6 +476,8 @@ void pose_optimize(const PoseProblem& p, const PoseParams& prm, int mode, int ro
     out.Tcw[12] = out.Tcw[13] = out.Tcw[14] = 0; out.Tcw[15] = 1;
     out.n_inliers = nInitial - nBad;
     out.lm_iterations = P.lm_iters;
+    out.n_trials = (int)P.trials.size(); out.empty_rounds = P.empty_rounds; out.ended_rejected = P.ended_rejected ? 1 : 0;
+    if (out.trials) for (size_t k = 0; k < P.trials.size(); k++) out.trials[k] = P.trials[k];
     P.active.clear();
     for (size_t k = 0; k < P.edges.size(); k++) if (P.edges[k].level == 0) P.active.push_back((int)k);
     compute_active_errors(P);

@@ -36,6 +36,11 @@ struct PoseResult {
     int n_inliers;         // return value of the reference function
     int lm_iterations;     // total LM iterations run (diagnostic)
     double final_chi2;     // robust chi2 after the last round (diagnostic)
+    // diagnostics of the LM driver (tests state with them that a case is in its regime)
+    int32_t* trials = nullptr;   // [rounds * its] or NULL: trial count (1..10) of every LM iteration run, in order; n_trials of them are written
+    int n_trials = 0;
+    int empty_rounds = 0;        // rounds entered with no level-0 edge (optimize() does nothing)
+    int ended_rejected = 0;      // 1 if some round's last evaluation was a rejected trial (classification then reads errors of a pose that was popped)
 };
 
 enum PoseMode { MODE_POSE = 0, MODE_TRANSLATION = 1 };

@@ -326,7 +326,11 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     Frame F;
-    F.np = Bt.n_points[b]; F.nl = Bt.n_lines[b]; F.nm = Bt.n_planes[b];
+    // counts outside their strides (planar_abi.h): points and lines are clamped, a negative plane count is none, and a frame with more planes than
+    // the stride is refused below with no plane touched (nm = 0 empties every plane loop), so nothing outside the frame's own rows and LDS carve is indexed
+    F.np = min(max(Bt.n_points[b], 0), Bt.max_points); F.nl = min(max(Bt.n_lines[b], 0), Bt.max_lines);
+    const bool too_many = Bt.n_planes[b] > Bt.max_planes;
+    F.nm = too_many ? 0 : max(Bt.n_planes[b], 0);
     F.pt_valid = Bt.pt_valid + (size_t)b * Bt.max_points; F.pt_xw = Bt.pt_xw + (size_t)b * Bt.max_points * 3;
     F.pt_obs = Bt.pt_obs + (size_t)b * Bt.max_points * 3; F.pt_is2 = Bt.pt_inv_sigma2 + (size_t)b * Bt.max_points;
     F.ln_valid = Bt.ln_valid + (size_t)b * Bt.max_lines; F.ln_obs = Bt.ln_obs + (size_t)b * Bt.max_lines * 3;
@@ -377,7 +381,6 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
     const int nInitial = (int)cnt[0] + (int)cntp[0];
     const int nEdges = (int)cnt[1] + (int)cntp[1];
     float* Tout = Bt.Tcw_out + (size_t)b * 16;
-    const bool too_many = npe > MAX_PLANE_EDGES || F.nm > Bt.max_planes;
     if (early_translation || nInitial < 3 || too_many) {   // :985 / :3199
         if (tid < 16) Tout[tid] = Tin[tid];
         if (tid == 0) { Bt.n_inliers[b] = too_many ? -1 : 0; if (Bt.lm_iters) Bt.lm_iters[b] = 0; }

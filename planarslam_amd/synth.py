@@ -62,9 +62,9 @@ def _rodrigues(w):
 
 
 def pose_batch(B=4, n_points=1000, n_lines=75, n_planes=4, seed=7, outlier_frac=0.10, stereo_frac=0.85,
-               max_points=None, max_lines=None, max_planes=None, rot_pert=0.02, trans_pert=0.05):
-    """B synthetic frames.  Returns a dict of contiguous numpy arrays (+ 'T_gt' [B,4,4] float64)."""
-    P = TUM3
+               max_points=None, max_lines=None, max_planes=None, rot_pert=0.02, trans_pert=0.05, cam=TUM3):
+    """B synthetic frames seen through the camera `cam` (fx, fy, cx, cy, bf).  Returns a dict of contiguous numpy arrays (+ 'T_gt' [B,4,4] float64)."""
+    P = cam
     MP, ML, MM = max_points or n_points, max_lines or n_lines, max_planes or n_planes
     scale = 1.2 ** np.arange(8)
     out = dict(

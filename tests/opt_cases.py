@@ -41,6 +41,140 @@ POSE_CASES = {
 }
 
 
+# ---- regimes of the pose-only LM that POSE_CASES never reaches (fixtures: tests/golden/opt_pose_regimes.npz) ----
+OTHER_CAM = dict(fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=20.7, angle_info=0.3, distance_info=80.0, parallel_info=0.3, vertical_info=0.3,
+                 plane_chi=90.0, vp_chi=40.0)
+T_W = (0.7, -0.4, 1.3)
+
+
+def pose_turn_world(batch, W, t):
+    """The same frames in a world frame turned by W and shifted by t (X' = W X + t): R' = R W^T, t' = t_cw - R' t; planes n . X + d = 0 become
+    (W n) . X' + (d - (W n) . t) = 0.  Observations are measurements in the camera: unchanged.  The pose-batch twin of turn_world."""
+    W = np.asarray(W, np.float64); t = np.asarray(t, np.float64)
+    out = dict(batch)
+    for key in ("Tcw", "T_gt"):
+        T = np.asarray(batch[key], np.float64).reshape(-1, 4, 4).copy()
+        R = T[:, :3, :3] @ W.T
+        T[:, :3, 3] -= R @ t
+        T[:, :3, :3] = R
+        out[key] = T.astype(np.float32).reshape(-1, 16) if key == "Tcw" else T
+    out["pt_xw"] = (batch["pt_xw"].astype(np.float64) @ W.T + t).astype(np.float32)
+    ln = batch["ln_xw"].reshape(*batch["ln_xw"].shape[:2], 2, 3) @ W.T + t
+    out["ln_xw"] = np.ascontiguousarray(ln.reshape(batch["ln_xw"].shape))
+    pl = batch["pl_world"].astype(np.float64)
+    pl[..., :3] = pl[..., :3] @ W.T
+    pl[..., 3] -= pl[..., :3] @ t
+    out["pl_world"] = pl.astype(np.float32)
+    return out
+
+
+def shuffle_points(batch, seed=1):
+    """The same frames with each frame's points in a seeded random order, so that every sum over them associates differently.
+    Returns (batch, perm): point i of frame b of the result is point perm[b][i] of `batch`."""
+    out = dict(batch)
+    for k in ("pt_valid", "pt_xw", "pt_obs", "pt_inv_sigma2"):
+        out[k] = batch[k].copy()
+    rng = np.random.default_rng(seed)
+    perm = []
+    for b, n in enumerate(np.clip(batch["n_points"], 0, batch["pt_valid"].shape[1])):
+        p = rng.permutation(int(n)); perm.append(p)
+        for k in ("pt_valid", "pt_xw", "pt_obs", "pt_inv_sigma2"):
+            out[k][b, :n] = batch[k][b, :n][p]
+    return out, perm
+
+
+def _turn_base():
+    return synth.pose_batch(B=4, n_points=300, n_lines=30, n_planes=4, seed=211)
+
+
+def _turned(diag):
+    return lambda: pose_turn_world(_turn_base(), np.diag(np.asarray(diag, np.float64)), T_W)
+
+
+def _displace(obs, rng, lo=150.0, hi=300.0):
+    a = rng.uniform(0, 2 * np.pi, len(obs)); r = rng.uniform(lo, hi, len(obs))
+    obs[:, 0] += (r * np.cos(a)).astype(np.float32); obs[:, 1] += (r * np.sin(a)).astype(np.float32)
+
+
+def _emptied():
+    """Frames 0-2: 12 valid points, nothing else, every observation 150-300 px off: round 0 classifies every edge as an outlier and rounds 1-3 start
+    with an empty active set.  Frame 3: half of the points displaced, lines intact.  Frame 4: only the lines displaced."""
+    b = synth.pose_batch(B=5, n_points=12, n_lines=6, n_planes=0, seed=241, outlier_frac=0.0, max_planes=2)
+    b["pt_valid"][:] = 1
+    b["n_lines"][:3] = 0
+    rng = np.random.default_rng(243)
+    for f in range(3):
+        _displace(b["pt_obs"][f], rng)
+    _displace(b["pt_obs"][3, ::2], rng)
+    b["ln_obs"][4, :, 2] += 0.5
+    return b
+
+
+FEW_EDGES_FRAMES = (          # (points, lines, planes [i][kind]) valid per frame
+    (3, 0, ()), (9, 0, ()), (10, 0, ()),
+    (1, 1, ((0, 0),)),                                       # 1 point + 1 line + 1 matched plane: nInitial 3, 4 edges
+    (2, 4, "all"),                                           # translation: returns early with lines and planes present
+    (0, 3, ()), (0, 0, "all"), (3, 0, "all"))
+
+
+def _few_edges():
+    b = synth.pose_batch(B=len(FEW_EDGES_FRAMES), n_points=12, n_lines=6, n_planes=3, seed=251, outlier_frac=0.0)
+    b["pt_valid"][:] = 0; b["ln_valid"][:] = 0; b["pl_valid"][:] = 0
+    for f, (npt, nln, pl) in enumerate(FEW_EDGES_FRAMES):
+        b["pt_valid"][f, :npt] = 1; b["ln_valid"][f, :nln] = 1
+        if pl == "all":
+            b["pl_valid"][f] = 1
+        for i, kind in (() if pl == "all" else pl):
+            b["pl_valid"][f, i, kind] = 1
+    return b
+
+
+def _behind():
+    """Every tenth point reflected through the camera centre of the initial pose: z_c < 0 there (the reference has no depth test in these functions)."""
+    b = synth.pose_batch(B=3, n_points=300, n_lines=20, n_planes=3, seed=261)
+    for f in range(3):
+        T = b["Tcw"][f].astype(np.float64).reshape(4, 4)
+        c = -T[:3, :3].T @ T[:3, 3]
+        b["pt_xw"][f, ::10] = (2 * c - b["pt_xw"][f, ::10].astype(np.float64)).astype(np.float32)
+    return b
+
+
+def _stereo_only():
+    b = synth.pose_batch(B=3, n_points=200, n_lines=15, n_planes=2, seed=283, stereo_frac=1.0)
+    b["pt_valid"][b["pt_obs"][..., 2] < 0] = 0          # a right coordinate left of the image would read as "monocular"
+    return b
+
+
+def _straddle():
+    b = synth.pose_batch(B=3, n_points=257, n_lines=129, n_planes=2, seed=271)
+    b["n_points"][:] = [255, 256, 257]
+    b["n_lines"][:] = [127, 128, 129]
+    return b
+
+
+# name -> (builder, params, modes).  Seeds were selected by the rule that tests/test_oracle_opt_ref.py re-checks (oracle = real reference with a
+# pose gap <= 5e-6, half the 1e-5 gate; the same flags and return values with every frame's points in another order).  Measured: oracle - reference
+# <= 1.5e-7 (few_edges, pose mode; <= 3.8e-9 elsewhere), device - reference <= 1.7e-6 (all_outliers, translation mode; <= 6.9e-8 elsewhere).
+POSE_REGIME_CASES = {
+    "turn_base": (_turn_base, synth.TUM3, (0, 1)),
+    "turned_x": (_turned((1, -1, -1)), synth.TUM3, (0, 1)),        # Eigen's Quaternion(Matrix3) with trace <= 0: largest diagonal element R[0][0],
+    "turned_y": (_turned((-1, 1, -1)), synth.TUM3, (0, 1)),        # R[1][1],
+    "turned_z": (_turned((-1, -1, 1)), synth.TUM3, (0, 1)),        # R[2][2]
+    "planes32": (lambda: synth.pose_batch(B=2, n_points=120, n_lines=10, n_planes=32, seed=223), synth.TUM3, (0, 1)),
+    # 71 440 bytes of LDS per frame: above the 64 KiB that need no opt-in
+    "big_capacity": (lambda: synth.pose_batch(B=2, n_points=300, n_lines=20, n_planes=4, seed=227, max_points=40000, max_lines=64, max_planes=32),
+                     synth.TUM3, (0, 1)),
+    "all_outliers": (lambda: synth.pose_batch(B=3, n_points=200, n_lines=20, n_planes=4, seed=231, outlier_frac=1.0), synth.TUM3, (0, 1)),
+    "emptied": (_emptied, synth.TUM3, (0, 1)),
+    "few_edges": (_few_edges, synth.TUM3, (0, 1)),
+    "mono_only": (lambda: synth.pose_batch(B=3, n_points=200, n_lines=15, n_planes=2, seed=281, stereo_frac=0.0), synth.TUM3, (0, 1)),
+    "stereo_only": (_stereo_only, synth.TUM3, (0, 1)),
+    "behind": (_behind, synth.TUM3, (0, 1)),
+    "other_cam": (lambda: synth.pose_batch(B=3, n_points=300, n_lines=30, n_planes=4, seed=291, cam=OTHER_CAM), OTHER_CAM, (0, 1)),
+    "straddle": (_straddle, synth.TUM3, (0, 1)),
+}
+
+
 def _ba(cur, **kw):
     return synth.ba_local_only(synth.ba_problem(lines_on_kf=cur, **kw))
 

@@ -149,23 +149,30 @@ def pose_params(d):
                        d["vertical_info"], d["plane_chi"], d["vp_chi"])
 
 
-def pose_optimize(batch, params, mode=0, rounds=4, its=10):
-    """CPU oracle of Optimizer::PoseOptimization (mode 0) / TranslationOptimization (mode 1) on a synth.pose_batch()."""
+def pose_optimize(batch, params, mode=0, rounds=4, its=10, out_fill=0):
+    """CPU oracle of Optimizer::PoseOptimization (mode 0) / TranslationOptimization (mode 1) on a synth.pose_batch().  The flag arrays start
+    filled with the byte `out_fill` (what a caller's arrays may hold).  Diagnostics of the LM driver per frame: `trials` (list of arrays: the trial
+    count of every LM iteration run), `empty_rounds` (rounds entered with an empty active set), `ended_rejected` (some round's last evaluation
+    was a rejected trial)."""
     L = lib()
     B = len(batch["n_points"])
     MP, ML, MM = batch["pt_valid"].shape[1], batch["ln_valid"].shape[1], batch["pl_valid"].shape[1]
-    res = dict(Tcw=np.zeros((B, 16), np.float32), pt_outlier=np.zeros((B, MP), np.uint8), ln_outlier=np.zeros((B, ML), np.uint8),
-               pl_outlier=np.zeros((B, MM, 3), np.uint8), n_inliers=np.zeros(B, np.int32), lm_iters=np.zeros(B, np.int32),
+    res = dict(Tcw=np.zeros((B, 16), np.float32), pt_outlier=np.full((B, MP), out_fill, np.uint8), ln_outlier=np.full((B, ML), out_fill, np.uint8),
+               pl_outlier=np.full((B, MM, 3), out_fill, np.uint8), n_inliers=np.zeros(B, np.int32), lm_iters=np.zeros(B, np.int32),
                final_chi2=np.zeros(B, np.float64))
+    trials, n_trials = np.zeros((B, rounds * its), np.int32), np.zeros(B, np.int32)
+    res["empty_rounds"], res["ended_rejected"] = np.zeros(B, np.int32), np.zeros(B, np.uint8)
     prm = pose_params(params)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    L.orc_pose_optimize_batch.restype = C.c_int
-    L.orc_pose_optimize_batch(
+    L.orc_pose_optimize_batch_diag.restype = C.c_int
+    L.orc_pose_optimize_batch_diag(
         C.c_int(B), C.c_int(MP), C.c_int(ML), C.c_int(MM), p(batch["n_points"]), p(batch["n_lines"]), p(batch["n_planes"]),
         p(batch["pt_valid"]), p(batch["pt_xw"]), p(batch["pt_obs"]), p(batch["pt_inv_sigma2"]), p(batch["ln_valid"]),
         p(batch["ln_obs"]), p(batch["ln_xw"]), p(batch["pl_meas"]), p(batch["pl_valid"]), p(batch["pl_world"]), p(batch["Tcw"]),
         C.byref(prm), C.c_int(mode), C.c_int(rounds), C.c_int(its), p(res["Tcw"]), p(res["pt_outlier"]), p(res["ln_outlier"]),
-        p(res["pl_outlier"]), p(res["n_inliers"]), p(res["lm_iters"]), p(res["final_chi2"]))
+        p(res["pl_outlier"]), p(res["n_inliers"]), p(res["lm_iters"]), p(res["final_chi2"]), p(trials), p(n_trials), p(res["empty_rounds"]),
+        p(res["ended_rejected"]))
+    res["trials"] = [trials[b, :n_trials[b]].copy() for b in range(B)]
     return res
 
 

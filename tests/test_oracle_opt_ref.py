@@ -226,3 +226,151 @@ def test_regime_fixture_is_what_the_reference_produces_now(regimes):
     r = ol.run_ref_local_ba(regime_run("reject_robust")[0], TUM3, cur)
     assert np.array_equal(r["kf_Tcw"], regimes["ba/reject_robust/kf_Tcw"]) and np.array_equal(r["lm"], regimes["ba/reject_robust/lm"])
     assert np.array_equal(np.packbits(r["e_outlier"]), regimes["ba/reject_robust/e_outlier"])
+
+
+# ---- regimes of the pose-only LM that POSE_CASES never reaches (opt_cases.POSE_REGIME_CASES, tests/golden/opt_pose_regimes.npz) ----
+@pytest.fixture(scope="module")
+def pose_regimes(golden_dir):
+    return np.load(os.path.join(golden_dir, "opt_pose_regimes.npz"))
+
+
+_POSE_RUNS = {}
+
+
+def pose_regime_run(name, mode):
+    """(batch, params, oracle result) of a pose regime case, solved once per session."""
+    build, params, modes = cases.POSE_REGIME_CASES[name]
+    if (name, "batch") not in _POSE_RUNS:
+        _POSE_RUNS[(name, "batch")] = build()
+    b = _POSE_RUNS[(name, "batch")]
+    if (name, mode) not in _POSE_RUNS:
+        _POSE_RUNS[(name, mode)] = ol.pose_optimize(b, params, mode)
+    return b, params, _POSE_RUNS[(name, mode)]
+
+
+POSE_REGIME_RUNS = [(n, m) for n, (_, _, modes) in cases.POSE_REGIME_CASES.items() for m in modes]
+
+
+@pytest.mark.parametrize("name,mode", POSE_REGIME_RUNS)
+def test_pose_oracle_equals_regime_fixture(pose_regimes, name, mode):
+    b, params, got = pose_regime_run(name, mode)
+    assert len(b["n_points"]) <= 8 and b["n_points"].max() <= 600
+    _check_pose(golden_pose(pose_regimes, name, mode, b), got, b)
+
+
+@pytest.mark.parametrize("name,mode", POSE_REGIME_RUNS)
+def test_pose_regime_cases_meet_the_selection_rule(pose_regimes, name, mode):
+    """As for the BA's reject_* cases: a regime fixture must agree with the real reference to half the 1e-5 gate (the device gets the other half; it
+    differs from the oracle by summation order just as the oracle differs from the reference), and give the same flags and return values when every
+    frame's points, and with them every sum, come in another order.  A seed that fails is replaced."""
+    b, params, got = pose_regime_run(name, mode)
+    assert np.abs(got["Tcw"] - pose_regimes[f"pose/{name}/{mode}/Tcw"]).max() <= 5e-6
+    sb, perm = cases.shuffle_points(b, seed=1)
+    assert any((np.diff(p) < 0).any() for p in perm)
+    s = ol.pose_optimize(sb, params, mode)
+    back = got["pt_outlier"].copy()
+    for f, p in enumerate(perm):
+        back[f, p] = s["pt_outlier"][f, :len(p)]
+    assert np.array_equal(back, got["pt_outlier"])
+    for k in ("ln_outlier", "pl_outlier", "n_inliers"):
+        assert np.array_equal(s[k], got[k]), k
+
+
+def pose_lds_bytes(max_points, max_lines, max_planes):
+    """Dynamic LDS per frame of pose_opt_kernel (pose_launch, planarslam_amd/csrc/pose.hip): the reduction scratch [4][28], the uniform state (28 + 3 * 8),
+    [3 * max_planes][13][3] numeric-Jacobian errors, all doubles; one level byte per point, line and plane edge; 16 bytes of slack."""
+    return (4 * 28 + 28 + 3 * 8 + max_planes * 3 * 39) * 8 + max_points + max_lines + 3 * max_planes + 16
+
+
+def few_edges_counts(mode):
+    """(edges, nInitialCorrespondences) per frame of the few_edges case, from its valid masks (a line is two edges; the translation variant counts only
+    points and builds only the matched-plane edges)."""
+    b = pose_regime_run("few_edges", mode)[0]
+    npt, nln = b["pt_valid"].sum(1).astype(int), b["ln_valid"].sum(1).astype(int)
+    npl = (b["pl_valid"].sum((1, 2)) if mode == 0 else b["pl_valid"][:, :, 0].sum(1)).astype(int)
+    return npt + 2 * nln + npl, (npt + nln + npl if mode == 0 else npt)
+
+
+def test_pose_regime_cases_are_in_their_regimes(golden, pose_regimes):
+    # turned_*: Converter::toSE3Quat's three trace <= 0 branches, and the verdicts of the unturned frames
+    base = pose_regime_run("turn_base", 0)[0]
+    for axis, name in enumerate(("turned_x", "turned_y", "turned_z")):
+        b = pose_regime_run(name, 0)[0]
+        for T in b["Tcw"]:
+            R = T.reshape(4, 4)[:3, :3]
+            assert np.trace(R) <= 0 and int(np.argmax(np.diag(R))) == axis
+        for mode in (0, 1):
+            want, unturned = golden_pose(pose_regimes, name, mode, b), golden_pose(pose_regimes, "turn_base", mode, base)
+            for k in ("pt_outlier", "ln_outlier", "pl_outlier", "n_inliers"):
+                assert np.array_equal(want[k], unturned[k]), (name, mode, k)
+    # emptied / all_outliers: a round entered with an empty active set (the reference prints "0 vertices to optimize" there)
+    for mode in (0, 1):
+        e = pose_regime_run("emptied", mode)[2]
+        assert (e["empty_rounds"][:3] == 3).all() and (e["n_inliers"][:3] == 0).all() and (e["empty_rounds"][3:] == 0).all()
+    assert pose_regimes["pose/all_outliers/1/n_inliers"].min() < 0
+    assert pose_regime_run("all_outliers", 1)[2]["n_inliers"].min() < 0
+    # few_edges: one round only below 10 edges; the early returns
+    for mode in (0, 1):
+        b, _, got = pose_regime_run("few_edges", mode)
+        edges, ninit = few_edges_counts(mode)
+        early = ninit < 3
+        assert early.any() == (mode == 1) and (edges[~early] < 10).any() and (edges[~early] >= 10).any()
+        assert np.array_equal(got["lm_iters"][~early] <= 10, edges[~early] < 10)
+        assert (got["lm_iters"][~early] >= 1).all()
+        want = golden_pose(pose_regimes, "few_edges", mode, b)
+        assert (want["n_inliers"][early] == 0).all() and np.array_equal(want["Tcw"][early], b["Tcw"][early])
+        assert (got["lm_iters"][early] == 0).all()
+    b = pose_regime_run("few_edges", 1)[0]
+    assert b["pt_valid"][4].sum() == 2 and b["ln_valid"][4].sum() == 4 and b["pl_valid"][4].all()      # the early return with lines and planes present
+    assert not golden_pose(pose_regimes, "few_edges", 1, b)["pl_outlier"][4].any()
+    # capacities
+    b = pose_regime_run("big_capacity", 0)[0]
+    assert pose_lds_bytes(b["pt_valid"].shape[1], b["ln_valid"].shape[1], b["pl_valid"].shape[1]) > 65536
+    b = pose_regime_run("planes32", 0)[0]
+    assert b["pl_valid"].shape[1] == 32 and (b["n_planes"] == 32).all() and b["pl_valid"].all()
+    # mono_only / stereo_only / behind / straddle
+    assert (pose_regime_run("mono_only", 0)[0]["pt_obs"][..., 2] < 0).all()
+    b = pose_regime_run("stereo_only", 0)[0]
+    assert (b["pt_obs"][..., 2][b["pt_valid"] != 0] >= 0).all() and b["pt_valid"].sum(1).min() > 150
+    b = pose_regime_run("behind", 0)[0]
+    T = b["Tcw"].astype(np.float64).reshape(-1, 4, 4)
+    zc = np.einsum("bj,bnj->bn", T[:, 2, :3], b["pt_xw"].astype(np.float64)) + T[:, 2, 3:4]
+    assert (zc[:, ::10] < 0).all() and (np.delete(zc, np.s_[::10], axis=1) > 0).all()
+    b = pose_regime_run("straddle", 0)[0]
+    assert b["n_points"].tolist() == [255, 256, 257] and (2 * b["n_lines"]).tolist() == [254, 256, 258]
+    # rejected LM trials stay exercised by the plain cases: a round whose last evaluation is a rejected trial is classified from that trial's pose
+    got = ol.pose_optimize(cases.POSE_CASES["c4_b8"][0](), TUM3, 0)
+    assert got["ended_rejected"].any() and max(int(t.max()) for t in got["trials"]) == 10
+    assert [len(t) for t in got["trials"]] == got["lm_iters"].tolist()
+
+
+def test_pose_oracle_out_fill_and_count_clamp():
+    """The oracle's own side of the contract in include/planar_abi.h: flags are written only where valid and below the count, and counts outside their
+    strides are clamped (more planes than the stride: -1, pose copied, no plane flag touched)."""
+    b = cases.POSE_CASES["ragged"][0]()
+    for mode in (0, 1):
+        z, f = ol.pose_optimize(b, TUM3, mode), ol.pose_optimize(b, TUM3, mode, out_fill=0xA5)
+        assert np.array_equal(z["Tcw"], f["Tcw"]) and np.array_equal(z["n_inliers"], f["n_inliers"])
+        for k, valid, n in (("pt_outlier", "pt_valid", "n_points"), ("ln_outlier", "ln_valid", "n_lines")):
+            live = (b[valid] != 0) & (np.arange(b[valid].shape[1])[None] < b[n][:, None])
+            assert np.array_equal(f[k][live], z[k][live]) and (f[k][~live] == 0xA5).all() and (z[k][~live] == 0).all()
+    over = dict(b)
+    over["n_points"] = b["n_points"].copy(); over["n_points"][1] = b["pt_valid"].shape[1] + 5
+    over["n_planes"] = b["n_planes"].copy(); over["n_planes"][3] = b["pl_valid"].shape[1] + 1
+    full = dict(b); full["n_points"] = b["n_points"].copy(); full["n_points"][1] = b["pt_valid"].shape[1]
+    got, want = ol.pose_optimize(over, TUM3, 0, out_fill=0xA5), ol.pose_optimize(full, TUM3, 0, out_fill=0xA5)
+    keep = np.arange(len(b["n_points"])) != 3
+    for k in ("Tcw", "n_inliers", "pt_outlier", "ln_outlier", "pl_outlier"):
+        assert np.array_equal(got[k][keep], want[k][keep]), k
+    assert got["n_inliers"][3] == -1 and np.array_equal(got["Tcw"][3], b["Tcw"][3]) and (got["pl_outlier"][3] == 0xA5).all()
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/ref_opt not built")
+def test_pose_regime_fixture_is_what_the_reference_produces_now(pose_regimes):
+    b, params, _ = pose_regime_run("few_edges", 0)
+    for mode in (0, 1):
+        r = ol.run_ref_pose(b, params, mode)
+        assert np.array_equal(r["Tcw"], pose_regimes[f"pose/few_edges/{mode}/Tcw"])
+        assert np.array_equal(r["n_inliers"], pose_regimes[f"pose/few_edges/{mode}/n_inliers"])
+        for k in ("pt_outlier", "ln_outlier", "pl_outlier"):
+            assert np.array_equal(np.packbits(r[k]), pose_regimes[f"pose/few_edges/{mode}/{k}"]), k

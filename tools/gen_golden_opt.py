@@ -1,4 +1,4 @@
-"""Generate tests/golden/opt_ref.npz and tests/golden/opt_ba_regimes.npz (argument "ref" or "regimes": only that file) from the REAL reference optimiser: oracle/_ref/ref_opt = src/Optimizer.cc + src/Converter.cc + the
+"""Generate tests/golden/opt_ref.npz, tests/golden/opt_ba_regimes.npz and tests/golden/opt_pose_regimes.npz (argument "ref", "regimes" or "pose_regimes": only that file) from the REAL reference optimiser: oracle/_ref/ref_opt = src/Optimizer.cc + src/Converter.cc + the
 vendored g2o + g2oAddition/*.h + include/EdgeLine.h compiled where they lie (recipe: oracle/Makefile).  Inputs are regenerated from seeds
 (tests/opt_cases.py); only the reference's outputs are stored."""
 import os
@@ -12,7 +12,7 @@ import oracle_lib as O  # noqa: E402
 import opt_cases as cases  # noqa: E402
 from planarslam_amd import synth  # noqa: E402
 
-which = sys.argv[1:] or ["ref", "regimes"]
+which = sys.argv[1:] or ["ref", "regimes", "pose_regimes"]
 
 
 def save(fname, arrays):
@@ -28,6 +28,20 @@ def ba_outputs(out, table):
         out[f"ba/{name}/kf_Tcw"] = r["kf_Tcw"]; out[f"ba/{name}/lm"] = r["lm"]; out[f"ba/{name}/e_outlier"] = np.packbits(r["e_outlier"])
 
 
+def pose_outputs(out, name, b, params, modes):
+    for mode in modes:
+        r = O.run_ref_pose(b, params, mode)
+        for k in ("Tcw", "n_inliers"):
+            out[f"pose/{name}/{mode}/{k}"] = r[k]
+        for k in ("pt_outlier", "ln_outlier", "pl_outlier"):
+            out[f"pose/{name}/{mode}/{k}"] = np.packbits(r[k])
+
+
+if "pose_regimes" in which:
+    out = {}
+    for name, (build, params, modes) in cases.POSE_REGIME_CASES.items():
+        pose_outputs(out, name, build(), params, modes)
+    save("opt_pose_regimes.npz", out)
 if "regimes" in which:
     out = {}
     ba_outputs(out, cases.BA_REGIME_CASES)
@@ -36,13 +50,7 @@ if "ref" not in which:
     sys.exit(0)
 out = {}
 for name, (build, modes) in cases.POSE_CASES.items():
-    b = build()
-    for mode in modes:
-        r = O.run_ref_pose(b, synth.TUM3, mode)
-        for k in ("Tcw", "n_inliers"):
-            out[f"pose/{name}/{mode}/{k}"] = r[k]
-        for k in ("pt_outlier", "ln_outlier", "pl_outlier"):
-            out[f"pose/{name}/{mode}/{k}"] = np.packbits(r[k])
+    pose_outputs(out, name, build(), synth.TUM3, modes)
 ba_outputs(out, cases.BA_CASES)
 n, seed = cases.EDGE_CASES
 e, H = O.run_ref_edges(O._edge_cases(n, seed), synth.TUM3)
