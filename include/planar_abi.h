@@ -670,6 +670,51 @@ int planar_horn_ransac_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, cons
                            int32_t* d_its_done, int32_t* d_best_inliers, float* d_best_R, float* d_best_t, float* d_best_s, int32_t* d_found, int32_t* d_no_more,
                            int32_t* d_n_inliers, uint8_t* d_inliers, float* d_R12, float* d_t12, float* d_s12, int32_t* d_match12_inl, double* d_S12);
 
+/* PnPsolver (src/PnPsolver.cc: EPnP inside a RANSAC), batched over B independent (lost frame, candidate key frame) problems: step 3 of Tracking::Relocalization
+ * (src/Tracking.cc:2554-2698), between planar_search_by_bow, whose match array it takes as written, and planar_pose_opt.  Each problem has the semantics of one
+ * PnPsolver(F, vpMapPointMatches), SetRansacParameters(prob, min_inliers, max_its, min_set, epsilon, th2) and ONE iterate(n_iterations, bNoMore, vbInliers, nInliers);
+ * the solver's state is passed in and out, so a later call is the same solver's next iterate.
+ *   fr: the lost frames: n, keys_un (pt and octave), fx fy cx cy and scale_factors (mvLevelSigma2[octave] = sf * sf) are read; nothing else is and may be NULL.
+ *   kf_usable [B][kf_stride], kf_xw [B][kf_stride][3]: the candidate's map points by key-frame feature: whether it holds a point that is not bad, and GetWorldPos().
+ *   match [B][fr->stride]: exactly what planar_search_by_bow writes: the key-frame feature matched to key point i of the frame, or -1.  i is a correspondence where
+ *       0 <= match[i] < kf_stride and kf_usable[match[i]] is set.  Correspondences are numbered in ascending i (mvKeyPointIndices): that order decides what a draw picks.
+ *   seeds[b]: the problem's draws are glibc's rand() after srand(seeds[b]) (the reference's stream is process-global; a stream per item is the rule
+ *       planar_is_line_good set).  Iteration k, counted from the solver's construction, uses draws 4k .. 4k + 3, so the place in the stream follows from its_done.  A draw
+ *       is DUtils::Random::RandomInt(0, size - 1) and the four picks follow the swap-with-back rule of :191-201.
+ *   State of the solver, in/out (zero for a new solver): its_done [B] = mnIterations; best_inliers [B] = mnBestInliers; best_set [B][fr->stride] = mvbBestInliers, by key
+ *       point of the frame (only entries of correspondences are ever written); best_Tcw [B][16] = mBestTcw.  Refine()'s outcome on the best set is no state: it
+ *       depends on that set alone and is computed again when a later call first needs it.
+ *   found[b]: 1 where the reference returns a non-empty matrix.  no_more[b]: bNoMore.  n_inliers[b]: nInliers.  inliers[b][i]: vbInliers, by key point of the frame; the
+ *       first n[b] entries of a row are written (zero unless found), the rest is left alone.  Tcw [B][16] row-major float: mRefinedTcw or mBestTcw, mRi / mti narrowed as
+ *       convertTo(CV_32F) does; zero where found is 0.
+ * mRansacMinInliers = max(int(N * epsilon), min_inliers, min_set), epsilon = max(epsilon, (float)mRansacMinInliers / N) and mRansacMaxIts = max(1, min(ceil(log(1 - prob)
+ * / log(1 - pow(epsilon, 3))), max_its)) (the exponent is 3 although the minimal set is 4), 1 where mRansacMinInliers == N, are host libm arithmetic: the library
+ * evaluates the reference's expressions on the host for every N, keeps the table in the context per (prob, min_inliers, max_its, epsilon) and the kernel reads it.
+ * Kept as the reference has them: the loop runs while mnIterations < mRansacMaxIts OR this call has run fewer than n_iterations, so the first call of a solver runs
+ * max(mRansacMaxIts, n_iterations) iterations unless a Refine returns, and find() is n_iterations = mRansacMaxIts; N < mRansacMinInliers gives no_more before any
+ * draw; the best is replaced on strict >; Refine() runs whenever mnInliersi >= mRansacMinInliers, on the best set, and returns on strict mnInliersi >
+ * mRansacMinInliers; at the end the best is returned when mnIterations >= mRansacMaxIts and mnBestInliers >= mRansacMinInliers (found = 1 with no_more = 1);
+ * maxError = sigma2 * th2 is a float product; CheckInliers narrows Xc, Yc, 1 / Zc to float, has ue, ve in double and distX, distY, error2 in float, and no positivity
+ * gate on Zc.  EPnP itself runs in double through OpenCV's JacobiSVD and SVBackSubst as restated in csrc/epnp_arith.h, the RNG(0x12345678) tail for a zero singular
+ * value included (coplanar sets reach it).  qr_solve's early return on a singular A leaves X as it was; the reference's X is uninitialised there, here it is the
+ * previous step's or zero.
+ * Defined where the reference is not: n[b] is clamped to [0, stride]; an octave outside the levels is taken modulo PLANAR_MAX_LEVELS; a negative its_done counts as 0 and one above
+ * PLANAR_PNP_MAX_ITS_DONE as that value (one thread walks 4 * its_done values of the stream before the call's first draw, about 10 ns each, so a solver resumed
+ * after thousands of iterations pays for them again on every call).
+ * PLANAR_EINVAL, before any device call: a null required array, B < 1, fr->stride or kf_stride outside [1, PLANAR_MAX_FRAME_KEYS], n_iterations or max_its outside
+ * [1, PLANAR_PNP_MAX_ITS] (the draws and counts of one call are kept on chip; the reference passes 300 and 5), prob outside (0, 1), min_set != 4 (the only value the
+ * reference passes; EPnP on another minimal set is simply not built).
+ * The _dev flavour keeps the correspondences of frames above 512 key points in the context's scratch block. */
+#define PLANAR_PNP_MAX_ITS 1024
+#define PLANAR_PNP_MAX_ITS_DONE (1 << 20)
+int planar_pnp_ransac(planar_ctx* ctx, const planar_frame_view* fr, const uint8_t* kf_usable, const float* kf_xw, int kf_stride, const int32_t* match, double prob,
+                      int min_inliers, int max_its, int min_set, float epsilon, float th2, int n_iterations, const uint32_t* seeds, int32_t* its_done,
+                      int32_t* best_inliers, uint8_t* best_set, float* best_Tcw, int32_t* found, int32_t* no_more, int32_t* n_inliers, uint8_t* inliers, float* Tcw);
+int planar_pnp_ransac_dev(planar_ctx* ctx, const planar_frame_view* d_fr, const uint8_t* d_kf_usable, const float* d_kf_xw, int kf_stride, const int32_t* d_match,
+                          double prob, int min_inliers, int max_its, int min_set, float epsilon, float th2, int n_iterations, const uint32_t* d_seeds,
+                          int32_t* d_its_done, int32_t* d_best_inliers, uint8_t* d_best_set, float* d_best_Tcw, int32_t* d_found, int32_t* d_no_more,
+                          int32_t* d_n_inliers, uint8_t* d_inliers, float* d_Tcw);
+
 /* ORBmatcher(nn_ratio, check_orientation)::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (src/ORBmatcher.cc:526-659), batched
  * over B independent key-frame pairs (LoopClosing::ComputeSim3 calls it with ORBmatcher(0.75, true), once per candidate).  Both FeatureVectors are passed as one
  * node id per feature (-1: in no node), as planar_search_by_bow takes them.  Probes are key frame 1's features in (node ascending, feature index ascending)

@@ -11,6 +11,7 @@
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
+//   Planar_SLAM::PnPsolver  <- include/PnPsolver.h, src/PnPsolver.cc                                    (PLANAR_ADAPTERS_WITH_PNP_SOLVER)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1674,3 +1675,109 @@ protected:
 
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_SIM3_SOLVER
+
+// ---- PnPsolver (reference include/PnPsolver.h, src/PnPsolver.cc): the class Tracking::Relocalization constructs per candidate key frame (src/Tracking.cc:2590-2625),
+//      with the reference's signatures.  Enabled with PLANAR_ADAPTERS_WITH_PNP_SOLVER, after the reference's Frame.h and MapPoint.h and INSTEAD of its PnPsolver.h; leave
+//      src/PnPsolver.cc out.  The constructor gathers what the reference's does (F.mvKeysUn, F.mvScaleFactors, whose squares are mvLevelSigma2, F.fx fy cx cy, isBad(),
+//      GetWorldPos()): key point i is matched to "feature" i of a candidate that holds vpMapPointMatches[i].  iterate() runs planar_pnp_ransac with B = 1 on the tracking
+//      context and carries the state (mnIterations, mnBestInliers, mvbBestInliers, mBestTcw) in the object.  SetRansacParameters evaluates the reference's chain for
+//      mRansacMinInliers and mRansacMaxIts (:129-152), the same libm doubles as the library's table, because find() is iterate(mRansacMaxIts).  The draws come from this
+//      solver's own glibc stream, srand(seed) with the seed of SetSeed (0 unless set): the reference's solvers share the process's rand().  A failing call returns an
+//      empty matrix with bNoMore set.
+#ifdef PLANAR_ADAPTERS_WITH_PNP_SOLVER
+namespace Planar_SLAM {
+
+class PnPsolver {
+public:
+    PnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches) : mnIterations(0), mnBestInliers(0), N(0), mSeed(0) {
+        mnMatches = vpMapPointMatches.size();
+        mn = (int32_t)(mnMatches < F.mvKeysUn.size() ? mnMatches : F.mvKeysUn.size());
+        const size_t S = mn > 0 ? (size_t)mn : 1;
+        mvKeys.resize(S); mvUsable.assign(S, 0); mvXw.assign(S * 3, 0.f); mvMatch.assign(S, -1); mvbBestInliers.assign(S, 0);
+        for (int i = 0; i < mn; i++) {
+            std::memcpy(&mvKeys[i], &F.mvKeysUn[i], sizeof(planar_keypoint));
+            MapPoint* pMP = vpMapPointMatches[i];
+            if (!pMP) continue;
+            mvMatch[i] = i;
+            if (pMP->isBad()) continue;
+            mvUsable[i] = 1;
+            cv::Mat Pos = pMP->GetWorldPos();
+            for (int k = 0; k < 3; k++) mvXw[3 * i + k] = Pos.at<float>(k);
+            N++;
+        }
+        std::memset(&mView, 0, sizeof(mView));
+        mView.B = 1; mView.stride = (int32_t)S;
+        mView.fx = F.fx; mView.fy = F.fy; mView.cx = F.cx; mView.cy = F.cy;
+        for (int l = 0; l < PLANAR_MAX_LEVELS; l++) mView.scale_factors[l] = 1.f;
+        for (size_t l = 0; l < F.mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) mView.scale_factors[l] = F.mvScaleFactors[l];
+        for (int k = 0; k < 16; k++) mBestTcw[k] = 0.f;
+        SetRansacParameters();
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4, float th2 = 5.991) {
+        mRansacProb = probability; mRansacMinSet = minSet; mRansacEpsilon = epsilon; mRansacTh = th2;
+        mMinInliersGiven = minInliers; mMaxItsGiven = maxIterations;
+        int nMinInliers = N * epsilon;
+        if (nMinInliers < minInliers) nMinInliers = minInliers;
+        if (nMinInliers < minSet) nMinInliers = minSet;
+        mRansacMinInliers = nMinInliers;
+        if (epsilon < (float)mRansacMinInliers / N) epsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N) nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
+            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);   // what x86-64's conversion gives where the double is no int
+        }
+        const int m = nIterations < maxIterations ? nIterations : maxIterations;
+        mRansacMaxIts = m > 1 ? m : 1;
+    }
+    void SetSeed(unsigned seed) { mSeed = seed; }
+    cv::Mat find(std::vector<bool>& vbInliers, int& nInliers) {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers);
+    }
+    cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+        using namespace planar_adapter;
+        bNoMore = true;
+        vbInliers.clear();
+        nInliers = 0;
+        if (mn > PLANAR_MAX_FRAME_KEYS) return cv::Mat();
+        int32_t found = 0, no_more = 1, n_inl = 0;
+        std::vector<uint8_t> inl((size_t)mView.stride, 0);
+        float T[16];
+        mView.n = &mn; mView.keys_un = mvKeys.data();                                       // here, not in the constructor: the object may have been copied
+        {
+            Runtime::Lane& L = Runtime::get().lane(TRACKING);
+            std::lock_guard<std::mutex> g(L.mu);
+            if (!ok(planar_pnp_ransac(L.ctx, &mView, mvUsable.data(), mvXw.data(), mView.stride, mvMatch.data(), mRansacProb, mMinInliersGiven, mMaxItsGiven,
+                                      mRansacMinSet, mRansacEpsilon, mRansacTh, nIterations, &mSeed, &mnIterations, &mnBestInliers, mvbBestInliers.data(), mBestTcw,
+                                      &found, &no_more, &n_inl, inl.data(), T), "planar_pnp_ransac")) return cv::Mat();
+        }
+        bNoMore = no_more != 0;
+        if (!found) return cv::Mat();
+        nInliers = n_inl;
+        vbInliers = std::vector<bool>(mnMatches, false);
+        for (int i = 0; i < mn; i++) vbInliers[i] = inl[i] != 0;
+        cv::Mat Tcw(4, 4, CV_32F);
+        for (int k = 0; k < 16; k++) Tcw.at<float>(k / 4, k % 4) = T[k];
+        return Tcw;
+    }
+
+protected:
+    size_t mnMatches;
+    int32_t mn;
+    std::vector<planar_keypoint> mvKeys;
+    std::vector<uint8_t> mvUsable, mvbBestInliers;
+    std::vector<float> mvXw;
+    std::vector<int32_t> mvMatch;
+    planar_frame_view mView;
+    int32_t mnIterations, mnBestInliers;
+    float mBestTcw[16];
+    int N;
+    uint32_t mSeed;
+    double mRansacProb;
+    int mRansacMinInliers, mRansacMaxIts, mRansacMinSet, mMinInliersGiven, mMaxItsGiven;
+    float mRansacEpsilon, mRansacTh;
+};
+
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_PNP_SOLVER

@@ -256,6 +256,8 @@ _SIGS = {
     "planar_optimize_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_float, C.c_int] + [C.c_void_p] * 3),
     "planar_horn_ransac": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 15),
     "planar_horn_ransac_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 15),
+    "planar_pnp_ransac": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int] + [C.c_void_p] * 10),
+    "planar_pnp_ransac_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int] + [C.c_void_p] * 10),
     "planar_is_line_good": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_is_line_good_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 8),
     "planar_normals_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

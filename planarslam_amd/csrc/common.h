@@ -202,6 +202,13 @@ struct planar_ctx {
     std::vector<int32_t> horn_table_host;
     double horn_prob = -1;
     int horn_min_inliers = 0, horn_max_its = 0;
+    // planar_pnp_ransac: mRansacMaxIts, then the adjusted mRansacMinInliers, over N in [0, PLANAR_MAX_FRAME_KEYS], kept per (prob, min_inliers, max_its, epsilon)
+    // (pnpransac.hip)
+    planar::DevBuf pnp_table;
+    std::vector<int32_t> pnp_table_host;
+    double pnp_prob = -1;
+    int pnp_min_inliers = 0, pnp_max_its = 0;
+    float pnp_epsilon = 0;
     // Optional side stream for the one-wavefront-per-frame kernels of the extractors (PEAC clustering, LSD region growing): planar_ctx_set_seq_stream.  Such a kernel
     // is latency-bound and occupies a CU for tens of milliseconds with four wavefronts; on a CU-masked stream (planar_cu_stream_create) it stays on a subset of the
     // CUs while the wide kernels of `stream` keep the rest.  seq_begin() / seq_end() bracket the launch: fork by event from `stream`, join back into it.

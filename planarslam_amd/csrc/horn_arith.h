@@ -94,6 +94,23 @@ HORN_HD void pick3(int r0, int r1, int r2, int N, int idx[3]) {
     idx[2] = c == b ? back : (c == a ? N - 1 : c);
 }
 
+// PnPsolver::iterate (reference src/PnPsolver.cc:191-201): the four picks out of vAvailableIndices = 0 .. N-1 with the swap-with-back rule, N >= 4, in closed
+// form: at most three positions hold an entry that is no longer their own index
+HORN_HD void pick4(int r0, int r1, int r2, int r3, int N, int idx[4]) {
+    const int p0 = random_int(r0, N), p1 = random_int(r1, N - 1), p2 = random_int(r2, N - 2), p3 = random_int(r3, N - 3);
+    // entry at position p after the earlier swaps: position q_k was overwritten with the entry of the then-last position
+    const int v0 = p0;                                   // list = identity
+    const int e0 = N - 1;                                // position p0 now holds entry(N - 1) = N - 1
+    const int v1 = p1 == p0 ? e0 : p1;
+    const int b1 = (N - 2) == p0 ? e0 : N - 2;           // the entry of the last position (N - 2) of the second list, moved into p1
+    // third list (length N - 2): position p1 holds b1, position p0 holds e0 unless p1 == p0 overwrote it
+    const int v2 = p2 == p1 ? b1 : (p2 == p0 ? e0 : p2);
+    const int l3 = N - 3;                                // the last position of the third list, moved into p2
+    const int b2 = l3 == p1 ? b1 : (l3 == p0 ? e0 : l3);
+    const int v3 = p3 == p2 ? b2 : (p3 == p1 ? b1 : (p3 == p0 ? e0 : p3));
+    idx[0] = v0; idx[1] = v1; idx[2] = v2; idx[3] = v3;
+}
+
 // ---- cv::eigen of a symmetric 4x4 CV_32F: JacobiImpl_<float> (OpenCV 3.4 core/src/lapack.cpp), eigenvalues descending, eigenvectors in rows ----
 HORN_HD float cv_hypot(float a, float b) {
     a = fabsf(a); b = fabsf(b);
