@@ -20,7 +20,7 @@
 //                       reference => bit-identical), min/max and NFA pixel counts are order-free wave reductions.
 //   (K5, the Sobel images of the 5x5-blurred image, is fused into K7 since round 5)
 //   K6 lsd_keylines     per frame: KeyLine fields, libstdc++ std::sort emulation on `response`, keep max_lines, equations
-//   K7 lbd_describe     one wavefront per kept line: 63 support rows on 63 lanes, band sums in reference order
+//   K7 lbd_describe     one wavefront per kept line: 63 support rows on 63 lanes (64 samples at a time from an LDS tile), band sums in reference order
 // HBM traffic is small (a 640x480 frame: 0.3 MB in, 3 KB out, ~5 MB of L2-resident intermediates); K4 is latency bound.
 #include "common.h"
 #include "ref_arith.h"
@@ -1431,6 +1431,13 @@ __global__ __launch_bounds__(64) void lsd_keylines(const Plan* __restrict__ plan
 
 // ---- K7: LBD (BinaryDescriptor::computeLBD + binaryConversion), one wavefront per kept line ----------------------------
 constexpr int NUM_OF_BANDS = 9, WIDTH_OF_BAND = 7, LSP_H = 63;
+// lbd_describe's LDS tile: the box of one chunk of LBD_CH samples of the 63 support rows, at most LBD_BOX pixels per side.  A rotated 62 x (LBD_CH - 1) rectangle
+// spans at most sqrt(62^2 + (LBD_CH - 1)^2) <= (63 + LBD_CH) / sqrt(2) per axis; + 1 for the rounding of its corners, + 2 for the Sobel halo, + 1 to count pixels
+// = ceil((63 + LBD_CH) / sqrt(2)) + 4, and LBD_BOX leaves two more for the float chains' accumulated rounding.  A row is LBD_PITCH_DW words: the box + up to 3 bytes
+// of misalignment, and an ODD number of words, so that the 63 lanes of a horizontal line (one column, consecutive rows) read 63 different banks.
+constexpr int LBD_CH = 64, LBD_BOX = 96, LBD_PITCH_DW = 25;
+static_assert(2 * (LBD_BOX - 6) * (LBD_BOX - 6) >= (LSP_H + LBD_CH) * (LSP_H + LBD_CH), "LBD_BOX >= ceil((63 + LBD_CH) / sqrt(2)) + 4, and two to spare");
+static_assert(LBD_PITCH_DW * 4 >= LBD_BOX + 3 && (LBD_PITCH_DW & 1) == 1, "a tile row holds the box and its misalignment; odd pitch in words");
 __constant__ int LBD_COMB[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}, {1, 2}, {1, 3}, {1, 4}, {1, 5}, {1, 6}, {2, 3}, {2, 4}, {2, 5}, {2, 6}, {2, 7},
                                     {2, 8}, {3, 4}, {3, 5}, {3, 6}, {3, 7}, {3, 8}, {4, 5}, {4, 6}, {4, 7}, {4, 8}, {5, 6}, {5, 7}, {5, 8}, {6, 7}, {6, 8}, {7, 8}};
 
@@ -1438,6 +1445,7 @@ __global__ __launch_bounds__(64) void lbd_describe(const Plan* __restrict__ plan
                                                    uint8_t* __restrict__ out_desc, int B) {
     __shared__ float row[LSP_H][8];    // pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2 row sums (after the global weight)
     __shared__ float des[NUM_OF_BANDS * 8];
+    __shared__ uint32_t tile[LBD_BOX * LBD_PITCH_DW];
     const Plan& P = *plan;
     int b, li;
     xcd_frame_block(max_lines, B, b, li);           // a frame's support regions overlap: its lines on one XCD (common.h)
@@ -1446,10 +1454,13 @@ __global__ __launch_bounds__(64) void lbd_describe(const Plan* __restrict__ plan
     const Misc* misc = miscs + b;
     if (li >= misc->n_kl) return;
     const planar_keyline L = ((const planar_keyline*)(F + P.off_kl))[li];
-    // the Sobel derivatives (16S, 3x3, BORDER_REFLECT_101) of the 5x5-blurred image are taken where they are read: eight byte reads of a 0.3 MB image per sample
-    // instead of two 2-byte reads of two 0.6 MB images that a separate kernel had to write first (rounds 1-4: lbd_sobel, 1.9 GB + lbd_describe 6.1 GB per 1024 frames)
+    // the Sobel derivatives (16S, 3x3, BORDER_REFLECT_101) of the 5x5-blurred image are taken where they are read (no Sobel images, no lbd_sobel launch, since
+    // round 5).  The eight bytes of a sample come from an LDS tile, not from the image: with a lane per support row, one byte load of the wavefront touched up to
+    // 63 cache lines unless the line was vertical, 512 such loads per 64 samples, and the kernel spent its time in the address path (wait 0.64 of its resident cycles
+    // at 0.14 GB of fetches per 1024 frames).  The line is walked in chunks of LBD_CH samples; the 63 x LBD_CH rotated rectangle of a chunk, with its Sobel halo, is
+    // fetched once with coalesced 32-bit loads.
     const uint8_t* S5 = F + P.off_blur5;
-    const short realWidth = (short)P.W, imageWidth = (short)(P.W - 1), imageHeight = (short)(P.H - 1);
+    const short imageWidth = (short)(P.W - 1), imageHeight = (short)(P.H - 1);
     const short lengthOfLSP = (short)L.num_pixels;
     const short halfWidth = (lengthOfLSP - 1) / 2, halfHeight = (LSP_H - 1) / 2;
     const float lineMiddlePointX = (float)(0.5 * (L.s_oct_x + L.e_oct_x));
@@ -1457,30 +1468,71 @@ __global__ __launch_bounds__(64) void lbd_describe(const Plan* __restrict__ plan
     float dL[2], dO[2];
     dL[0] = (float)cos((double)L.angle); dL[1] = (float)sin((double)L.angle);
     dO[0] = -dL[1]; dO[1] = dL[0];
-    if (lane < LSP_H) {
-        float sCorX0 = -dL[0] * halfWidth + dL[1] * halfHeight + lineMiddlePointX;
-        float sCorY0 = -dL[1] * halfWidth - dL[0] * halfHeight + lineMiddlePointY;
-        for (int h = 0; h < lane; h++) { sCorX0 -= dL[1]; sCorY0 += dL[0]; }
-        float sCorX = sCorX0, sCorY = sCorY0;
-        float pgdLRowSum = 0, ngdLRowSum = 0, pgdORowSum = 0, ngdORowSum = 0;
-        for (short wID = 0; wID < lengthOfLSP; wID++) {
-            short tempCor = (short)roundf(sCorX);
-            const short xCor = (tempCor < 0) ? 0 : (tempCor > imageWidth) ? imageWidth : tempCor;
-            tempCor = (short)roundf(sCorY);
-            const short yCor = (tempCor < 0) ? 0 : (tempCor > imageHeight) ? imageHeight : tempCor;
-            const uint8_t* r0 = S5 + (size_t)reflect101(yCor - 1, P.H) * realWidth;
-            const uint8_t* r1 = S5 + (size_t)yCor * realWidth;
-            const uint8_t* r2 = S5 + (size_t)reflect101(yCor + 1, P.H) * realWidth;
-            const int xm = reflect101(xCor - 1, P.W), xp = reflect101(xCor + 1, P.W);
-            const int a0 = r0[xm], a1 = r0[xCor], a2 = r0[xp], b0 = r1[xm], b2 = r1[xp], c0 = r2[xm], c1 = r2[xCor], c2 = r2[xp];
-            const short dx = (short)((a2 - a0) + 2 * (b2 - b0) + (c2 - c0)), dy = (short)((c0 - a0) + 2 * (c1 - a1) + (c2 - a2));
-            const float gDL = dx * dL[0] + dy * dL[1];
-            const float gDO = dx * dO[0] + dy * dO[1];
-            if (gDL > 0) pgdLRowSum += gDL; else ngdLRowSum -= gDL;
-            if (gDO > 0) pgdORowSum += gDO; else ngdORowSum -= gDO;
-            sCorX += dL[0];
-            sCorY += dL[1];
+    const bool has_row = lane < LSP_H;              // (lane 63 has no support row; it helps to fetch the tiles)
+    float sCorX = -dL[0] * halfWidth + dL[1] * halfHeight + lineMiddlePointX;
+    float sCorY = -dL[1] * halfWidth - dL[0] * halfHeight + lineMiddlePointY;
+    for (int h = 0; h < lane; h++) { sCorX -= dL[1]; sCorY += dL[0]; }
+    float pgdLRowSum = 0, ngdLRowSum = 0, pgdORowSum = 0, ngdORowSum = 0;
+    auto clampX = [&](float v) -> short { const short t = (short)roundf(v); return (t < 0) ? (short)0 : (t > imageWidth) ? imageWidth : t; };
+    auto clampY = [&](float v) -> short { const short t = (short)roundf(v); return (t < 0) ? (short)0 : (t > imageHeight) ? imageHeight : t; };
+    const int W = P.W, H = P.H, w3 = W & 3;
+    for (int w0 = 0; w0 < lengthOfLSP; w0 += LBD_CH) {
+        const int n = min(LBD_CH, (int)lengthOfLSP - w0);
+        // The chunk's box: every lane's start is an iterate of ONE float chain (h steps of -dL[1] / +dL[0]), and a sample is k further additions of one constant,
+        // which is monotone in its operand under round-to-nearest; roundf and the clamp are monotone too.  So the clamped coordinates are monotone in the row AND
+        // in the sample, and their minimum and maximum over the 63 rows at the chunk's first and last sample - which bound every sample between them - are taken
+        // at rows 0 and 62.  (Row 62 is 62 unit steps across from row 0, the last sample at most LBD_CH - 1 along: an extent of at most
+        // sqrt(62^2 + (LBD_CH - 1)^2) + 1 for the rounding + 2 for the halo, below LBD_BOX by the static_assert's margin.)
+        float eX = sCorX, eY = sCorY;
+        for (int k = 1; k < n; k++) { eX += dL[0]; eY += dL[1]; }
+        const int xs = clampX(sCorX), ys = clampY(sCorY), xe = clampX(eX), ye = clampY(eY);
+        const int xs0 = __builtin_amdgcn_readlane(xs, 0), xs1 = __builtin_amdgcn_readlane(xs, LSP_H - 1), xe0 = __builtin_amdgcn_readlane(xe, 0), xe1 = __builtin_amdgcn_readlane(xe, LSP_H - 1);
+        const int ys0 = __builtin_amdgcn_readlane(ys, 0), ys1 = __builtin_amdgcn_readlane(ys, LSP_H - 1), ye0 = __builtin_amdgcn_readlane(ye, 0), ye1 = __builtin_amdgcn_readlane(ye, LSP_H - 1);
+        // ... grown by the Sobel halo and clipped to the image.  reflect101 of a clamped coordinate -1 / +1 stays inside: c - 1 >= 0 is at least the unclipped
+        // minimum - 1, and c = 0 reflects to 1 <= min(max + 1, W - 1) as W >= 2; c + 1 <= W - 1 is at most the maximum + 1, and c = W - 1 reflects to
+        // W - 2 >= max(min - 1, 0) as min <= W - 1.  The same for rows.  (planar_lsd_create refuses images below 32 x 32.)
+        const int x_lo = max(min(min(xs0, xs1), min(xe0, xe1)) - 1, 0), x_hi = min(max(max(xs0, xs1), max(xe0, xe1)) + 1, W - 1);
+        const int y_lo = max(min(min(ys0, ys1), min(ye0, ye1)) - 1, 0), y_hi = min(max(max(ys0, ys1), max(ye0, ye1)) + 1, H - 1);
+        const int bw = x_hi - x_lo + 1, bh = min(y_hi - y_lo + 1, LBD_BOX);
+        // The tile's row r holds the aligned 32-bit words around bytes [x_lo, x_hi] of image row y_lo + r: it begins mis(r) bytes left of the box (the blurred
+        // image has pitch W, so the misalignment turns with the row unless W is a multiple of 4).  The image starts on a 256-byte boundary of the workspace, so the
+        // first word of row 0 does not begin before it; the last word of row H - 1 ends at most 3 bytes past the image, inside the padding of its 256-byte carve.
+        const int m0 = (int)(((uintptr_t)S5 + (size_t)y_lo * W + x_lo) & 3);
+        lds_sync();                                 // the previous chunk's reads are done (the workgroup is one wavefront)
+        // (eight loads in flight per lane and no branch between them: a word past the box's end re-reads the first of its row, a word past the tile's the last)
+        const int nw = bh * LBD_PITCH_DW;
+        for (int i0 = lane; i0 < nw; i0 += 64 * 8) {
+            uint32_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int i = min(i0 + 64 * u, nw - 1), r = i / LBD_PITCH_DW, q = i - r * LBD_PITCH_DW;
+                const int mis = (m0 + r * w3) & 3;
+                v[u] = *(const uint32_t*)(S5 + (size_t)(y_lo + r) * W + (x_lo - mis + (4 * q < mis + bw ? 4 * q : 0)));
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) tile[min(i0 + 64 * u, nw - 1)] = v[u];
         }
+        lds_sync();
+        if (has_row) {
+            const uint8_t* T = (const uint8_t*)tile;
+            auto row_at = [&](int y) { const int r = y - y_lo; return r * (LBD_PITCH_DW * 4) + ((m0 + r * w3) & 3) - x_lo; };      // + x: the byte (x, y) in the tile
+            for (int k = 0; k < n; k++) {
+                const short xCor = clampX(sCorX), yCor = clampY(sCorY);
+                // (reflect101 of c - 1 / c + 1 for a c in [0, n - 1], n >= 2: one fold at most, so no loop)
+                const int r0 = row_at(yCor == 0 ? 1 : yCor - 1), r1 = row_at(yCor), r2 = row_at(yCor == imageHeight ? H - 2 : yCor + 1);
+                const int xm = xCor == 0 ? 1 : xCor - 1, xp = xCor == imageWidth ? W - 2 : xCor + 1;
+                const int a0 = T[r0 + xm], a1 = T[r0 + xCor], a2 = T[r0 + xp], b0 = T[r1 + xm], b2 = T[r1 + xp], c0 = T[r2 + xm], c1 = T[r2 + xCor], c2 = T[r2 + xp];
+                const short dx = (short)((a2 - a0) + 2 * (b2 - b0) + (c2 - c0)), dy = (short)((c0 - a0) + 2 * (c1 - a1) + (c2 - a2));
+                const float gDL = dx * dL[0] + dy * dL[1];
+                const float gDO = dx * dO[0] + dy * dO[1];
+                if (gDL > 0) pgdLRowSum += gDL; else ngdLRowSum -= gDL;
+                if (gDO > 0) pgdORowSum += gDO; else ngdORowSum -= gDO;
+                sCorX += dL[0];
+                sCorY += dL[1];
+            }
+        }
+    }
+    if (has_row) {
         const float coef = (float)P.gaussCoefG[lane];
         pgdLRowSum = coef * pgdLRowSum; ngdLRowSum = coef * ngdLRowSum;
         pgdORowSum = coef * pgdORowSum; ngdORowSum = coef * ngdORowSum;

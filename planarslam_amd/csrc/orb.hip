@@ -13,7 +13,7 @@
 //   K4 orb_octree      one wave per (frame, level): the reference's node-list algorithm on
 //                      contiguous ranges of the sorted array, then per-node arg-max           (:539-763)
 //   K5 orb_blur        7x7 sigma-2 separable fixed-point Gaussian, LDS tiles                   (:1085-1086)
-//   K6 orb_describe    16 lanes per keypoint: IC_Angle + steered 256-bit BRIEF                 (:77-147)
+//   K6 orb_describe    16 lanes per keypoint: IC_Angle + steered 256-bit BRIEF on LDS tiles    (:77-147)
 //
 // Why a sort: DivideNode splits at midpoints that depend only on the node's bounds, so the
 // quadtree cell of a key at every depth is a pure function of its (x,y): its "path code"
@@ -753,12 +753,37 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     return a;
 }
 
+// The two patches of a key point go through LDS.  IC_Angle reads the 31-row disc of the level image, the steered pattern the box of the blurred image that a tap
+// can reach under any rotation: a tap (px, py) lands on (rn(px b + py a), rn(px a - py b)), both at most |(px, py)| in magnitude before the rounding, so the radius is
+// the largest |(px, py)| of brief_pattern.inc rounded up.
+constexpr signed char k_pattern_host[1024] = {
+#include "brief_pattern.inc"
+};
+constexpr int brief_reach() {
+    int m = 0;
+    for (int i = 0; i < 1024; i += 2) { const int n2 = k_pattern_host[i] * k_pattern_host[i] + k_pattern_host[i + 1] * k_pattern_host[i + 1]; m = n2 > m ? n2 : m; }
+    int r = 0;
+    while (r * r < m) r++;
+    return r;
+}
+constexpr int BRIEF_R = brief_reach();
+// key points lie in [EDGE_THRESHOLD, w - EDGE_THRESHOLD) x [EDGE_THRESHOLD, h - EDGE_THRESHOLD) of their level (the FAST windows begin at minB + 3 = EDGE_THRESHOLD and
+// end at maxB - 3 = size - EDGE_THRESHOLD, :771-786), so both patches lie inside the level image as long as their radii do not exceed EDGE_THRESHOLD
+static_assert(BRIEF_R <= EDGE_THRESHOLD && HALF_PATCH <= EDGE_THRESHOLD, "a key point's patches must lie inside its level");
+constexpr int DISC_ROWS = 2 * HALF_PATCH + 1, DISC_DW = (3 + DISC_ROWS + 3) / 4;      // a row: up to 3 bytes of misalignment + the bytes, in whole words
+constexpr int BOX_ROWS = 2 * BRIEF_R + 1, BOX_DW = (3 + BOX_ROWS + 3) / 4;
+constexpr int KP_TILE_RAW = DISC_ROWS * DISC_DW + BOX_ROWS * BOX_DW;
+constexpr int KP_TILE_DW = KP_TILE_RAW + (8 + 32 - KP_TILE_RAW % 32) % 32;            // = 8 (mod 32): the four key points of a wavefront start 8 banks apart
+static_assert(KP_TILE_DW % 32 == 8 && KP_TILE_DW >= KP_TILE_RAW && 16 * KP_TILE_DW * 4 <= 64 * 1024, "key point tiles: bank offset and static LDS limit");
+
 __global__ __launch_bounds__(256) void orb_describe(const PlanDev* __restrict__ plan, const uint8_t* __restrict__ pyr,
                                                     const uint8_t* __restrict__ blur, const uint32_t* __restrict__ kept,
                                                     const int* __restrict__ kept_count, planar_keypoint* __restrict__ kps,
                                                     uint8_t* __restrict__ desc, int32_t* __restrict__ n_out, int per_frame, int B) {
     // a frame's 1000 patches (38 rows of the level image and of its blurred clone each) overlap 4-5 times over: its workgroups run on one XCD (common.h), so that
     // the frame's two pyramids go through ONE L2 once (rounds 1-4: spread over all eight, 5.0 GB of fetches per 1024 frames for 1.6 GB of pyramids)
+    // 16 x 2.8 KB of LDS: three workgroups (twelve wavefronts) per CU, each with its ~45 row loads per lane in flight at once
+    __shared__ uint32_t s_tile[16 * KP_TILE_DW];
     int frame, bx;
     xcd_frame_block(per_frame, B, frame, bx);
     const int sub = threadIdx.x & 15;
@@ -778,16 +803,45 @@ __global__ __launch_bounds__(256) void orb_describe(const PlanDev* __restrict__ 
     const int score = (int)(key >> 24);
     const int64_t lvl_off = (int64_t)frame * plan->pyr_stride + L.off;
 
+    // the key point's 16 lanes fetch its two patches as aligned 32-bit words (rows of a level start on 16-byte boundaries, L.off and pyr_stride are multiples of
+    // 256), flattened over (row, word): a tile row begins `mis` bytes left of the patch.  Only words that hold a byte of the patch are read (a lane whose word would hold none re-reads the row's first: no branch between the loads), and those lie inside
+    // columns [0, pitch) of rows [0, h) of the level: the patch does (static_assert above) and pitch is a multiple of 4 - no read leaves the level, the last level
+    // of the last frame included.  A tile belongs to its 16 lanes alone, and a wavefront's LDS operations complete in order: a wavefront-scope fence is all the
+    // ordering the reads below need, and the inactive groups of the last workgroup (returned above) take no part in it.
+    uint32_t* const t_disc = s_tile + (threadIdx.x >> 4) * KP_TILE_DW;
+    uint32_t* const t_box = t_disc + DISC_ROWS * DISC_DW;
+    const int dmis = (x - HALF_PATCH) & 3, bmis = (x - BRIEF_R) & 3;
+    {
+        const uint8_t* g = pyr + lvl_off + (int64_t)(y - HALF_PATCH) * L.pitch + (x - HALF_PATCH - dmis);
+        const int nd = (dmis + DISC_ROWS + 3) >> 2;
+#pragma unroll
+        for (int j = 0; j < (DISC_ROWS * DISC_DW + 15) / 16; j++) {
+            const int i = min(sub + 16 * j, DISC_ROWS * DISC_DW - 1), r = i / DISC_DW, q = i - r * DISC_DW;
+            t_disc[i] = *(const uint32_t*)(g + (int64_t)r * L.pitch + 4 * (q < nd ? q : 0));
+        }
+    }
+    {
+        const uint8_t* g = blur + lvl_off + (int64_t)(y - BRIEF_R) * L.pitch + (x - BRIEF_R - bmis);
+        const int nd = (bmis + BOX_ROWS + 3) >> 2;
+#pragma unroll
+        for (int j = 0; j < (BOX_ROWS * BOX_DW + 15) / 16; j++) {
+            const int i = min(sub + 16 * j, BOX_ROWS * BOX_DW - 1), r = i / BOX_DW, q = i - r * BOX_DW;
+            t_box[i] = *(const uint32_t*)(g + (int64_t)r * L.pitch + 4 * (q < nd ? q : 0));
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+
     // IC_Angle (:77-104): lane `sub` handles rows +-sub (sub = 0: centre row)
-    const uint8_t* c = pyr + lvl_off + (int64_t)y * L.pitch + x;
+    constexpr int DISC_STEP = DISC_DW * 4;
+    const uint8_t* c = (const uint8_t*)t_disc + HALF_PATCH * DISC_STEP + dmis + HALF_PATCH;
     int m10 = 0, m01 = 0;
     if (sub == 0) {
         for (int u = -HALF_PATCH; u <= HALF_PATCH; ++u) m10 += u * c[u];
     } else {
         const int d = plan->umax[sub];
         int vsum = 0;
-        const uint8_t* cp = c + (int64_t)sub * L.pitch;
-        const uint8_t* cm = c - (int64_t)sub * L.pitch;
+        const uint8_t* cp = c + sub * DISC_STEP;
+        const uint8_t* cm = c - sub * DISC_STEP;
         for (int u = -d; u <= d; ++u) {
             const int vp = cp[u], vm = cm[u];
             vsum += vp - vm;
@@ -803,12 +857,12 @@ __global__ __launch_bounds__(256) void orb_describe(const PlanDev* __restrict__ 
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
     const float ang = __fmul_rn(angle, factorPI);
     const float a = (float)cos((double)ang), b = (float)sin((double)ang);
-    const uint8_t* bc = blur + lvl_off + (int64_t)y * L.pitch + x;
-    const int step = L.pitch;
+    constexpr int step = BOX_DW * 4;
+    const uint8_t* bc = (const uint8_t*)t_box + BRIEF_R * step + bmis + BRIEF_R;
     uint32_t bits = 0;
     const signed char* pat = c_pattern + sub * 64;
 #pragma unroll
-    for (int i = 0; i < 16; i++) {                      // (fully unrolled: the 32 taps of a lane are independent byte loads, all of them in flight)
+    for (int i = 0; i < 16; i++) {                      // (fully unrolled: the 32 taps of a lane are independent LDS byte reads, all of them in flight)
         const float x0 = (float)pat[4 * i], y0 = (float)pat[4 * i + 1], x1 = (float)pat[4 * i + 2], y1 = (float)pat[4 * i + 3];
         const int r0 = __float2int_rn(__fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a)));
         const int q0 = __float2int_rn(__fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b)));
