@@ -153,7 +153,7 @@ static void computeLine3d_svd(const std::vector<RandomPoint3d>& pts, const std::
     drct = {Vt[0], Vt[1], Vt[2]};
 }
 
-struct Line3dOut { P3 A, B, director; int n_pts = 0; };
+struct Line3dOut { P3 A, B, director; int n_pts = 0, n_ransac = 0; };     // n_ransac: the RANSAC set's size before the re-fit loop (diagnostic)
 
 static Line3dOut extract3dline_mahdist(const std::vector<RandomPoint3d>& pts, GlibcRand& rng) {
     const int maxIterNo = std::min(10, int(pts.size() * (pts.size() - 1) * 0.5));
@@ -181,6 +181,7 @@ static Line3dOut extract3dline_mahdist(const std::vector<RandomPoint3d>& pts, Gl
         if (maxInlierSet.size() > pts.size() * 0.6) break;
     }
     Line3dOut rl;
+    rl.n_ransac = (int)maxInlierSet.size();
     if (maxInlierSet.size() >= 2) {
         P3 m = (bestA.pos + bestB.pos) * 0.5, d = bestB.pos - bestA.pos;
         while (true) {
@@ -217,15 +218,17 @@ int orc_glibc_rand(uint32_t seed, int count, int32_t* out) {
 }
 
 // Frame::isLineGood for one frame.  depth_line [n] (mvDepthLine), lines3d [n][6] (mvLines3D), good [n] (the line went into mVF3DLines),
-// direction [n][3] (FrameLine::direction; NaN-free only where good), n_inliers [n] (tmpLine.pts.size()), n_samples [n] (pts3d.size()).  Returns the number of good lines.
-int orc_is_line_good(const planar_keyline* kl, int n_lines, const uint16_t* depth, int W, int H, int pitch_px, float factor, float fx, float fy, float cx, float cy,
-                     uint32_t seed, float* depth_line, double* lines3d, uint8_t* good, double* direction, int32_t* n_inliers, int32_t* n_samples) {
+// direction [n][3] (FrameLine::direction; NaN-free only where good), n_inliers [n] (tmpLine.pts.size()), n_samples [n] (pts3d.size()), n_ransac [n] (optional
+// diagnostic: the inlier set RANSAC handed to the re-fit loop; n_inliers > n_ransac means the re-fit grew it).  Returns the number of good lines.
+int orc_is_line_good_ex(const planar_keyline* kl, int n_lines, const uint16_t* depth, int W, int H, int pitch_px, float factor, float fx, float fy, float cx, float cy,
+                        uint32_t seed, float* depth_line, double* lines3d, uint8_t* good, double* direction, int32_t* n_inliers, int32_t* n_samples, int32_t* n_ransac) {
     using namespace orc;
     const float invfx = 1.0f / fx, invfy = 1.0f / fy;
     auto imDepth = [&](int row, int col) -> float { return (float)depth[(size_t)row * pitch_px + col] * factor; };
     int ngood = 0;
     for (int i = 0; i < n_lines; i++) {
         depth_line[i] = -1.0f; good[i] = 0; n_inliers[i] = 0; n_samples[i] = 0;
+        if (n_ransac) n_ransac[i] = 0;
         for (int k = 0; k < 6; k++) lines3d[(size_t)i * 6 + k] = 0;
         for (int k = 0; k < 3; k++) direction[(size_t)i * 3 + k] = 0;
         const float sx = kl[i].start_x, sy = kl[i].start_y, ex = kl[i].end_x, ey = kl[i].end_y;
@@ -258,6 +261,7 @@ int orc_is_line_good(const planar_keyline* kl, int n_lines, const uint16_t* dept
         GlibcRand rng(seed + (uint32_t)i);
         const Line3dOut tl = extract3dline_mahdist(rnd, rng);
         n_inliers[i] = tl.n_pts;
+        if (n_ransac) n_ransac[i] = tl.n_ransac;
         if (tl.n_pts / len > 0.4 && norm(tl.A - tl.B) > 0.02) {
             depth_line[i] = std::min(imDepth((int)ey, (int)ex), imDepth((int)sy, (int)sx));
             good[i] = 1; ngood++;
@@ -267,6 +271,11 @@ int orc_is_line_good(const planar_keyline* kl, int n_lines, const uint16_t* dept
         }
     }
     return ngood;
+}
+
+int orc_is_line_good(const planar_keyline* kl, int n_lines, const uint16_t* depth, int W, int H, int pitch_px, float factor, float fx, float fy, float cx, float cy,
+                     uint32_t seed, float* depth_line, double* lines3d, uint8_t* good, double* direction, int32_t* n_inliers, int32_t* n_samples) {
+    return orc_is_line_good_ex(kl, n_lines, depth, W, H, pitch_px, factor, fx, fy, cx, cy, seed, depth_line, lines3d, good, direction, n_inliers, n_samples, nullptr);
 }
 
 }  // extern "C"

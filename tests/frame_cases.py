@@ -76,3 +76,56 @@ def manhattan_pose_case(n=64, seed=31):
     T = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (n, 1)); T[:, [3, 7, 11]] = rng.normal(size=(n, 3)).astype(np.float32)
     T[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]] = rot(rng.normal(size=(n, 4)))
     return rot(q0), rot(q1), T
+
+
+# ---- Tracking::TrackManhattanFrame at the edges of the kernel's staged chain sums (256-element blocks, an eight-wide body and a scalar tail) ----
+MANHATTAN_EDGE_SN_STRIDE, MANHATTAN_EDGE_LN_STRIDE = 600, 16
+# (n_normals, n_lines): nothing but lines, fewer than eight elements, exactly eight, totals of 255 / 256 / 257 / 513, lines behind a tail
+MANHATTAN_EDGE_COUNTS = [(0, 9), (1, 0), (7, 0), (8, 0), (248, 7), (249, 7), (250, 7), (256, 0), (513, 0), (300, 3)]
+
+
+def _one_frame(sc, n, m):
+    import numpy as np
+    return dict(R_last=sc["R_last"][0].copy(), normals=np.ascontiguousarray(sc["normals"][0, :n]), lines=np.ascontiguousarray(sc["lines"][0, :m]))
+
+
+def _manhattan_edge_builders():
+    import numpy as np
+    out = {}
+    for i, (n, m) in enumerate(MANHATTAN_EDGE_COUNTS):
+        out[f"n{n}_l{m}"] = lambda i=i, n=n, m=m: _one_frame(synth.manhattan_scene(B=1, seed=140 + i, n_normals=MANHATTAN_EDGE_SN_STRIDE, n_lines=MANHATTAN_EDGE_LN_STRIDE,
+                                                                                    clutter=0.1), n, m)
+
+    def poisoned():
+        """every 7th normal NaN, every 50th (from index 3) the zero vector, line 5 zero: a zero vector lies in every cone and adds to no sum"""
+        fr = _one_frame(synth.manhattan_scene(B=1, seed=77, n_normals=600, n_lines=12, clutter=0.1), 600, 12)
+        fr["normals"][::7] = np.nan
+        fr["normals"][3::50] = 0
+        fr["lines"][5] = 0
+        return fr
+    out["poisoned"] = poisoned
+    out["lines_only_two_axes"] = lambda: _one_frame(synth.manhattan_scene(B=1, seed=78, n_normals=1, n_lines=30, drop_axis=1), 0, 30)
+    return out
+
+
+MANHATTAN_EDGE_CASES = _manhattan_edge_builders()      # name -> () -> dict(R_last [3,3] f32, normals [n,3] f32, lines [m,3] f64): one frame each
+
+
+def manhattan_edge_batch(names=None, fill=3.25):
+    """the edge frames stacked into one ragged batch at strides strictly above every count (the poisoned frame has its own stride and stays out); rows past the
+    counts hold non-zero garbage that must not be read.  -> (names, manhattan_scene-like dict)"""
+    import numpy as np
+    names = list(names or [k for k in MANHATTAN_EDGE_CASES if k not in ("poisoned", "lines_only_two_axes")])
+    S, T = MANHATTAN_EDGE_SN_STRIDE, MANHATTAN_EDGE_LN_STRIDE
+    B = len(names)
+    sc = dict(R_last=np.zeros((B, 3, 3), np.float32), normals=np.full((B, S, 3), fill, np.float32), lines=np.full((B, T, 3), -fill, np.float64),
+              n_normals=np.zeros(B, np.int32), n_lines=np.zeros(B, np.int32))
+    for b, k in enumerate(names):
+        fr = MANHATTAN_EDGE_CASES[k]()
+        n, m = len(fr["normals"]), len(fr["lines"])
+        assert n < S and m < T
+        sc["R_last"][b] = fr["R_last"]; sc["normals"][b, :n] = fr["normals"]; sc["lines"][b, :m] = fr["lines"]; sc["n_normals"][b] = n; sc["n_lines"][b] = m
+    # garbage that would be seen: unit vectors along the frame's first axis would join a cone
+    sc["normals"][:, :, :] = np.where(np.arange(S)[None, :, None] < sc["n_normals"][:, None, None], sc["normals"], sc["R_last"][:, None, :, 0])
+    sc["lines"][:, :, :] = np.where(np.arange(T)[None, :, None] < sc["n_lines"][:, None, None], sc["lines"], sc["R_last"][:, None, :, 0].astype(np.float64))
+    return names, sc

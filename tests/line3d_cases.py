@@ -1,4 +1,7 @@
-"""Seeded cases shared by tools/gen_golden_line3d.py (the REAL reference's Frame::isLineGood -> tests/golden/line3d_ref.npz), the oracle test and the GPU test."""
+"""Seeded cases shared by tools/gen_golden_line3d.py (the REAL reference's Frame::isLineGood -> tests/golden/line3d_ref.npz and line3d_edges_ref.npz), the oracle
+test and the GPU test."""
+import functools
+
 import numpy as np
 
 import oracle_lib as O
@@ -24,3 +27,117 @@ def build(name):
     if extra == "half":
         d = d.copy(); d[:, 300:] = 0
     return kl, d, seed
+
+
+# ---- hand-built key lines (Frame::isLineGood reads start / end only): the sampling, length and gate edges no detected line reaches on purpose ----
+def keylines(segments):
+    """[(x0, y0, x1, y1)] -> KEYLINE_DTYPE array with start_* / end_* set"""
+    from planarslam_amd._lib import KEYLINE_DTYPE
+    kl = np.zeros(len(segments), KEYLINE_DTYPE)
+    s = np.asarray(segments, np.float32).reshape(-1, 4)
+    kl["start_x"], kl["start_y"], kl["end_x"], kl["end_y"] = s.T
+    return kl
+
+
+def tilted_plane(seed=7, w=640, h=480):
+    """z = 1.5 + 0.001 x + 0.0005 y metres, sigma = 8 depth units of noise"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    z = (1.5 + 0.001 * xx + 0.0005 * yy) * 5000 + np.random.default_rng(seed).normal(0, 8, (h, w))
+    return np.rint(z).astype(np.uint16)
+
+
+# (segment, samples, good): what the reference returns on tilted_plane() with rand seed 7 (tests/golden/line3d_edges_ref.npz holds every output)
+PLANE_LINES = [
+    ((100, 200, 150, 200), 51, 1),            # every sample has integer coordinates: the `- 1` sampling branch
+    ((100, 100, 130, 140), 51, 1),            # diagonal, 3-4-5: steps of (0.6, 0.8), both branches alternate along one line
+    ((0, 0, 50, 0), 51, 1),                   # max(int(x - 1), 0): samples 0 and 1 are the same pixel, row clamped at 0
+    ((0, 10, 0, 60), 51, 1),                  # column clamped at 0
+    ((200.5, 300.5, 210.4, 300.5), 10, 1),    # length 9.9: 10 samples, the fewest that pass
+    ((200.5, 310.5, 210.5, 310.5), 11, 1),    # length 10.0
+    ((100.5, 50.5, 227.5, 50.5), 51, 1),      # length 127: 51 / 127 > 0.4
+    ((100.5, 60.5, 228.0, 60.5), 51, 0),      # length 127.5: 51 / 127.5 = 0.4, not above it
+    ((100.5, 70.5, 228.5, 70.5), 51, 0),      # length 128
+    ((100.5, 80.5, 400.5, 80.5), 51, 0),      # length 300
+    ((300.5, 300.5, 309.4, 300.5), 9, 0),     # length 8.9: 9 samples, skipped, every output at its default
+    ((300.5, 310.5, 309.5, 310.5), 10, 1),    # length 9.0: (int)len = 9 -> 10 samples
+    ((589.5, 479.5, 639.5, 479.5), 51, 1),    # last row, last column
+    ((600.5, 100.5, 639.9, 100.5), 40, 1),    # 40 samples, ends in the last column
+]
+SUBPIXEL_LINE = (50.25, 50.25, 50.75, 50.5)   # (int)len < 1: skipped by the kernel and the oracle; the reference binary dies on it (0 / 0 -> int(NaN) index), so never in a fixture
+
+# frame seeds for which the first RANSAC draw of line 0 = (0,0)-(50,0) is the coincident pair {sample 0, sample 1}: the norm(B - A) < EPS skip
+COINCIDENT_SEEDS = (3066, 3985, 4503)
+
+
+def first_draw(seed, n):
+    """the first random_unique(indexes, 2) of extract3dline_mahdist after srand(seed): r0 = rand % n, r1 = 1 + rand % (n - 1), two swaps -> (indexes[0], indexes[1])"""
+    r = O.glibc_rand(seed, 2)
+    idx = list(range(n))
+    r0 = int(r[0]) % n
+    idx[0], idx[r0] = idx[r0], idx[0]
+    r1 = 1 + int(r[1]) % (n - 1)
+    idx[1], idx[r1] = idx[r1], idx[1]
+    return idx[0], idx[1]
+
+
+def random_segments(rng, n, w, h, lo=12, hi=120):
+    """n segments: starts uniform in [5, w - 140] x [5, h - 10] (at 640x480: [5,500] x [5,470]), lengths lo..hi px, random angles, ends clipped to [1, w - 2] x [1, h - 2]"""
+    x0 = rng.uniform(5, max(w - 140, 6), n); y0 = rng.uniform(5, h - 10, n)
+    ln = rng.uniform(lo, hi, n); a = rng.uniform(0, 2 * np.pi, n)
+    x1 = np.clip(x0 + ln * np.cos(a), 1, w - 2); y1 = np.clip(y0 + ln * np.sin(a), 1, h - 2)
+    return np.stack([x0, y0, x1, y1], 1)
+
+
+MULTI_CHUNK_STRIDE = 160
+OTHER_CAM = (300.0, 310.0, 140.3, 150.7)
+OTHER_FACTOR = 1.0 / 1000.0
+
+# name -> what goes into tests/golden/line3d_edges_ref.npz
+EDGE_CASES = ("plane", "near_wall", "multi_chunk") + tuple(f"coincident_{s}" for s in COINCIDENT_SEEDS)
+
+
+@functools.lru_cache(maxsize=None)
+def build_edge(name):
+    """-> (key lines, depth [480,640] u16, rand seed)"""
+    if name == "plane":
+        return keylines([s for s, _, _ in PLANE_LINES]), tilted_plane(), 7
+    if name.startswith("coincident_"):
+        return keylines([PLANE_LINES[2][0], PLANE_LINES[0][0]]), tilted_plane(), int(name.split("_")[1])
+    if name == "near_wall":       # 0.12 m away: a 12 px line (13 inliers, 13 / 12 > 0.4) spans less than 0.02 m in space, a 110 px one more
+        return keylines([(300.5, 200.5, 312.5, 200.5), (300.5, 210.5, 410.5, 210.5)]), np.full((480, 640), 600, np.uint16), 7
+    if name == "multi_chunk":     # 150 lines: three 64-line chunks of pack_kernel, good and rejected lines in each
+        segs = random_segments(np.random.default_rng(4), 150, 640, 480)
+        return keylines(segs), synth.depth_image(111, noise=True, holes=True), 5
+    raise KeyError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_oracle(name):
+    kl, d, seed = build_edge(name)
+    return O.is_line_good(kl, d, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def other_camera_case(B=2, n=48):
+    """325x247 frames, another camera, depth in millimetres -> (key lines [B,n], depth [B,247,325], seeds [B])"""
+    w, h = 325, 247
+    rng = np.random.default_rng(21)
+    kl = np.stack([keylines(random_segments(rng, n, w, h, lo=10, hi=90)) for _ in range(B)])
+    d = np.stack([synth.depth_image(131 + b, w, h) // 5 for b in range(B)])
+    return kl, d, np.array([17, 170000], np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def hd_chain_case():
+    """one 1280x720 frame for the normals -> lines -> Manhattan chain: depth, 110 hand-built key lines (60 random, 25 near-horizontal and 25 near-vertical ones,
+    which line up with the room's axes), the camera of the 1280x720 pipeline test, the rand seed -> (depth, key lines, camera, seed)"""
+    P = synth.TUM3
+    cam = (2 * P["fx"], 2 * P["fy"], 2 * P["cx"], 2 * P["cy"])
+    w, h = 1280, 720
+    rng = np.random.default_rng(3)
+    segs = random_segments(rng, 60, w, h, lo=20, hi=120)
+    hx, hy, hl = rng.uniform(20, 1100, 25), rng.uniform(20, 700, 25), rng.uniform(30, 120, 25)
+    vx, vy, vl = rng.uniform(20, 1260, 25), rng.uniform(20, 580, 25), rng.uniform(30, 120, 25)
+    segs = np.concatenate([segs, np.stack([hx, hy, hx + hl, hy + rng.uniform(-3, 3, 25)], 1), np.stack([vx, vy, vx + rng.uniform(-3, 3, 25), vy + vl], 1)])
+    assert segs[:, [0, 2]].min() >= 1 and segs[:, [0, 2]].max() <= w - 2 and segs[:, [1, 3]].min() >= 1 and segs[:, [1, 3]].max() <= h - 2
+    return synth.depth_image(7, w, h), keylines(segs), cam, 11

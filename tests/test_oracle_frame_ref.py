@@ -102,3 +102,43 @@ def test_manhattan_oracle_vs_live_reference_fresh_seeds(seed):
         o = ol.track_manhattan_frame(sc["R_last"][b], sc["normals"][b, :n], sc["lines"][b, :m])
         r = ol.run_ref_manhattan(sc["R_last"][b], sc["normals"][b, :n], sc["lines"][b, :m])
         assert np.array_equal(o["R"], r["R"]) and np.array_equal(o["member"], r["member"])
+
+
+# ---- the one-frame edge cases (tests/golden/manhattan_edges_ref.npz, tools/gen_golden_manhattan_edges.py) ----
+@pytest.fixture(scope="module")
+def edges_golden(golden_dir):
+    return np.load(os.path.join(golden_dir, "manhattan_edges_ref.npz"))
+
+
+@pytest.mark.parametrize("name", list(cases.MANHATTAN_EDGE_CASES))
+def test_manhattan_oracle_equals_reference_edge_fixture(edges_golden, name):
+    fr = cases.MANHATTAN_EDGE_CASES[name]()
+    o = ol.track_manhattan_frame(fr["R_last"], fr["normals"], fr["lines"])
+    assert np.array_equal(o["R"], edges_golden[f"{name}/R"]), f"rotation differs by {np.abs(o['R'] - edges_golden[f'{name}/R']).max()}"
+    assert np.array_equal(o["member"], edges_golden[f"{name}/member"])
+    assert o["info"][0] >= 1 and not np.array_equal(o["R"], fr["R_last"])          # something was found and the matrix moved: no case is a no-op
+
+
+def test_manhattan_edge_cases_reach_what_they_are_for():
+    got = {k: ol.track_manhattan_frame(**f()) for k, f in cases.MANHATTAN_EDGE_CASES.items()}
+    tot = {k: len(f()["normals"]) + len(f()["lines"]) for k, f in cases.MANHATTAN_EDGE_CASES.items()}
+    assert {255, 256, 257, 513} <= set(tot.values()) and {1, 7, 8, 9} <= set(tot.values())          # block edges of the staged chain sum, and below / at its eight-wide body
+    assert any(t % 256 % 8 and t > 256 for t in tot.values()) and any(t % 256 % 8 == 0 for t in tot.values())
+    assert got["n7_l0"]["info"][0] == 2                                                             # two axes from seven normals: the cross-product branch
+    assert list(got["n0_l9"]["info"][2:5]) == [0, 0, 0] and got["n0_l9"]["info"][0] == 3            # lines and no normals
+    # zero vectors: members of every cone (mask 7), NaN normals of none; neither adds to a sum
+    fr = cases.MANHATTAN_EDGE_CASES["poisoned"]()
+    zero = ~fr["normals"].any(axis=1); nan = np.isnan(fr["normals"][:, 0])
+    m = got["poisoned"]["member"]
+    assert zero.sum() == 12 and nan.sum() > 70 and (m[:600][zero] == 7).all() and (m[:600][nan] == 0).all() and m[600 + 5] == 7
+    info = got["poisoned"]["info"]
+    assert info[0] == 3 and all(info[5 + a] == ((m >> a) & 1).sum() - 13 for a in range(3))         # the 12 + 1 zero vectors are members that count for nothing
+    assert list(got["lines_only_two_axes"]["info"]) == [2, 5, 0, 0, 0, 18, 0, 12]
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/ref_frame not built")
+def test_manhattan_edge_fixture_is_what_the_reference_produces_now(edges_golden):
+    for name in ("n8_l0", "n249_l7", "poisoned"):
+        fr = cases.MANHATTAN_EDGE_CASES[name]()
+        r = ol.run_ref_manhattan(fr["R_last"], fr["normals"], fr["lines"])
+        assert np.array_equal(r["R"], edges_golden[f"{name}/R"]) and np.array_equal(r["member"], edges_golden[f"{name}/member"])
