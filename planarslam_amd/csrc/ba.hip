@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "geom_dev.h"
+#include "wg_team.h"
 
 namespace planar {
 namespace ba {
@@ -152,13 +153,6 @@ __device__ __forceinline__ void huber(double c2, double delta, double& r0, doubl
     const double dsqr = delta * delta;
     if (c2 <= dsqr) { r0 = c2; r1 = 1; } else { const double sq = sqrt(c2); r0 = 2 * sq * delta - dsqr; r1 = delta / sq; }
 }
-__device__ __forceinline__ double block_sum(double v, double* lds4) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
 
 // landmark of edge e (round 6: was a binary search in the CSR - eleven dependent loads at the head of every edge thread)
 __device__ __forceinline__ int edge_landmark(const Dev& D, int e) { return D.e_lm[e]; }
@@ -182,9 +176,10 @@ __global__ __launch_bounds__(NT) void ba_errors(Dev D, int robust, double* chi_o
         const double c2 = edge_chi2(edge_dim(type), err, D.e_info + (size_t)e * 4);
         if (robust) { double r0, r1; huber(c2, D.e_info[(size_t)e * 4 + 3], r0, r1); chi = r0; } else chi = c2;
     }
-    const double tot = block_sum(chi, s4);
+    double tot[1] = {chi};
+    WorkgroupTeam<NT>{nullptr, s4}.reduce(tot);
     if (threadIdx.x == 0) {
-        if (tot != 0) atomicAdd(chi_out, tot);
+        if (tot[0] != 0) atomicAdd(chi_out, tot[0]);
         if (decide_cnt) {
             __threadfence();
             if (atomicAdd(decide_cnt, 1u) == gridDim.x - 1) {
@@ -670,8 +665,9 @@ __global__ __launch_bounds__(NT) void ba_update(Dev D, int stop) {
             if (v.type == 0) { o[0] = v.X.x; o[1] = v.X.y; o[2] = v.X.z; } else for (int a = 0; a < 4; a++) o[a] = v.P.c[a];
         }
     }
-    const double tot = block_sum(sc, s4);
-    if (threadIdx.x == 0 && tot != 0) atomicAdd(lmscale_out, tot);
+    double tot[1] = {sc};
+    WorkgroupTeam<NT>{nullptr, s4}.reduce(tot);
+    if (threadIdx.x == 0 && tot[0] != 0) atomicAdd(lmscale_out, tot[0]);
 }
 
 // computeLambdaInit (optimization_algorithm_levenberg.cpp:132-149) from the summed Hpp and the MAX-reduced landmark diagonal; the stop word

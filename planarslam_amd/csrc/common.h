@@ -57,6 +57,30 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+// A table of int32 over N that an entry point computes on the host from a few parameters and its kernel reads (the RANSAC solvers' mRansacMaxIts: hornransac.hip,
+// pnpransac.hip): kept on the device for the parameters it was built for and rebuilt when a call brings others.
+struct ParamKey {
+    double prob; int min_inliers, max_its; float epsilon;
+    bool operator==(const ParamKey& o) const { return prob == o.prob && min_inliers == o.min_inliers && max_its == o.max_its && epsilon == o.epsilon; }
+};
+struct ParamTable {
+    DevBuf dev;
+    std::vector<int32_t> host;
+    ParamKey key{-1, 0, 0, 0};   // prob = -1: the device table is not (yet, or no longer) that of a key
+    // fill(int32_t* table) writes the n_entries of `k`; n_entries is the same in every call.  The copy is enqueued on `stream`, the stream of the kernels that read it.
+    template <class Fill> int ensure(hipStream_t stream, const ParamKey& k, size_t n_entries, Fill fill) {
+        if (dev.p && key == k) return PLANAR_OK;
+        if (dev.p) PLANAR_HIP_CHECK(hipStreamSynchronize(stream));   // a previous kernel may still be reading the table, a previous copy the host block
+        else if (int rc = dev.alloc(n_entries * sizeof(int32_t))) return rc;
+        host.resize(n_entries);
+        fill(host.data());
+        key.prob = -1;
+        PLANAR_HIP_CHECK(hipMemcpyAsync(dev.p, host.data(), n_entries * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        key = k;
+        return PLANAR_OK;
+    }
+};
+
 // Host<->device staging for the synchronous host-pointer entry points: one device block, inputs copied in on the stream, outputs copied back after the launch.
 // in() / out() / inout() take a host array and its length in ELEMENTS and return a handle that converts to the array's device address once upload() has run;
 // a null host array (an optional argument) is not staged and converts to a null device pointer.  Every array starts on a 256-byte boundary of the block.
@@ -198,17 +222,10 @@ struct planar_ctx {
     hipStream_t stream = nullptr;   // the stream work is enqueued on (own_stream unless overridden)
     planar::DevBuf scratch;         // grow-only device scratch for entry points that need temporaries
     // planar_horn_ransac: mRansacMaxIts over N in [0, PLANAR_MAX_FRAME_KEYS], host libm arithmetic, kept per (prob, min_inliers, max_its) (hornransac.hip)
-    planar::DevBuf horn_table;
-    std::vector<int32_t> horn_table_host;
-    double horn_prob = -1;
-    int horn_min_inliers = 0, horn_max_its = 0;
+    planar::ParamTable horn_table;
     // planar_pnp_ransac: mRansacMaxIts, then the adjusted mRansacMinInliers, over N in [0, PLANAR_MAX_FRAME_KEYS], kept per (prob, min_inliers, max_its, epsilon)
     // (pnpransac.hip)
-    planar::DevBuf pnp_table;
-    std::vector<int32_t> pnp_table_host;
-    double pnp_prob = -1;
-    int pnp_min_inliers = 0, pnp_max_its = 0;
-    float pnp_epsilon = 0;
+    planar::ParamTable pnp_table;
     // Optional side stream for the one-wavefront-per-frame kernels of the extractors (PEAC clustering, LSD region growing): planar_ctx_set_seq_stream.  Such a kernel
     // is latency-bound and occupies a CU for tens of milliseconds with four wavefronts; on a CU-masked stream (planar_cu_stream_create) it stays on a subset of the
     // CUs while the wide kernels of `stream` keep the rest.  seq_begin() / seq_end() bracket the launch: fork by event from `stream`, join back into it.
@@ -249,3 +266,25 @@ struct planar_ctx {
         return PLANAR_OK;
     }
 };
+
+namespace planar {
+
+// Where a RANSAC kernel (hornransac.hip, pnpransac.hip) keeps the correspondences of one problem, `rows` rows of floats: in LDS ([rows][LDS_CORR]) while the problem
+// has at most LDS_CORR key points, in its [rows][stride] slice of the context's scratch block beyond that.
+constexpr int LDS_CORR = 512;
+// host: *scratch = the block for B problems where a stride beyond the LDS tier may need it, else left as it is (null)
+static inline int corr_scratch(planar_ctx* ctx, int B, int rows, int stride, float** scratch) {
+    if (stride <= LDS_CORR) return PLANAR_OK;
+    if (int rc = ctx->ensure_scratch((size_t)B * rows * stride * sizeof(float))) return rc;
+    *scratch = ctx->scratch.as<float>();
+    return PLANAR_OK;
+}
+#ifdef __HIPCC__
+// kernel, for problem b with n <= stride key points: n > LDS_CORR implies stride > LDS_CORR, so the block exists
+__device__ __forceinline__ void corr_tier(int b, int n, int stride, int rows, float* lds_corr, float* scratch, float*& corr, int& cap) {
+    if (n <= LDS_CORR) { corr = lds_corr; cap = LDS_CORR; }
+    else { corr = scratch + (size_t)b * rows * stride; cap = stride; }
+}
+#endif
+
+}  // namespace planar

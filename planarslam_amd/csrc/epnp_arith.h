@@ -13,8 +13,7 @@
 #include <stdint.h>
 
 #ifndef EPNP_CV_ONLY   // tools/pnp_ransac_golden/pnp_cv.hpp takes the OpenCV section alone
-#include "glibc_rand.h"
-#include "horn_arith.h"   // random_int, pick4, Key
+#include "ransac_proto.h"
 #endif
 
 #if defined(__HIPCC__)
@@ -29,12 +28,11 @@ namespace planar {
 namespace epnp {
 
 #ifndef EPNP_CV_ONLY
-using horn::Key;
-using horn::pick4;
-using horn::random_int;
+using ransac::Key;
+using ransac::MAX_LEVELS;
+using ransac::pick4;
 #endif
 
-constexpr int MAX_LEVELS = 16;      // PLANAR_MAX_LEVELS
 constexpr int MAX_ITS_CAP = 1024;   // PLANAR_PNP_MAX_ITS: the draws and counts of one call are kept on chip
 constexpr int MAX_ITS_DONE = 1 << 20;   // PLANAR_PNP_MAX_ITS_DONE: its_done on entry is clamped to it
 constexpr int CORR_ROWS = 8;        // per correspondence: xw (3), pt (2), maxError, i (int32), and one entry of the best set's index list (int32): rows of `cap`
@@ -593,22 +591,14 @@ EPNP_HD bool is_inlier(const double* R, const double* t, const float* corr, int 
     return error2_of(R, t, corr, cap, c, K) < corr[5 * cap + c];
 }
 
-// SetRansacParameters (:121-152) for N correspondences: the adjusted mRansacMinInliers and mRansacMaxIts.  Host libm arithmetic.  Where the double is not an int
-// (NaN or an overflow at N = 0 or a tiny epsilon) the conversion is undefined in C++; x86-64 yields INT_MIN there, which the max() turns into 1.
+// SetRansacParameters (:121-152) for N correspondences: the adjusted mRansacMinInliers and mRansacMaxIts.  Host libm arithmetic.
 static inline void ransac_table(double prob, int min_inliers, int max_its, int min_set, float epsilon, int N, int& minInl, int& maxIts) {
     int nMinInliers = (int)((float)N * epsilon);
     if (nMinInliers < min_inliers) nMinInliers = min_inliers;
     if (nMinInliers < min_set) nMinInliers = min_set;
     minInl = nMinInliers;
     if (epsilon < (float)nMinInliers / N) epsilon = (float)nMinInliers / N;
-    int nIterations;
-    if (nMinInliers == N) nIterations = 1;
-    else {
-        const double v = ceil(log(1 - prob) / log(1 - pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
-    }
-    const int m = nIterations < max_its ? nIterations : max_its;
-    maxIts = m > 1 ? m : 1;
+    maxIts = ransac::ransac_iterations(prob, epsilon, max_its, nMinInliers == N);
 }
 
 struct Problem {   // one (lost frame, candidate key frame); n already clamped to the stride
@@ -666,8 +656,9 @@ struct TeamAll {
     EPNP_M void sync() const { p.sync(); }
 };
 
-// ---- the protocol: one iterate(n_iterations) of one problem.  Par: tid(), nt(), sync(); rank(flag, total); group(), ngroups(), lane(), lanes(), count(flag) as in
-// horn_arith.h; slot(): the hypothesis slot this thread computes alone, or -1; slots(): how many there are.  Returns N.
+// ---- the protocol: one iterate(n_iterations) of one problem.  Par: ransac_proto.h, with slot() and slots().  Returns N.  The constructor's compaction and the
+// rebuild of the best set are written out, not ransac::compact_ascending: the rebuild stores a flag for every correspondence between the rank and the count, and
+// with these two written out pnp_ransac_kernel stays the code object it was.
 template <class Par>
 EPNP_HD int ransac_problem(Par& par, const Problem& P, const Params& prm, const State& st, const Out& out, const Work& w) {
     const int tid = par.tid(), nt = par.nt();
@@ -707,15 +698,7 @@ EPNP_HD int ransac_problem(Par& par, const Problem& P, const Params& prm, const 
         }
         // the best set of the earlier calls as an index list; Refine's outcome on it is not state: it is computed again when it is first asked for
         int nsel = 0;
-        if (best > 0)
-            for (int base = 0; base < N; base += nt) {
-                const int c = base + tid;
-                const bool f = c < N && st.best_set[idx_row[c]] != 0;
-                int total;
-                const int pos = par.rank(f, total);
-                if (f) sel_row[nsel + pos] = c;
-                nsel += total;
-            }
+        if (best > 0) nsel = ransac::compact_ascending(par, N, [&](int c) { return st.best_set[idx_row[c]] != 0; }, [&](int c, int pos) { sel_row[pos] = c; });
         par.sync();
         int refined = -1;   // -1: not computed for the present best set; else mnRefinedInliers (wr.Rb, wr.tb hold the refined pose)
         int ret = -1;
@@ -737,15 +720,7 @@ EPNP_HD int ransac_problem(Par& par, const Problem& P, const Params& prm, const 
                 }
             }
             par.sync();
-            for (int h = par.group(); h < nb; h += par.ngroups()) {
-                const Ws& wh = w.ws[h];
-                int cnt = 0;
-                for (int c0 = 0; c0 < N; c0 += par.lanes()) {
-                    const int c = c0 + par.lane();
-                    cnt += par.count(c < N && is_inlier(wh.Rb, wh.tb, w.corr, w.cap, c, P.K));
-                }
-                if (par.lane() == 0) w.counts[b0 + h] = cnt;
-            }
+            ransac::count_hypotheses(par, nb, N, [&](int h, int c) { return is_inlier(w.ws[h].Rb, w.ws[h].tb, w.corr, w.cap, c, P.K); }, w.counts + b0);
             par.sync();
             // the ordered scan (:209-238), by every thread alike
             for (int k = b0; k < b0 + nb && ret < 0; k++) {
@@ -773,14 +748,7 @@ EPNP_HD int ransac_problem(Par& par, const Problem& P, const Params& prm, const 
                     // Refine (:260-305) on mvbBestInliers
                     const Sel S{w.corr, w.cap, sel_row, nsel};
                     compute_pose(all, wr, S, P.K);
-                    int cnt2 = 0;
-                    for (int base = 0; base < N; base += nt) {
-                        const int c = base + tid;
-                        int total;
-                        (void)par.rank(c < N && is_inlier(wr.Rb, wr.tb, w.corr, w.cap, c, P.K), total);
-                        cnt2 += total;
-                    }
-                    refined = cnt2;
+                    refined = ransac::compact_ascending(par, N, [&](int c) { return is_inlier(wr.Rb, wr.tb, w.corr, w.cap, c, P.K); }, [](int, int) {});
                 }
                 if (refined > minInl) ret = k;
             }

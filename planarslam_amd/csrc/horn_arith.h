@@ -3,13 +3,14 @@
 // (:167-181) on glibc's rand() through DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50), Horn's closed form as ComputeSim3 (:230-341) runs it
 // through OpenCV 3.4 (cv::reduce, cv::gemm, cv::eigen = JacobiImpl_<float>, cv::Rodrigues, Mat::dot, cv::pow), CheckInliers (:344-368) and the ordered scan over
 // the inlier counts that iterate's loop amounts to (:187-204).  The protocol is a template over a `Par` that says how a thread takes its share: a workgroup on the
-// device, a single thread on the CPU.  -ffp-contract=off.  The float products restate ref_arith.h's small-matrix row (that header is device code only).  DESIGN.md §4.15.
+// device, a single thread on the CPU; what it shares with PnPsolver's (the key point, the picks, the compaction, the count per hypothesis, the tail of
+// SetRansacParameters) is ransac_proto.h.  -ffp-contract=off.  The float products restate ref_arith.h's small-matrix row (that header is device code only).  DESIGN.md §4.15.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "geom_dev.h"
-#include "glibc_rand.h"
+#include "ransac_proto.h"
 
 #if defined(__HIPCC__)
 #define HORN_HD __host__ __device__ __forceinline__
@@ -20,12 +21,13 @@
 namespace planar {
 namespace horn {
 
-constexpr int MAX_LEVELS = 16;        // PLANAR_MAX_LEVELS: an octave outside the levels is taken modulo it, as the other entry points do
+using ransac::Key;
+using ransac::MAX_LEVELS;
+using ransac::pick3;
+
 constexpr int MAX_ITS_CAP = 1024;     // PLANAR_HORN_MAX_ITS: the draws and counts of one call are kept on chip
 constexpr int CORR_ROWS = 13;         // per correspondence: X3Dc1 (3), X3Dc2 (3), P1im1 (2), P2im2 (2), maxError1, maxError2, i1 (int32): rows of `cap` entries
 
-struct Key { float x, y, size, angle, response; int32_t octave, class_id; };   // planar_keypoint
-static_assert(sizeof(Key) == 28, "planar_keypoint");
 struct Cam { float fx, fy, cx, cy; };
 
 // one row of cv::gemm's CV_32F small-matrix path (inner length 3, no transpose flag): products summed in float, left to right, then alpha and beta * C in double
@@ -81,34 +83,6 @@ HORN_HD void corr_setup(const Pair& P, int i, float* corr, int cap, int c) {
     corr[10 * cap + c] = max_error(P.sig1[(unsigned)P.keys1[i].octave % MAX_LEVELS]);
     corr[11 * cap + c] = max_error(P.sig2[(unsigned)P.keys2[i2].octave % MAX_LEVELS]);
     ((int32_t*)corr)[12 * cap + c] = i;
-}
-
-// DUtils::Random::RandomInt(0, size - 1) on one rand() value
-HORN_HD int random_int(int r, int size) { return (int)(((double)r / ((double)2147483647 + 1.0)) * size); }
-// the three picks of :170-181 out of vAvailableIndices = 0 .. N-1 with the swap-with-back rule, N >= 3
-HORN_HD void pick3(int r0, int r1, int r2, int N, int idx[3]) {
-    const int a = random_int(r0, N), b = random_int(r1, N - 1), c = random_int(r2, N - 2);
-    idx[0] = a;                                   // position a now holds N - 1, the list is N - 1 long
-    idx[1] = b == a ? N - 1 : b;
-    const int back = (N - 2) == a ? N - 1 : N - 2;   // what the second pop moves into position b
-    idx[2] = c == b ? back : (c == a ? N - 1 : c);
-}
-
-// PnPsolver::iterate (reference src/PnPsolver.cc:191-201): the four picks out of vAvailableIndices = 0 .. N-1 with the swap-with-back rule, N >= 4, in closed
-// form: at most three positions hold an entry that is no longer their own index
-HORN_HD void pick4(int r0, int r1, int r2, int r3, int N, int idx[4]) {
-    const int p0 = random_int(r0, N), p1 = random_int(r1, N - 1), p2 = random_int(r2, N - 2), p3 = random_int(r3, N - 3);
-    // entry at position p after the earlier swaps: position q_k was overwritten with the entry of the then-last position
-    const int v0 = p0;                                   // list = identity
-    const int e0 = N - 1;                                // position p0 now holds entry(N - 1) = N - 1
-    const int v1 = p1 == p0 ? e0 : p1;
-    const int b1 = (N - 2) == p0 ? e0 : N - 2;           // the entry of the last position (N - 2) of the second list, moved into p1
-    // third list (length N - 2): position p1 holds b1, position p0 holds e0 unless p1 == p0 overwrote it
-    const int v2 = p2 == p1 ? b1 : (p2 == p0 ? e0 : p2);
-    const int l3 = N - 3;                                // the last position of the third list, moved into p2
-    const int b2 = l3 == p1 ? b1 : (l3 == p0 ? e0 : l3);
-    const int v3 = p3 == p2 ? b2 : (p3 == p1 ? b1 : (p3 == p0 ? e0 : p3));
-    idx[0] = v0; idx[1] = v1; idx[2] = v2; idx[3] = v3;
 }
 
 // ---- cv::eigen of a symmetric 4x4 CV_32F: JacobiImpl_<float> (OpenCV 3.4 core/src/lapack.cpp), eigenvalues descending, eigenvectors in rows ----
@@ -310,18 +284,9 @@ HORN_HD bool is_inlier(const float* T12, const float* T21, const float* corr, in
     return e1 < corr[10 * cap + c] && e2 < corr[11 * cap + c];
 }
 
-// mRansacMaxIts of SetRansacParameters (:118-142) for N correspondences: host libm arithmetic.  Where the double is not an int (NaN for N < minInliers, an overflow
-// for a tiny epsilon) the conversion is undefined in C++; x86-64 yields INT_MIN there, which the max() turns into 1, and that is what this returns.
+// mRansacMaxIts of SetRansacParameters (:118-142) for N correspondences: host libm arithmetic
 static inline int ransac_max_its(double prob, int min_inliers, int max_its, int N) {
-    const float epsilon = (float)min_inliers / N;
-    int nIterations;
-    if (min_inliers == N) nIterations = 1;
-    else {
-        const double v = ceil(log(1 - prob) / log(1 - pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
-    }
-    const int m = nIterations < max_its ? nIterations : max_its;
-    return m > 1 ? m : 1;
+    return ransac::ransac_iterations(prob, (float)min_inliers / N, max_its, min_inliers == N);
 }
 
 struct Params { int min_inliers, n_iterations, fix_scale; uint32_t seed; const int32_t* max_its_table; /* [stride1 + 1] */ };
@@ -349,24 +314,14 @@ HORN_HD void make_hyp(const Work& w, int N, int k, bool fix_scale, Hyp& H, float
     compute_sim3(P1, P2, fix_scale, H, ws);
 }
 
-// ---- the protocol: one iterate(n_iterations) of one pair.  Par: tid(), nt(), sync(); rank(flag, total): the number of threads below this one whose flag is set and,
-// in total, of all (every thread calls it); group(), ngroups(), lane(), lanes(): the threads as groups that count together; count(flag): the flags set in the
-// thread's group (every thread of the group calls it).  Returns N.
+// ---- the protocol: one iterate(n_iterations) of one pair.  Par: ransac_proto.h.  Returns N.
 template <class Par>
 HORN_HD int ransac_pair(Par& par, const Pair& P, const Params& prm, const State& st, const Out& out, const Work& w) {
     const int tid = par.tid(), nt = par.nt();
     const bool fix_scale = prm.fix_scale != 0;
     float* const ws = w.hyp + tid * HYP_FLOATS;   // this thread's row
     // the constructor: correspondences in ascending i1
-    int N = 0;
-    for (int base = 0; base < P.n1; base += nt) {
-        const int i = base + tid;
-        const bool f = i < P.n1 && corresponds(P, i);
-        int total;
-        const int pos = par.rank(f, total);
-        if (f) corr_setup(P, i, w.corr, w.cap, N + pos);
-        N += total;
-    }
+    const int N = ransac::compact_ascending(par, P.n1, [&](int i) { return corresponds(P, i); }, [&](int i, int c) { corr_setup(P, i, w.corr, w.cap, c); });
     for (int i = tid; i < P.stride1; i += nt) { out.inliers[i] = 0; if (out.match12_inl) out.match12_inl[i] = -1; }   // vbInliers = vector<bool>(mN1, false)
     const int run0 = *st.best_inliers;
     int k0 = *st.its_done;
@@ -396,15 +351,10 @@ HORN_HD int ransac_pair(Par& par, const Pair& P, const Params& prm, const State&
                 for (int e = 0; e < 12; e++) { o[e] = H.T12[e]; o[12 + e] = H.T21[e]; }
             }
             par.sync();
-            for (int h = par.group(); h < nb; h += par.ngroups()) {
+            ransac::count_hypotheses(par, nb, N, [&](int h, int c) {
                 const float* T = w.hyp + h * HYP_FLOATS;
-                int cnt = 0;
-                for (int c0 = 0; c0 < N; c0 += par.lanes()) {
-                    const int c = c0 + par.lane();
-                    cnt += par.count(c < N && is_inlier(T, T + 12, w.corr, w.cap, c, P.K1, P.K2));
-                }
-                if (par.lane() == 0) w.counts[b0 + h] = cnt;
-            }
+                return is_inlier(T, T + 12, w.corr, w.cap, c, P.K1, P.K2);
+            }, w.counts + b0);
             par.sync();
             // the ordered scan (:187-204), by every thread alike
             for (int k = b0; k < b0 + nb && ret < 0; k++) {

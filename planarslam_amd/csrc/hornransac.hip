@@ -11,15 +11,16 @@
 //     correspondences, by ballot;
 //   * every thread runs the ordered scan over the counts of the batch ("best so far" with >=, return at the first count above min_inliers) and the batches stop at a
 //     return; the hypothesis that is left as the best (and the one that returns: the same) is computed once more instead of having been kept.
-// All arithmetic and the protocol itself are horn_arith.h, which the CPU test compiles too.  No MFMA: there is no dense contraction here (3x3 and 4x4 per hypothesis).
+// All arithmetic and the protocol itself are horn_arith.h (with ransac_proto.h), which the CPU test compiles too; the workgroup as the protocol's team is wg_team.h.  No MFMA: there is no dense contraction here (3x3 and 4x4 per hypothesis).
 #include "common.h"
 #include "horn_arith.h"
+#include "ref_arith.h"
+#include "wg_team.h"
 
 namespace planar {
 namespace horn {
 
 constexpr int NT = 256;
-constexpr int LDS_CORR = 512;   // key points of pKF1 up to which the correspondences live in LDS
 
 struct Args {
     planar_frame_view kf1, kf2;
@@ -51,36 +52,12 @@ struct Lds {
 static_assert(sizeof(Lds) == 81168, "DESIGN.md 4.15 states the LDS of horn_ransac_kernel");
 static_assert(MAX_ITS_CAP == PLANAR_HORN_MAX_ITS && MAX_LEVELS == PLANAR_MAX_LEVELS, "horn_arith.h restates the header's limits");
 
-struct Workgroup {   // Par of ransac_pair
-    Lds* l;
-    __device__ __forceinline__ int tid() const { return threadIdx.x; }
-    __device__ __forceinline__ int nt() const { return NT; }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ int rank(bool f, int& total) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const unsigned long long m = __ballot(f);
-        if (lane == 0) l->wsum[wave] = __popcll(m);
-        __syncthreads();
-        int below = 0;
-        total = 0;
-#pragma unroll
-        for (int w = 0; w < NT / 64; w++) { const int s = l->wsum[w]; total += s; below += w < wave ? s : 0; }
-        __syncthreads();
-        return below + __popcll(m & ((1ull << lane) - 1ull));
-    }
-    __device__ __forceinline__ int group() const { return threadIdx.x >> 6; }
-    __device__ __forceinline__ int ngroups() const { return NT / 64; }
-    __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
-    __device__ __forceinline__ int lanes() const { return 64; }
-    __device__ __forceinline__ int count(bool f) const { return __popcll(__ballot(f)); }
-};
-
 __global__ __launch_bounds__(NT) void horn_ransac_kernel(Args a) {
     __shared__ Lds lds;
     const int b = blockIdx.x;
     Pair P;
-    P.n1 = a.kf1.n[b]; P.n1 = P.n1 < 0 ? 0 : (P.n1 > a.kf1.stride ? a.kf1.stride : P.n1);
-    P.n2 = a.kf2.n[b]; P.n2 = P.n2 < 0 ? 0 : (P.n2 > a.kf2.stride ? a.kf2.stride : P.n2);
+    P.n1 = ref::clamp_n(a.kf1.n[b], a.kf1.stride);
+    P.n2 = ref::clamp_n(a.kf2.n[b], a.kf2.stride);
     P.stride1 = a.kf1.stride;
     const size_t o1 = (size_t)b * a.kf1.stride, o2 = (size_t)b * a.kf2.stride;
     P.keys1 = (const Key*)(a.kf1.keys_un + o1); P.keys2 = (const Key*)(a.kf2.keys_un + o2);
@@ -104,10 +81,9 @@ __global__ __launch_bounds__(NT) void horn_ransac_kernel(Args a) {
     const Out out{a.found + b, a.no_more + b, a.n_inliers + b, a.inliers + o1, a.R12 + 9 * (size_t)b, a.t12 + 3 * (size_t)b, a.s12 + b,
                   a.match12_inl ? a.match12_inl + o1 : nullptr, a.S12 ? a.S12 + 8 * (size_t)b : nullptr};
     Work w;
-    if (P.n1 <= LDS_CORR) { w.corr = lds.corr; w.cap = LDS_CORR; }
-    else { w.corr = a.scratch + (size_t)b * CORR_ROWS * a.kf1.stride; w.cap = a.kf1.stride; }   // n1 > LDS_CORR implies stride1 > LDS_CORR: the block exists
+    corr_tier(b, P.n1, a.kf1.stride, CORR_ROWS, lds.corr, a.scratch, w.corr, w.cap);
     w.draws = lds.draws; w.counts = lds.counts; w.hyp = lds.hyp; w.hyp_batch = NT; w.ring = lds.ring;
-    Workgroup wg{&lds};
+    WorkgroupTeam<NT> wg{lds.wsum, nullptr};   // Par of ransac_pair
     ransac_pair(wg, P, prm, st, out, w);
 }
 
@@ -115,19 +91,6 @@ __global__ __launch_bounds__(NT) void horn_ransac_kernel(Args a) {
 }  // namespace planar
 
 using namespace planar;
-
-// the table of mRansacMaxIts over N in [0, PLANAR_MAX_FRAME_KEYS], kept in the context per (prob, min_inliers, max_its)
-static int ensure_max_its_table(planar_ctx* ctx, double prob, int min_inliers, int max_its) {
-    if (ctx->horn_table.p && ctx->horn_prob == prob && ctx->horn_min_inliers == min_inliers && ctx->horn_max_its == max_its) return PLANAR_OK;
-    if (ctx->horn_table.p) PLANAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // a previous kernel may still be reading the table, a previous copy the host block
-    else if (int rc = ctx->horn_table.alloc((PLANAR_MAX_FRAME_KEYS + 1) * sizeof(int32_t))) return rc;
-    ctx->horn_table_host.resize(PLANAR_MAX_FRAME_KEYS + 1);
-    for (int N = 0; N <= PLANAR_MAX_FRAME_KEYS; N++) ctx->horn_table_host[N] = horn::ransac_max_its(prob, min_inliers, max_its, N);
-    ctx->horn_prob = -1;
-    PLANAR_HIP_CHECK(hipMemcpyAsync(ctx->horn_table.p, ctx->horn_table_host.data(), (PLANAR_MAX_FRAME_KEYS + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    ctx->horn_prob = prob; ctx->horn_min_inliers = min_inliers; ctx->horn_max_its = max_its;
-    return PLANAR_OK;
-}
 
 static int check_horn_args(const void* ctx, const planar_frame_view* kf1, const planar_kf_points* mp1, const planar_frame_view* kf2, const planar_kf_points* mp2,
                            bool arrays, double prob, int max_its, int n_iterations) {
@@ -154,14 +117,15 @@ int planar_horn_ransac_dev(planar_ctx* ctx, const planar_frame_view* kf1, const 
                                  prob, max_its, n_iterations))
         return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = ensure_max_its_table(ctx, prob, min_inliers, max_its)) return rc;
+    // the table of mRansacMaxIts over N in [0, PLANAR_MAX_FRAME_KEYS]
+    if (int rc = ctx->horn_table.ensure(ctx->stream, ParamKey{prob, min_inliers, max_its, 0.f}, PLANAR_MAX_FRAME_KEYS + 1, [&](int32_t* t) {
+            for (int N = 0; N <= PLANAR_MAX_FRAME_KEYS; N++) t[N] = horn::ransac_max_its(prob, min_inliers, max_its, N);
+        }))
+        return rc;
     horn::Args a{};
     a.kf1 = *kf1; a.kf2 = *kf2; a.mp1 = *mp1; a.mp2 = *mp2;
-    a.match12 = d_match12; a.max_its_table = ctx->horn_table.as<int32_t>(); a.seeds = d_seeds;
-    if (kf1->stride > horn::LDS_CORR) {
-        if (int rc = ctx->ensure_scratch((size_t)kf1->B * horn::CORR_ROWS * kf1->stride * sizeof(float))) return rc;
-        a.scratch = ctx->scratch.as<float>();
-    }
+    a.match12 = d_match12; a.max_its_table = ctx->horn_table.dev.as<int32_t>(); a.seeds = d_seeds;
+    if (int rc = corr_scratch(ctx, kf1->B, horn::CORR_ROWS, kf1->stride, &a.scratch)) return rc;
     a.min_inliers = min_inliers; a.n_iterations = n_iterations; a.fix_scale = fix_scale;
     a.its_done = d_its_done; a.best_inliers = d_best_inliers; a.best_R = d_best_R; a.best_t = d_best_t; a.best_s = d_best_s;
     a.found = d_found; a.no_more = d_no_more; a.n_inliers = d_n_inliers; a.inliers = d_inliers;

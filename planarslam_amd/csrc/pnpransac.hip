@@ -13,17 +13,18 @@
 //   * every thread runs the ordered scan over the counts of the batch; at a strict improvement the best set is recorded (as flags in the state and as an index list
 //     next to the correspondences) and Refine runs with the whole workgroup as the team: the sums over the inliers one accumulator per thread, in the reference's
 //     order, the serial parts on thread 0.  Refine's outcome depends on the best set alone and is kept until the set changes.  The batches stop at a return.
-// All arithmetic and the protocol itself are epnp_arith.h, which the CPU test compiles too.  No MFMA: the only dense product is the 2n x 12 MtM, one accumulator per
+// All arithmetic and the protocol itself are epnp_arith.h (with ransac_proto.h), which the CPU test compiles too; the workgroup as the protocol's team is wg_team.h.  No MFMA: the only dense product is the 2n x 12 MtM, one accumulator per
 // entry with the rows in order.
 #include "common.h"
 #include "epnp_arith.h"
+#include "ref_arith.h"
+#include "wg_team.h"
 
 namespace planar {
 namespace epnp {
 
 constexpr int NT = 256;
 constexpr int SLOTS = NT / 16;   // hypotheses of a batch: every sixteenth lane
-constexpr int LDS_CORR = 512;    // key points of the frame up to which the correspondences live in LDS
 
 struct Args {
     planar_frame_view fr;
@@ -59,28 +60,7 @@ static_assert(sizeof(Lds) == 91864, "DESIGN.md 4.16 states the LDS of pnp_ransac
 static_assert(sizeof(Lds) <= 160 * 1024, "one CU's LDS");
 static_assert(MAX_ITS_CAP == PLANAR_PNP_MAX_ITS && MAX_ITS_DONE == PLANAR_PNP_MAX_ITS_DONE && MAX_LEVELS == PLANAR_MAX_LEVELS, "epnp_arith.h restates the header's limits");
 
-struct Workgroup {   // Par of ransac_problem
-    Lds* l;
-    __device__ __forceinline__ int tid() const { return threadIdx.x; }
-    __device__ __forceinline__ int nt() const { return NT; }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ int rank(bool f, int& total) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const unsigned long long m = __ballot(f);
-        if (lane == 0) l->wsum[wave] = __popcll(m);
-        __syncthreads();
-        int below = 0;
-        total = 0;
-#pragma unroll
-        for (int w = 0; w < NT / 64; w++) { const int s = l->wsum[w]; total += s; below += w < wave ? s : 0; }
-        __syncthreads();
-        return below + __popcll(m & ((1ull << lane) - 1ull));
-    }
-    __device__ __forceinline__ int group() const { return threadIdx.x >> 6; }
-    __device__ __forceinline__ int ngroups() const { return NT / 64; }
-    __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
-    __device__ __forceinline__ int lanes() const { return 64; }
-    __device__ __forceinline__ int count(bool f) const { return __popcll(__ballot(f)); }
+struct Workgroup : WorkgroupTeam<NT> {   // Par of ransac_problem: the team, and every sixteenth lane a hypothesis slot
     __device__ __forceinline__ int slot() const { return (threadIdx.x & 15) == 0 ? (int)(threadIdx.x >> 4) : -1; }
     __device__ __forceinline__ int slots() const { return SLOTS; }
 };
@@ -90,7 +70,7 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(Args a) {
     const int b = blockIdx.x;
     Problem P;
     P.stride = a.fr.stride;
-    P.n = a.fr.n[b]; P.n = P.n < 0 ? 0 : (P.n > a.fr.stride ? a.fr.stride : P.n);
+    P.n = ref::clamp_n(a.fr.n[b], a.fr.stride);
     P.kf_n = a.kf_stride;
     const size_t o = (size_t)b * a.fr.stride, ok = (size_t)b * a.kf_stride;
     P.keys = (const Key*)(a.fr.keys_un + o);
@@ -107,10 +87,9 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(Args a) {
     const State st{a.its_done + b, a.best_inliers + b, a.best_set + o, a.best_Tcw + 16 * (size_t)b};
     const Out out{a.found + b, a.no_more + b, a.n_inliers + b, a.inliers + o, a.Tcw + 16 * (size_t)b};
     Work w;
-    if (P.n <= LDS_CORR) { w.corr = lds.corr; w.cap = LDS_CORR; }
-    else { w.corr = a.scratch + (size_t)b * CORR_ROWS * a.fr.stride; w.cap = a.fr.stride; }   // n > LDS_CORR implies stride > LDS_CORR: the block exists
+    corr_tier(b, P.n, a.fr.stride, CORR_ROWS, lds.corr, a.scratch, w.corr, w.cap);
     w.draws = lds.draws; w.counts = lds.counts; w.ws = lds.ws; w.picks = lds.picks; w.ring = lds.ring; w.hyp_out = nullptr;
-    Workgroup wg{&lds};
+    Workgroup wg{{lds.wsum, nullptr}};
     ransac_problem(wg, P, prm, st, out, w);
 }
 
@@ -118,24 +97,6 @@ __global__ __launch_bounds__(NT) void pnp_ransac_kernel(Args a) {
 }  // namespace planar
 
 using namespace planar;
-
-// the tables of mRansacMaxIts and the adjusted mRansacMinInliers over N in [0, PLANAR_MAX_FRAME_KEYS], kept in the context per (prob, min_inliers, max_its, epsilon)
-static int ensure_pnp_table(planar_ctx* ctx, double prob, int min_inliers, int max_its, float epsilon) {
-    constexpr int TN = PLANAR_MAX_FRAME_KEYS + 1;
-    if (ctx->pnp_table.p && ctx->pnp_prob == prob && ctx->pnp_min_inliers == min_inliers && ctx->pnp_max_its == max_its && ctx->pnp_epsilon == epsilon) return PLANAR_OK;
-    if (ctx->pnp_table.p) PLANAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // a previous kernel may still be reading the table, a previous copy the host block
-    else if (int rc = ctx->pnp_table.alloc(2 * TN * sizeof(int32_t))) return rc;
-    ctx->pnp_table_host.resize(2 * TN);
-    for (int N = 0; N < TN; N++) {
-        int mi, it;
-        epnp::ransac_table(prob, min_inliers, max_its, 4, epsilon, N, mi, it);
-        ctx->pnp_table_host[N] = it; ctx->pnp_table_host[TN + N] = mi;
-    }
-    ctx->pnp_prob = -1;
-    PLANAR_HIP_CHECK(hipMemcpyAsync(ctx->pnp_table.p, ctx->pnp_table_host.data(), 2 * TN * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    ctx->pnp_prob = prob; ctx->pnp_min_inliers = min_inliers; ctx->pnp_max_its = max_its; ctx->pnp_epsilon = epsilon;
-    return PLANAR_OK;
-}
 
 static int check_pnp_args(const void* ctx, const planar_frame_view* fr, bool arrays, int kf_stride, double prob, int max_its, int min_set, int n_iterations) {
     PLANAR_REQUIRE(ctx && fr && arrays, PLANAR_EINVAL, "null argument");
@@ -161,15 +122,17 @@ int planar_pnp_ransac_dev(planar_ctx* ctx, const planar_frame_view* fr, const ui
                                 kf_stride, prob, max_its, min_set, n_iterations))
         return rc;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = ensure_pnp_table(ctx, prob, min_inliers, max_its, epsilon)) return rc;
+    // the tables of mRansacMaxIts and the adjusted mRansacMinInliers over N in [0, PLANAR_MAX_FRAME_KEYS]
+    constexpr int TN = PLANAR_MAX_FRAME_KEYS + 1;
+    if (int rc = ctx->pnp_table.ensure(ctx->stream, ParamKey{prob, min_inliers, max_its, epsilon}, 2 * TN, [&](int32_t* t) {
+            for (int N = 0; N < TN; N++) epnp::ransac_table(prob, min_inliers, max_its, 4, epsilon, N, t[TN + N], t[N]);
+        }))
+        return rc;
     epnp::Args a{};
     a.fr = *fr;
     a.kf_usable = d_kf_usable; a.kf_xw = d_kf_xw; a.kf_stride = kf_stride; a.match = d_match;
-    a.table = ctx->pnp_table.as<int32_t>(); a.seeds = d_seeds;
-    if (fr->stride > epnp::LDS_CORR) {
-        if (int rc = ctx->ensure_scratch((size_t)fr->B * epnp::CORR_ROWS * fr->stride * sizeof(float))) return rc;
-        a.scratch = ctx->scratch.as<float>();
-    }
+    a.table = ctx->pnp_table.dev.as<int32_t>(); a.seeds = d_seeds;
+    if (int rc = corr_scratch(ctx, fr->B, epnp::CORR_ROWS, fr->stride, &a.scratch)) return rc;
     a.th2 = th2; a.n_iterations = n_iterations;
     a.its_done = d_its_done; a.best_inliers = d_best_inliers; a.best_set = d_best_set; a.best_Tcw = d_best_Tcw;
     a.found = d_found; a.no_more = d_no_more; a.n_inliers = d_n_inliers; a.inliers = d_inliers; a.Tcw = d_Tcw;

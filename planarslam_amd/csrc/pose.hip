@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "geom_dev.h"
+#include "wg_team.h"
 
 namespace planar {
 namespace pose {
@@ -149,6 +150,7 @@ struct ParamsDev {
 };
 
 struct Acc { double h[21]; double b[6]; double chi; };
+static_assert(sizeof(Acc) == 28 * sizeof(double), "pose_opt_kernel sums an Acc as double[28]");
 
 __device__ __forceinline__ void robustify(double c2, double delta, double& rho0, double& rho1) {
     const double dsqr = delta * delta;
@@ -280,41 +282,6 @@ __device__ __forceinline__ void plane_info(const ParamsDev& P, int kind, int& di
 constexpr int NT = 256;
 constexpr int MAX_PLANE_EDGES = 96;   // planes * kinds handled per frame (LDS scratch for numeric Jacobians)
 
-// block reduction of n doubles held per thread in v[] -> result broadcast to all threads
-template <int N>
-__device__ void block_reduce(double* v, double* lds /* [4][N] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        v[k] = x;
-    }
-    __syncthreads();
-    if (lane == 0) for (int k = 0; k < N; k++) lds[wave * N + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = (lds[k] + lds[N + k]) + (lds[2 * N + k] + lds[3 * N + k]);
-}
-
-// the same sums (same association), left in LDS at dst[0 .. N) instead of in every thread's registers: what follows an evaluation is wavefront-uniform work (the 6x6
-// solve, the gain ratio), and 28 doubles x 256 threads of registers held across it are what used to spill
-template <int N>
-__device__ __forceinline__ void block_reduce_to(const double* v, double* lds /* [4][N] */, double* dst /* [N], LDS */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        if (lane == 0) lds[wave * N + k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) { const int k = threadIdx.x; dst[k] = (lds[k] + lds[N + k]) + (lds[2 * N + k] + lds[3 * N + k]); }
-    __syncthreads();
-}
 __device__ __forceinline__ void se3_store(double* p, const SE3& T) { p[0] = T.r.x; p[1] = T.r.y; p[2] = T.r.z; p[3] = T.r.w; p[4] = T.t.x; p[5] = T.t.y; p[6] = T.t.z; }
 __device__ __forceinline__ SE3 se3_load(const double* p) { SE3 T; T.r.x = p[0]; T.r.y = p[1]; T.r.z = p[2]; T.r.w = p[3]; T.t.x = p[4]; T.t.y = p[5]; T.t.z = p[6]; return T; }
 constexpr int UNI_DOUBLES = 28 + 3 * 8;   // wavefront-uniform state kept in LDS: H | b | chi of the last evaluation, T0, T_eval, the LM step's backup pose
@@ -345,6 +312,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
 
     // LDS carve: reduction scratch, numeric-Jacobian scratch, levels
     double* red = (double*)smem;                              // [4][28]
+    const WorkgroupTeam<NT> team{nullptr, red};               // the workgroup sums: the rows of red packed at the length of each sum
     double* uH = red + 4 * 28;                                // [21] H, [6] b, [1] chi of the last full evaluation (uniform)
     double* uT0 = uH + 28; double* uTe = uT0 + 8; double* uBk = uTe + 8;   // T0, T_eval, the LM step's backup
     double* pj = uH + UNI_DOUBLES;                            // [3 * max_planes][13][3] perturbed errors (12) + the error itself
@@ -366,7 +334,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
         lvl_ln[i] = v ? 0 : 2;
         if (v) { o_ln[i] = 0; if (P.mode == 0) cnt[0] += 1; cnt[1] += 2; }
     }
-    block_reduce<2>(cnt, red);
+    team.reduce(cnt);
     const bool early_translation = P.mode == 1 && (int)cnt[0] < 3;   // :3199-3201 (before plane edges are built)
     double cntp[2] = {0, 0};
     if (!early_translation) {
@@ -377,7 +345,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
             if (v) { o_pl[3 * i + kind] = 0; if (P.mode == 0) cntp[0] += 1; cntp[1] += 1; }
         }
     }
-    block_reduce<2>(cntp, red);
+    team.reduce(cntp);
     const int nInitial = (int)cnt[0] + (int)cntp[0];
     const int nEdges = (int)cnt[1] + (int)cntp[1];
     float* Tout = Bt.Tcw_out + (size_t)b * 16;
@@ -486,7 +454,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
         for (int i = tid; i < F.np; i += NT) act[0] += lvl_pt[i] == 0;
         for (int i = tid; i < F.nl; i += NT) act[0] += lvl_ln[i] == 0;
         for (int pe = tid; pe < npe; pe += NT) act[0] += lvl_pl[pe] == 0;
-        block_reduce<1>(act, red);
+        team.reduce(act);
         if (act[0] > 0) {
             double lambda = -1, ni = 2;
             int nBadIt = 0;
@@ -496,7 +464,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
                     Acc acc;
                     evaluate(T, true, acc);
                     if (tid == 0) se3_store(uTe, T);              // T_eval (read after the barriers of the reduction)
-                    block_reduce_to<28>((const double*)&acc, red, uH);
+                    team.reduce_to(*(const double(*)[28])&acc, uH);
                 }
                 double currentChi = uH[27], tempChi = currentChi;
                 const double iniChi = currentChi;
@@ -516,7 +484,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
                     double c1[1];
                     { Acc trial; evaluate(T, false, trial); c1[0] = trial.chi; }
                     if (tid == 0) se3_store(uTe, T);              // T_eval
-                    block_reduce<1>(c1, red);
+                    team.reduce(c1);
                     tempChi = ok2 ? c1[0] : 1.7976931348623157e308;
                     rho = currentChi - tempChi;
                     double scale = 0;
@@ -588,7 +556,7 @@ __global__ __launch_bounds__(NT, 2) void pose_opt_kernel(BatchDev Bt, ParamsDev 
             lvl_pl[pe] = out ? 1 : 0; o_pl[3 * i + kind] = out ? 1 : 0;
             bad[0] += out;
         }
-        block_reduce<1>(bad, red);
+        team.reduce(bad);
         nBad = (int)bad[0];
         if (strip) robust = false;
         if (nEdges < 10) break;                              // :1265

@@ -1,5 +1,6 @@
 // planarslam_amd/csrc/ref_arith.h — the reference's float / double arithmetic, one definition per path, for the matcher and map-creation kernels
-// (guided.hip, loopmatch.hip and their match_chunk.h, frame.hip, triangulate.hip, newlines.hip; lsd.hip takes the workgroup scan).  Which path of OpenCV a small product takes decides its
+// (guided.hip, loopmatch.hip and their match_chunk.h, frame.hip, triangulate.hip, newlines.hip; lsd.hip takes the workgroup scan; hornransac.hip, pnpransac.hip and
+// sim3opt.hip take clamp_n alone: their arithmetic is horn_arith.h, epnp_arith.h and sim3_arith.h).  Which path of OpenCV a small product takes decides its
 // last bit, so a name here says the path and its comment where the reference takes it.  Expressions only, device code only;
 // -ffp-contract=off.  The checkers (oracle/, tests/host_shim/) restate all of this on their own and must not include this file.
 #pragma once

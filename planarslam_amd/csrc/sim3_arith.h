@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "geom_dev.h"
+#include "ransac_proto.h"   // Key, MAX_LEVELS
 
 #if defined(__HIPCC__)
 #define SIM3_HD __host__ __device__ __forceinline__
@@ -27,12 +28,11 @@ namespace sim3 {
 
 using namespace geomd;
 
-constexpr int MAX_LEVELS = 16;   // PLANAR_MAX_LEVELS: an octave outside the levels is taken modulo it, as the other entry points do
+using ransac::Key;
+using ransac::MAX_LEVELS;
 
 struct Sim3 { Quat r; V3 t; double s; };
 struct Cam { double fx, fy, cx, cy; };
-struct Key { float x, y, size, angle, response; int32_t octave, class_id; };   // planar_keypoint
-static_assert(sizeof(Key) == 28, "planar_keypoint");
 
 // ---- g2o::Sim3 -------------------------------------------------------------------------------------------------------------------------------------------------
 SIM3_HD M3 skew(V3 v) { return M3{{{0, -v.z, v.y}, {v.z, 0, -v.x}, {-v.y, v.x, 0}}}; }

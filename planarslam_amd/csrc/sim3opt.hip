@@ -10,9 +10,11 @@
 //     workgroup-uniform;
 //   * the errors are never stored: a classification reads chi2() of g2o's LAST evaluation, possibly a rejected trial, so the estimate of that evaluation is kept
 //     (Shared::S_eval) and the errors are evaluated again.
-// All arithmetic and the protocol itself are sim3_arith.h, which the CPU test compiles too.  No MFMA: there is no dense contraction here (7x7 per pair).
+// All arithmetic and the protocol itself are sim3_arith.h, which the CPU test compiles too; the workgroup as the protocol's team, with its sums, is wg_team.h.  No MFMA: there is no dense contraction here (7x7 per pair).
 #include "common.h"
 #include "sim3_arith.h"
+#include "ref_arith.h"
+#include "wg_team.h"
 
 namespace planar {
 namespace sim3 {
@@ -40,53 +42,12 @@ struct Lds {
 };
 static_assert(sizeof(Lds) == 7520, "DESIGN.md 4.14 states the LDS of optimize_sim3_kernel");
 
-struct Workgroup {   // Par of optimize_pair
-    Lds* l;
-    __device__ __forceinline__ int tid() const { return threadIdx.x; }
-    __device__ __forceinline__ int nt() const { return NT; }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    // the sum over the workgroup, in every thread, by the same association in every thread: lanes by xor-shuffle, then the four waves
-    template <int N> __device__ __forceinline__ void reduce(double (&v)[N]) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            double x = v[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-            v[k] = x;
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < N; k++) l->red[wave][k] = v[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = (l->red[0][k] + l->red[1][k]) + (l->red[2][k] + l->red[3][k]);
-    }
-    // the same sums by the same association, left in dst (LDS) for every thread to read
-    template <int N> __device__ __forceinline__ void reduce_to(const double (&v)[N], double* dst) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            double x = v[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-            if (lane == 0) l->red[wave][k] = x;
-        }
-        __syncthreads();
-        if (threadIdx.x < N) { const int k = threadIdx.x; dst[k] = (l->red[0][k] + l->red[1][k]) + (l->red[2][k] + l->red[3][k]); }
-        __syncthreads();
-    }
-};
-
 __global__ __launch_bounds__(NT) void optimize_sim3_kernel(Args a) {
     __shared__ Lds lds;
     const int b = blockIdx.x;
     Pair P;
-    P.n1 = a.kf1.n[b]; P.n1 = P.n1 < 0 ? 0 : (P.n1 > a.kf1.stride ? a.kf1.stride : P.n1);
-    P.n2 = a.kf2.n[b]; P.n2 = P.n2 < 0 ? 0 : (P.n2 > a.kf2.stride ? a.kf2.stride : P.n2);
+    P.n1 = ref::clamp_n(a.kf1.n[b], a.kf1.stride);
+    P.n2 = ref::clamp_n(a.kf2.n[b], a.kf2.stride);
     const size_t o1 = (size_t)b * a.kf1.stride, o2 = (size_t)b * a.kf2.stride;
     P.keys1 = (const Key*)(a.kf1.keys_un + o1); P.keys2 = (const Key*)(a.kf2.keys_un + o2);
     P.usable1 = a.mp1.usable + o1; P.usable2 = a.mp2.usable + o2;
@@ -101,7 +62,7 @@ __global__ __launch_bounds__(NT) void optimize_sim3_kernel(Args a) {
     __syncthreads();
     P.sf1 = lds.sf1; P.sf2 = lds.sf2;
     P.match12 = a.match12 + o1;
-    Workgroup wg{&lds};
+    WorkgroupTeam<NT, ACC_DOUBLES> wg{nullptr, &lds.red[0][0]};   // Par of optimize_pair
     const int nIn = optimize_pair(wg, P, a.S12 + (size_t)b * 8, a.th2, a.fix_scale != 0, lds.lvl, lds.sh, a.lm_iters ? a.lm_iters + 2 * (size_t)b : nullptr, (Events*)nullptr);
     if (threadIdx.x == 0) a.n_inliers[b] = nIn;
 }

@@ -111,7 +111,7 @@ def load_host(opt="-O2"):
     if opt in _HOST:
         return _HOST[opt]
     src = os.path.join(ROOT, "tests", "host_shim", "horn_ransac_host.cpp")
-    hdrs = [os.path.join(ROOT, "planarslam_amd", "csrc", h) for h in ("horn_arith.h", "glibc_rand.h", "geom_dev.h")]
+    hdrs = [os.path.join(ROOT, "planarslam_amd", "csrc", h) for h in ("horn_arith.h", "ransac_proto.h", "glibc_rand.h", "geom_dev.h")]
     so = os.path.join(ROOT, "tests", "host_shim", "libhorn_ransac_host" + ("" if opt == "-O2" else opt.replace("-", "_")) + ".so")
     if not os.path.exists(so) or max(os.path.getmtime(p) for p in [src] + hdrs) > os.path.getmtime(so):
         subprocess.check_call(["g++", opt, "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-o", so, src])

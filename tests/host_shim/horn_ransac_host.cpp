@@ -10,20 +10,6 @@
 
 using namespace planar::horn;
 
-namespace {
-struct Serial {   // Par of ransac_pair: one thread is every group
-    int tid() const { return 0; }
-    int nt() const { return 1; }
-    void sync() const {}
-    int rank(bool f, int& total) const { total = f; return 0; }
-    int group() const { return 0; }
-    int ngroups() const { return 1; }
-    int lane() const { return 0; }
-    int lanes() const { return 1; }
-    int count(bool f) const { return f; }
-};
-}  // namespace
-
 extern "C" {
 
 struct horn_host_kf {
@@ -64,7 +50,7 @@ int horn_ransac_host(const horn_host_kf* kf1, const horn_host_kf* kf2, const int
     float hyp[HYP_FLOATS];
     uint32_t ring[31];
     const Work w{corr.data(), P.stride1, draws.data(), cnt.data(), hyp, 1, ring};
-    Serial par;
+    planar::ransac::SerialTeam par;
     const int before = *its_done < 0 ? 0 : *its_done;
     const int N = ransac_pair(par, P, prm, st, out, w);
     const int ran = *its_done - before;   // 0 where the state was left untouched

@@ -10,22 +10,6 @@
 
 using namespace planar::epnp;
 
-namespace {
-struct Serial {   // Par of ransac_problem: one thread is every group and the only slot
-    int tid() const { return 0; }
-    int nt() const { return 1; }
-    void sync() const {}
-    int rank(bool f, int& total) const { total = f; return 0; }
-    int group() const { return 0; }
-    int ngroups() const { return 1; }
-    int lane() const { return 0; }
-    int lanes() const { return 1; }
-    int count(bool f) const { return f; }
-    int slot() const { return 0; }
-    int slots() const { return 1; }
-};
-}  // namespace
-
 extern "C" {
 
 struct pnp_host_problem {
@@ -71,7 +55,7 @@ int pnp_ransac_host(const pnp_host_problem* p, double prob, int min_inliers, int
     int32_t picks[4];
     uint32_t ring[31];
     const Work w{corr.data(), P.stride, draws.data(), cnt.data(), ws.data(), picks, ring, hyp};
-    Serial par;
+    planar::ransac::SerialTeam par;
     const int before = *its_done < 0 ? 0 : *its_done;
     const int N = ransac_problem(par, P, prm, st, out, w);
     const int ran = *its_done - before;   // 0 where the state was left untouched

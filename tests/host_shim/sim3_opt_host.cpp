@@ -10,16 +10,6 @@
 
 using namespace planar::sim3;
 
-namespace {
-struct Serial {   // Par of optimize_pair: one thread holds every sum
-    int tid() const { return 0; }
-    int nt() const { return 1; }
-    void sync() const {}
-    template <int N> void reduce(double (&)[N]) const {}
-    template <int N> void reduce_to(const double (&v)[N], double* dst) const { for (int k = 0; k < N; k++) dst[k] = v[k]; }
-};
-}  // namespace
-
 extern "C" {
 
 struct sim3_host_kf {
@@ -43,7 +33,7 @@ int sim3_opt_host(const sim3_host_kf* kf1, const sim3_host_kf* kf2, double* S12,
     P.match12 = match12;
     std::vector<uint8_t> lvl((size_t)(P.n1 > 0 ? P.n1 : 1));
     Shared sh;
-    Serial par;
+    planar::ransac::SerialTeam par;
     if (ev) memset(ev, 0, sizeof *ev);
     return optimize_pair(par, P, S12, th2, fix_scale != 0, lvl.data(), sh, lm_iters, ev);
 }

@@ -115,6 +115,24 @@ def test_n_is_clamped_and_a_pair_below_min_inliers_keeps_its_state(ctx, cases):
     assert st_got["best_inliers"][1] == 11 and st_got["best_s"][1] == 3.5 and st_got["its_done"][1] == 0
 
 
+def test_a_changed_parameter_set_rebuilds_the_table(ctx):
+    """The context keeps the table of mRansacMaxIts for the (prob, min_inliers, max_its) of its last call.  A, B, A on one context, with B different in prob alone and
+    then in max_its alone: every call, from a fresh state, equals the host build called with the same parameters bit for bit.  The host build's its_done differs
+    between A and either B (the pair of N = 24 exhausts its 6, 1 and 3 iterations), so a table left from the call before would show."""
+    case = HC.pair_case(ns=(40, 24), stride=48, seed=8909, outliers=(0.3,), fix_scale=1)
+    A, B_PROB, B_ITS = (HC.PROB, HC.MIN_INLIERS, HC.MAX_ITS), (0.5, HC.MIN_INLIERS, HC.MAX_ITS), (HC.PROB, HC.MIN_INLIERS, 3)
+    L = HC.load_host()
+    host = {p: HC.host_call(L, case, HC.new_state(2), HC.MAX_ITS, *p)[:2] for p in (A, B_PROB, B_ITS)}
+    for p in (B_PROB, B_ITS):
+        assert (host[p][1]["its_done"] != host[A][1]["its_done"]).any(), p
+    for p in (A, B_PROB, A, B_ITS, A):
+        o, st = HC.gpu_call(ctx, "dev", case, HC.new_state(2), HC.MAX_ITS, *p)
+        for k in HC.OUT_KEYS:
+            assert o[k].tobytes() == host[p][0][k].tobytes(), (p, k)
+        for k in HC.STATE_KEYS:
+            assert st[k].tobytes() == host[p][1][k].tobytes(), (p, k)
+
+
 def _chain_inputs():
     """The synthetic pairs of tests/test_sim3_opt_gpu.py's chain (sim3_small_padded), as a KF-KF BoW case: every feature in one vocabulary node."""
     name, args, th = LC.SIM3_CASES[2]

@@ -111,6 +111,25 @@ def test_state_carried_over_calls_equals_one_long_call(ctx, G, DEV, flavour):
     assert carried >= 1 and carried < B                                  # both kinds are present
 
 
+def test_a_changed_parameter_set_rebuilds_the_table(ctx):
+    """The context keeps the tables of mRansacMaxIts and the adjusted mRansacMinInliers for the (prob, min_inliers, max_its, epsilon) of its last call.  A, B, A on one
+    context, with B different in prob alone and then in max_its alone: every call, from a fresh state, equals the host build called with the same parameters bit
+    for bit.  iterate(1) runs mRansacMaxIts iterations unless a Refine returns, and the host build's its_done differs between A and either B (35 iterations allowed
+    against 6 and 3), so a table left from the call before would show."""
+    A, B_PROB, B_ITS = PC.RELOC, (0.5,) + PC.RELOC[1:], PC.RELOC[:2] + (3,) + PC.RELOC[3:]
+    cases = {p: PC.problem_case(ns=(40, 24), stride=48, seed=9909, outliers=(0.3,), params=p, calls=(1,)) for p in (A, B_PROB, B_ITS)}
+    L = PC.load_host()
+    host = {p: PC.host_call(L, cases[p], PC.new_state(2, 48), 0)[:2] for p in cases}
+    for p in (B_PROB, B_ITS):
+        assert (host[p][1]["its_done"] != host[A][1]["its_done"]).any(), p
+    for p in (A, B_PROB, A, B_ITS, A):
+        o, st = PC.gpu_call(ctx, "dev", cases[p], PC.new_state(2, 48), 1)
+        for k in PC.OUT_KEYS:                                             # whole arrays: beyond n[b] both keep what new_outputs and new_state put there
+            assert o[k].tobytes() == host[p][0][k].tobytes(), (p, k)
+        for k in PC.STATE_KEYS:
+            assert st[k].tobytes() == host[p][1][k].tobytes(), (p, k)
+
+
 def _chain_inputs(seed=31, M=60, S=72, KS=80):
     """one lost frame and one candidate key frame: M shared points (a fifth of their key points moved), descriptors a few bits apart, one vocabulary node per point"""
     from planarslam_amd import synth

@@ -14,5 +14,5 @@ t = time.perf_counter(); n = 5
 for _ in range(n): r = local_bundle_adjustment(pr, TUM3, ctx=ctx)
 dt = (time.perf_counter() - t) / n
 t = time.perf_counter(); o = ol.local_ba(pr, TUM3); dc = time.perf_counter() - t
-print(f"config5 BA: edges {len(pr['e_kf'])} landmarks {len(pr['lm_type'])} | HIP {dt*1e3:.1f} ms/solve ({r['lm_iters']} LM iterations, {r['lm_iters']/dt:.0f} it/s) | "
+print(f"config5 BA: edges {len(pr['e_kf'])} landmarks {len(pr['lm_type'])} | HIP {dt*1e3:.3f} ms/solve ({r['lm_iters']} LM iterations, {r['lm_iters']/dt:.0f} it/s) | "
       f"oracle {dc*1e3:.0f} ms ({o['lm_iters']} it) | all-reduce payload {(60*60+60)*8} B per trial")
