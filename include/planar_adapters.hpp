@@ -23,16 +23,24 @@
 // plans live in one process-wide runtime (planar_adapter::Runtime), one context + stream + mutex per ROLE (points, lines, planes,
 // tracking), so the three extraction threads run concurrently and nothing is created or leaked per frame or per thread; plans are cached
 // by image size (and ORB parameters).  The adapter classes hold only host data and are freely copyable.
+//
+// Shared parts (namespace planar_adapter, right below the runtime; every section is composed of them):
+//   on_lane(role, "planar_xxx", call)      the one locked call: the role's lane, its mutex, the call on its context, the report through ok()
+//   mat_to_array / array_to_mat / rt_to_array / vec3_to_array, copy_scale_factors, copy_desc_rows, copy_keypoints    poses, scale tables, descriptor rows, key points
+//   ViewGather                             owner of one planar_frame_view and its storage, filled by parts (add_keys, add_desc, add_u_right, add_pose, ...): a part that
+//                                          names a member of a reference class is a template and is instantiated only by the sections that read that member
+//   PointGather                            a list of MapPoint* as usable / xw, plus normals, descriptors and distance range where a section asks for them
+//   tri_camera, plane_pose_params, sim3_entry_matches, apply_fuse_edits, UNTOUCHED / NOT_IN_KF2
 #pragma once
 #include <opencv2/core/core.hpp>
 #include <opencv2/features2d/features2d.hpp>
 
+#include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <tuple>
@@ -120,6 +128,192 @@ inline bool ok(int rc, const char* where) {
     return false;
 }
 
+// The one locked call: the role's lane, then its mutex, then the call on the lane's context, reported through ok() under the name `where`.
+template <class Call> inline bool on_lane(Role role, const char* where, Call call) {
+    Runtime::Lane& L = Runtime::get().lane(role);
+    std::lock_guard<std::mutex> g(L.mu);
+    return ok(call(L.ctx), where);
+}
+
+const int32_t UNTOUCHED = -2;      // a match slot the call did not write
+const int32_t NOT_IN_KF2 = -2;     // vpMatches12[i] is set but is no (usable) feature of pKF2: takes i out of the search, nothing else
+
+// ---- poses, scale tables, descriptor rows, key points ----
+inline void mat_to_array(const cv::Mat& T, float* a) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) a[4 * r + c] = T.at<float>(r, c); }   // 4x4
+inline cv::Mat array_to_mat(const float* a, int rows = 4, int cols = 4) { cv::Mat M(rows, cols, CV_32F); std::memcpy(M.data, a, sizeof(float) * rows * cols); return M; }
+// R (3x3) to Ra[ld * r + c], t (3x1) to ta[tstep * r]: R[9] and t[3] with (3, 1), the upper rows of a 4x4 with (Tcw, 4, Tcw + 3, 4)
+inline void rt_to_array(const cv::Mat& R, const cv::Mat& t, float* Ra, int ld, float* ta, int tstep) {
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Ra[ld * r + c] = R.at<float>(r, c); ta[tstep * r] = t.at<float>(r); }
+}
+inline void vec3_to_array(const cv::Mat& x, float* a) { for (int k = 0; k < 3; k++) a[k] = x.at<float>(k); }
+inline void copy_scale_factors(float* dst, const std::vector<float>& v) { for (size_t l = 0; l < v.size() && l < PLANAR_MAX_LEVELS; l++) dst[l] = v[l]; }
+inline void copy_desc_rows(uint8_t* dst, const cv::Mat& d, int rows) { for (int i = 0; i < rows; i++) std::memcpy(dst + (size_t)i * 32, d.ptr(i), 32); }
+inline void copy_keypoints(void* dst, const void* src, size_t count) {      // cv::KeyPoint <-> planar_keypoint, either way
+    static_assert(sizeof(cv::KeyPoint) == sizeof(planar_keypoint), "cv::KeyPoint layout");
+    if (count) std::memcpy(dst, src, count * sizeof(planar_keypoint));
+}
+
+// ---- one planar_frame_view and the storage behind it, filled by parts.  Nothing is set that no part set: a view without add_keys has n = keys_un = NULL and
+//      stride 1 (LSDmatcher::Fuse), one without add_pose has Tcw = NULL.  Arrays are padded to stride = max(n, 1); padded u_right is -1, everything else 0.  A copy
+//      points into its own storage. ----
+struct ViewGather {
+    int32_t n;
+    std::vector<planar_keypoint> keys;
+    std::vector<float> ur;
+    std::vector<uint8_t> desc, blocked;
+    float Tcw[16];
+    planar_frame_view view;
+
+    ViewGather() : n(0) { std::memset(&view, 0, sizeof(view)); view.B = 1; view.stride = 1; }
+    ViewGather(const ViewGather& o) { *this = o; }
+    ViewGather& operator=(const ViewGather& o) {
+        n = o.n; keys = o.keys; ur = o.ur; desc = o.desc; blocked = o.blocked; view = o.view;
+        std::memcpy(Tcw, o.Tcw, sizeof(Tcw));
+        return bind();
+    }
+    ViewGather& bind() {      // the view's pointers follow the storage (after a part filled it, after a copy)
+        view.n = keys.empty() ? nullptr : &n; view.keys_un = keys.empty() ? nullptr : keys.data();
+        view.u_right = ur.empty() ? nullptr : ur.data(); view.desc = desc.empty() ? nullptr : desc.data(); view.blocked = blocked.empty() ? nullptr : blocked.data();
+        if (view.Tcw) view.Tcw = Tcw;
+        return *this;
+    }
+    ViewGather& add_keys(const std::vector<cv::KeyPoint>& k, int count) {          // mvKeysUn; the first part: it sets n and the stride
+        n = count; keys.resize(n > 0 ? n : 1); view.stride = (int32_t)keys.size();
+        copy_keypoints(keys.data(), k.data(), n > 0 ? n : 0);
+        return bind();
+    }
+    ViewGather& add_desc(const cv::Mat& d) { desc.assign((size_t)view.stride * 32, 0); copy_desc_rows(desc.data(), d, n); return bind(); }              // mDescriptors
+    ViewGather& add_u_right(const std::vector<float>& v) {                          // mvuRight; -1 where it is empty
+        ur.assign(view.stride, -1.f);
+        if (!v.empty() && n > 0) std::copy(v.begin(), v.begin() + n, ur.begin());
+        return bind();
+    }
+    ViewGather& add_blocked() { blocked.assign(view.stride, 0); return bind(); }    // all free; the section sets the flags
+    template <class MapPointT> ViewGather& add_blocked_observed(const std::vector<MapPointT*>& mps) {       // mvpMapPoints[i] && ->Observations() > 0
+        add_blocked();
+        for (int i = 0; i < n; i++) if (mps[i] && mps[i]->Observations() > 0) blocked[i] = 1;
+        return *this;
+    }
+    ViewGather& add_pose(const cv::Mat& T) { if (!T.empty()) { mat_to_array(T, Tcw); view.Tcw = Tcw; } return *this; }     // F.mTcw or pKF->GetPose()
+    ViewGather& add_pose(const cv::Mat& R, const cv::Mat& t) {                      // [R | t] of GetRotation() / GetTranslation()
+        rt_to_array(R, t, Tcw, 4, Tcw + 3, 4);
+        Tcw[12] = Tcw[13] = Tcw[14] = 0.f; Tcw[15] = 1.f; view.Tcw = Tcw;
+        return *this;
+    }
+    template <class T> ViewGather& add_bounds(const T& o) { view.min_x = o.mnMinX; view.max_x = o.mnMaxX; view.min_y = o.mnMinY; view.max_y = o.mnMaxY; return *this; }
+    template <class T> ViewGather& add_grid(const T& o) { view.grid_w_inv = o.mfGridElementWidthInv; view.grid_h_inv = o.mfGridElementHeightInv; return *this; }
+    template <class T> ViewGather& add_intrinsics(const T& o) { view.fx = o.fx; view.fy = o.fy; view.cx = o.cx; view.cy = o.cy; return *this; }
+    template <class T> ViewGather& add_stereo(const T& o) { view.bf = o.mbf; view.b = o.mb; return *this; }
+    ViewGather& add_intrinsics_K(const cv::Mat& K) { view.fx = K.at<float>(0, 0); view.fy = K.at<float>(1, 1); view.cx = K.at<float>(0, 2); view.cy = K.at<float>(1, 2); return *this; }
+    ViewGather& add_scales(const std::vector<float>& v, bool ones_first) {          // mvScaleFactors; the two solvers fill all levels with 1.f first
+        if (ones_first) std::fill_n(view.scale_factors, (int)PLANAR_MAX_LEVELS, 1.f);
+        copy_scale_factors(view.scale_factors, v);
+        return *this;
+    }
+};
+
+// ---- a list of map points as the arrays of the entries, by parts.  add_points: `count` slots (padded to max(count, 1)), usable = v[j] != NULL && !isBad() &&
+//      !excluded(v[j]), xw of the usable; a slot past the end of v counts as NULL.  The other parts fill their array for the usable points and leave zeros elsewhere;
+//      kp names only the arrays that were added.  A copy points into its own storage. ----
+struct NoExclusion { template <class P> bool operator()(P*) const { return false; } };
+struct PointGather {
+    std::vector<uint8_t> usable, desc;
+    std::vector<float> xw, nrm, mn, mx;
+    planar_kf_points kp;
+
+    PointGather() { std::memset(&kp, 0, sizeof(kp)); }
+    PointGather(const PointGather& o) { *this = o; }
+    PointGather& operator=(const PointGather& o) { usable = o.usable; desc = o.desc; xw = o.xw; nrm = o.nrm; mn = o.mn; mx = o.mx; return bind(); }
+    PointGather& bind() {
+        kp.usable = usable.empty() ? nullptr : usable.data(); kp.xw = xw.empty() ? nullptr : xw.data(); kp.desc = desc.empty() ? nullptr : desc.data();
+        kp.min_dist = mn.empty() ? nullptr : mn.data(); kp.max_dist = mx.empty() ? nullptr : mx.data();
+        return *this;
+    }
+    template <class MapPointT, class Excluded> PointGather& add_points(const std::vector<MapPointT*>& v, size_t count, Excluded excluded) {
+        usable.assign(count ? count : 1, 0); xw.assign(usable.size() * 3, 0.f);
+        for (size_t j = 0; j < count && j < v.size(); j++) {
+            MapPointT* p = v[j];
+            if (!p || p->isBad() || excluded(p)) continue;
+            usable[j] = 1;
+            vec3_to_array(p->GetWorldPos(), &xw[3 * j]);
+        }
+        return bind();
+    }
+    template <class MapPointT> PointGather& add_points(const std::vector<MapPointT*>& v) { return add_points(v, v.size(), NoExclusion()); }
+    template <class MapPointT> PointGather& add_normals(const std::vector<MapPointT*>& v) {      // GetNormal()
+        nrm.assign(usable.size() * 3, 0.f);
+        for (size_t j = 0; j < v.size() && j < usable.size(); j++) if (usable[j]) vec3_to_array(v[j]->GetNormal(), &nrm[3 * j]);
+        return *this;
+    }
+    template <class MapPointT> PointGather& add_desc(const std::vector<MapPointT*>& v) {         // GetDescriptor()
+        desc.assign(usable.size() * 32, 0);
+        for (size_t j = 0; j < v.size() && j < usable.size(); j++) if (usable[j]) copy_desc_rows(&desc[j * 32], v[j]->GetDescriptor(), 1);
+        return bind();
+    }
+    template <class MapPointT> PointGather& add_range(const std::vector<MapPointT*>& v) {        // GetDistanceRange(): the unscaled mfMinDistance / mfMaxDistance
+        mn.assign(usable.size(), 0.f); mx.assign(usable.size(), 0.f);
+        for (size_t j = 0; j < v.size() && j < usable.size(); j++) if (usable[j]) v[j]->GetDistanceRange(mn[j], mx[j]);
+        return bind();
+    }
+};
+
+// ---- smaller pieces ----
+// the camera of CreateNewMapPoints / CreateNewMapLines, off the current key frame
+template <class KeyFrameT> inline planar_tri_camera tri_camera(KeyFrameT* pKF) {
+    planar_tri_camera cam;
+    std::memset(&cam, 0, sizeof(cam));
+    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.invfx = pKF->invfx; cam.invfy = pKF->invfy; cam.scale_factor = pKF->mfScaleFactor;
+    cam.n_levels = (int32_t)pKF->mvScaleFactors.size();
+    copy_scale_factors(cam.scale_factors, pKF->mvScaleFactors);
+    copy_scale_factors(cam.level_sigma2, pKF->mvLevelSigma2);
+    return cam;
+}
+
+// the intrinsics and the six Plane.* values Config::Get<double> returns (ConfigT = Planar_SLAM::Config)
+template <class ConfigT> inline planar_pose_params plane_pose_params(float fx, float fy, float cx, float cy, float bf) {
+    planar_pose_params prm;
+    prm.fx = fx; prm.fy = fy; prm.cx = cx; prm.cy = cy; prm.bf = bf;
+    prm.angle_info = ConfigT::template Get<double>("Plane.AngleInfo"); prm.distance_info = ConfigT::template Get<double>("Plane.DistanceInfo");
+    prm.parallel_info = ConfigT::template Get<double>("Plane.ParallelInfo"); prm.vertical_info = ConfigT::template Get<double>("Plane.VerticalInfo");
+    prm.plane_chi = ConfigT::template Get<double>("Plane.Chi"); prm.vp_chi = ConfigT::template Get<double>("Plane.VPChi");
+    return prm;
+}
+
+// vpMatches (of pKF1's features) as the entry's match array over `stride1` slots: -1 = NULL, i2 = GetIndexInKeyFrame(pKF2) where that is a feature of pKF2 and the
+// matched point is not bad, NOT_IN_KF2 otherwise.  usable2 describes pKF2's own slot, so a match makes slot i2 of `side2` usable with the matched point's position.
+template <class KeyFrameT, class MapPointT>
+inline std::vector<int32_t> sim3_entry_matches(const std::vector<MapPointT*>& vpMatches, int n1, size_t stride1, KeyFrameT* pKF2, int n2, PointGather& side2) {
+    std::vector<int32_t> match(stride1, -1);
+    const int N = (int)vpMatches.size() < n1 ? (int)vpMatches.size() : n1;
+    for (int i = 0; i < N; i++) {
+        if (!vpMatches[i]) continue;
+        const int i2 = vpMatches[i]->GetIndexInKeyFrame(pKF2);
+        match[i] = (i2 >= 0 && i2 < n2 && !vpMatches[i]->isBad()) ? i2 : NOT_IN_KF2;
+        if (match[i] >= 0) { side2.usable[i2] = 1; vec3_to_array(vpMatches[i]->GetWorldPos(), &side2.xw[3 * i2]); }
+    }
+    return match;
+}
+
+// the map edits of the two Fuse functions (src/ORBmatcher.cc:953-974, src/LSDmatcher.cpp:993-1010) on the reference's own objects: landmark j found feature idx[j];
+// in_kf(i) is GetMapPoint / GetMapLine, add_to_kf(p, i) is AddMapPoint / AddMapLine
+template <class KeyFrameT, class LandmarkT, class InKF, class AddToKF>
+inline void apply_fuse_edits(KeyFrameT* pKF, const std::vector<LandmarkT*>& v, const std::vector<int32_t>& idx, InKF in_kf, AddToKF add_to_kf) {
+    for (size_t j = 0; j < v.size(); j++) {
+        if (idx[j] < 0) continue;
+        LandmarkT* p = v[j];
+        LandmarkT* held = in_kf(idx[j]);
+        if (held) {
+            if (!held->isBad()) {
+                if (held->Observations() > p->Observations()) p->Replace(held);
+                else held->Replace(p);
+            }
+        } else {
+            p->AddObservation(pKF, idx[j]);
+            add_to_kf(p, idx[j]);
+        }
+    }
+}
+
 }  // namespace planar_adapter
 
 namespace Planar_SLAM {
@@ -138,31 +332,30 @@ public:
         if (_image.empty()) return;
         cv::Mat image = _image.getMat();
         assert(image.type() == CV_8UC1);   // src/ORBextractor.cc:1050
-        planar_adapter::Runtime& R = planar_adapter::Runtime::get();
-        planar_adapter::Runtime::Lane& L = R.lane(planar_adapter::POINTS);
-        std::lock_guard<std::mutex> g(L.mu);
-        planar_orb* orb = R.orb(params(), image.cols, image.rows);
-        if (!orb) { _keypoints.clear(); _descriptors.release(); return; }
-        const int cap = planar_orb_max_keypoints(orb);
-        std::vector<planar_keypoint> kps(cap);
-        std::vector<uint8_t> desc((size_t)cap * 32);
+        std::vector<planar_keypoint> kps;
+        std::vector<uint8_t> desc;
         int32_t n = 0;
-        if (!planar_adapter::ok(planar_orb_extract(orb, image.data, 1, (int)image.step, (int64_t)image.step * image.rows, kps.data(), desc.data(), &n), "ORBextractor")) n = 0;
-        static_assert(sizeof(cv::KeyPoint) == sizeof(planar_keypoint), "cv::KeyPoint layout");
+        const bool done = planar_adapter::on_lane(planar_adapter::POINTS, "ORBextractor", [&](planar_ctx*) -> int {
+            planar_orb* orb = planar_adapter::Runtime::get().orb(params(), image.cols, image.rows);
+            if (!orb) return PLANAR_OK;            // (said at create: no key points, the pyramid left alone)
+            const int cap = planar_orb_max_keypoints(orb);
+            kps.resize(cap); desc.resize((size_t)cap * 32);
+            const int rc = planar_orb_extract(orb, image.data, 1, (int)image.step, (int64_t)image.step * image.rows, kps.data(), desc.data(), &n);
+            for (int l = 0; l < nlevels; l++) {      // public member of the reference class (include/ORBextractor.h:85)
+                int w, h;
+                planar_orb_level_size(orb, l, &w, &h);
+                mvImagePyramid[l].create(h, w, CV_8UC1);
+                planar_orb_read_level(orb, 0, l, mvImagePyramid[l].data);
+            }
+            return rc;
+        });
+        if (!done) n = 0;
         _keypoints.resize(n);
-        if (n) std::memcpy((void*)_keypoints.data(), kps.data(), (size_t)n * sizeof(planar_keypoint));
-        if (n == 0) { _descriptors.release(); }
-        else {
-            _descriptors.create(n, 32, CV_8U);
-            cv::Mat d = _descriptors.getMat();
-            for (int i = 0; i < n; i++) std::memcpy(d.ptr(i), &desc[(size_t)i * 32], 32);
-        }
-        for (int l = 0; l < nlevels; l++) {      // public member of the reference class (include/ORBextractor.h:85)
-            int w, h;
-            planar_orb_level_size(orb, l, &w, &h);
-            mvImagePyramid[l].create(h, w, CV_8UC1);
-            planar_orb_read_level(orb, 0, l, mvImagePyramid[l].data);
-        }
+        planar_adapter::copy_keypoints((void*)_keypoints.data(), kps.data(), n);
+        if (n == 0) { _descriptors.release(); return; }
+        _descriptors.create(n, 32, CV_8U);
+        cv::Mat d = _descriptors.getMat();
+        for (int i = 0; i < n; i++) std::memcpy(d.ptr(i), &desc[(size_t)i * 32], 32);
     }
 
     int GetLevels() { return nlevels; }
@@ -178,13 +371,12 @@ protected:
     planar_orb_params params() const { return planar_orb_params{nfeatures, (float)scaleFactor, nlevels, iniThFAST, minThFAST}; }
     std::vector<float> factors(int which) {
         // the scale tables depend only on the constructor arguments; any cached plan with these parameters can answer
-        planar_adapter::Runtime& R = planar_adapter::Runtime::get();
-        planar_adapter::Runtime::Lane& L = R.lane(planar_adapter::POINTS);
-        std::lock_guard<std::mutex> g(L.mu);
-        planar_orb* orb = R.orb(params(), 640, 480);
         std::vector<float> v[4];
         for (auto& x : v) x.resize(nlevels);
-        planar_orb_get_scale_factors(orb, v[0].data(), v[1].data(), v[2].data(), v[3].data());
+        planar_adapter::on_lane(planar_adapter::POINTS, "ORBextractor", [&](planar_ctx*) -> int {
+            planar_orb_get_scale_factors(planar_adapter::Runtime::get().orb(params(), 640, 480), v[0].data(), v[1].data(), v[2].data(), v[3].data());
+            return PLANAR_OK;
+        });
         return v[which];
     }
     int nfeatures; double scaleFactor; int nlevels, iniThFAST, minThFAST;
@@ -240,15 +432,12 @@ public:
         labels.assign((size_t)W * H, -1);
         planes.assign((size_t)planar_peac_max_planes() * 8, 0.0);
         int32_t n = 0;
-        {
-            planar_adapter::Runtime& R = planar_adapter::Runtime::get();
-            planar_adapter::Runtime::Lane& L = R.lane(planar_adapter::PLANES);
-            std::lock_guard<std::mutex> g(L.mu);
-            planar_peac* pp = R.peac(W, H);
-            if (!pp) { n = 0; labels.assign((size_t)W * H, -1); }          // (unsupported frame size: said once, at create)
-            else if (!planar_adapter::ok(planar_peac_segment(pp, (const uint16_t*)depth_.data, 1, (int)(depth_.step / 2), (int64_t)(depth_.step / 2) * H, fx_, fy_, cx_, cy_,
-                                                        factor_, labels.data(), planes.data(), &n), "PlaneDetection")) { n = 0; labels.assign((size_t)W * H, -1); }
-        }
+        if (!planar_adapter::on_lane(planar_adapter::PLANES, "PlaneDetection", [&](planar_ctx*) -> int {
+                planar_peac* pp = planar_adapter::Runtime::get().peac(W, H);
+                if (!pp) return PLANAR_OK;                                     // (unsupported frame size: said once, at create; no planes)
+                return planar_peac_segment(pp, (const uint16_t*)depth_.data, 1, (int)(depth_.step / 2), (int64_t)(depth_.step / 2) * H, fx_, fy_, cx_, cy_, factor_,
+                                           labels.data(), planes.data(), &n);
+            })) { n = 0; labels.assign((size_t)W * H, -1); }
         plane_num_ = n;
         plane_vertices_.assign(n, std::vector<int>());
         for (size_t i = 0; i < labels.size(); i++) if (labels[i] >= 0) plane_vertices_[labels[i]].push_back((int)i);   // raster order, as :362-372
@@ -281,43 +470,43 @@ public:
             for (int t = 0; t < 4; t++) m.at<float>(t, 0) = cf[(size_t)k * 4 + t];
             planeCoefficients.push_back(m);
         };
-        {
-            planar_adapter::Runtime& R = planar_adapter::Runtime::get();
-            planar_adapter::Runtime::Lane& L = R.lane(planar_adapter::PLANES);
-            std::lock_guard<std::mutex> g(L.mu);
-            if (!R.clouds(W, H)) return 0;                                   // (unsupported frame size: said once, at create)
-            const int rc = planar_plane_clouds_compute(R.clouds(W, H), (const uint16_t*)depth_.data, 1, (int)(depth_.step / 2), (int64_t)(depth_.step / 2) * H, fx_, fy_,
-                                                       cx_, cy_, factor_, labels_.data(), planes_.data(), &n_in, disTh, leaf, &n_out, coef.data(), src.data(), off.data(),
-                                                       pts.data(), nullptr, nullptr, nullptr);
-            int32_t fst = 0;                                                  // the frame's result code (3 = more voxels than the table holds), not the message's text
-            if (rc == PLANAR_ECAPACITY) planar_plane_clouds_last_status(R.clouds(W, H), 1, &fst);
-            if (rc == PLANAR_ECAPACITY && fst == 3) {
-                // pcl::VoxelGrid has no voxel cap (src/Frame.cc:674-679); the frame's voxel table here has (8192 for all planes together).  The frame goes through once
-                // more PLANE BY PLANE (planar_plane_clouds_set_plane_window), results appended in plane order - the very sequence of Frame::ComputePlanes' loop, every
-                // plane's cloud and refit what the one-pass call would have produced.  Only a single plane of more than 8192 voxels (> 80 m^2 at the 0.1 m leaf) is
-                // beyond the structure: it alone is dropped, with a message (this runs on the thread Frame's constructor spawned: no exception may leave it).
-                planar_plane_clouds* pc = R.clouds(W, H);
-                int total = 0;
-                for (int i = 0; i < n_in; i++) {
-                    int32_t n1 = 0;
-                    planar_plane_clouds_set_plane_window(pc, i, 1);
-                    const int rc1 = planar_plane_clouds_compute(pc, (const uint16_t*)depth_.data, 1, (int)(depth_.step / 2), (int64_t)(depth_.step / 2) * H, fx_, fy_, cx_, cy_, factor_,
-                                                                labels_.data(), planes_.data(), &n_in, disTh, leaf, &n1, coef.data(), src.data(), off.data(), pts.data(), nullptr,
-                                                                nullptr, nullptr);
-                    int32_t pst = 0;
-                    if (rc1 == PLANAR_ECAPACITY) planar_plane_clouds_last_status(pc, 1, &pst);
-                    if (rc1 == PLANAR_ECAPACITY && pst == 3) {
-                        std::fprintf(stderr, "planar: plane %d of this frame alone has more than %d voxels: dropped (%s)\n", i, MP, planar_last_error());
-                        continue;
-                    }
-                    if (!planar_adapter::ok(rc1, "ComputePlaneClouds (plane by plane)")) { total = 0; planePoints.clear(); planeCoefficients.clear(); break; }
-                    if (n1 == 1) { append(0, coef.data(), off.data(), pts.data()); total++; }
+        int total = -1;                                                       // >= 0: the frame went through plane by plane, this many were kept
+        const bool done = planar_adapter::on_lane(planar_adapter::PLANES, "ComputePlaneClouds", [&](planar_ctx*) -> int {
+            planar_plane_clouds* pc = planar_adapter::Runtime::get().clouds(W, H);
+            if (!pc) { total = 0; return PLANAR_OK; }                         // (unsupported frame size: said once, at create)
+            // one call; *st = the frame's result code where the table was too small (3 = more voxels than it holds), not the message's text
+            auto compute = [&](int32_t* n_kept, int32_t* st) {
+                const int rc = planar_plane_clouds_compute(pc, (const uint16_t*)depth_.data, 1, (int)(depth_.step / 2), (int64_t)(depth_.step / 2) * H, fx_, fy_, cx_, cy_,
+                                                           factor_, labels_.data(), planes_.data(), &n_in, disTh, leaf, n_kept, coef.data(), src.data(), off.data(),
+                                                           pts.data(), nullptr, nullptr, nullptr);
+                *st = 0;
+                if (rc == PLANAR_ECAPACITY) planar_plane_clouds_last_status(pc, 1, st);
+                return rc;
+            };
+            int32_t fst = 0;
+            const int rc = compute(&n_out, &fst);
+            if (!(rc == PLANAR_ECAPACITY && fst == 3)) return rc;
+            // pcl::VoxelGrid has no voxel cap (src/Frame.cc:674-679); the frame's voxel table here has (8192 for all planes together).  The frame goes through once
+            // more PLANE BY PLANE (planar_plane_clouds_set_plane_window), results appended in plane order - the very sequence of Frame::ComputePlanes' loop, every
+            // plane's cloud and refit what the one-pass call would have produced.  Only a single plane of more than 8192 voxels (> 80 m^2 at the 0.1 m leaf) is
+            // beyond the structure: it alone is dropped, with a message (this runs on the thread Frame's constructor spawned: no exception may leave it).
+            total = 0;
+            for (int i = 0; i < n_in; i++) {
+                int32_t n1 = 0, pst = 0;
+                planar_plane_clouds_set_plane_window(pc, i, 1);
+                const int rc1 = compute(&n1, &pst);
+                if (rc1 == PLANAR_ECAPACITY && pst == 3) {
+                    std::fprintf(stderr, "planar: plane %d of this frame alone has more than %d voxels: dropped (%s)\n", i, MP, planar_last_error());
+                    continue;
                 }
-                planar_plane_clouds_set_plane_window(pc, 0, -1);
-                return total;
+                if (!planar_adapter::ok(rc1, "ComputePlaneClouds (plane by plane)")) { total = 0; planePoints.clear(); planeCoefficients.clear(); break; }
+                if (n1 == 1) { append(0, coef.data(), off.data(), pts.data()); total++; }
             }
-            if (!planar_adapter::ok(rc, "ComputePlaneClouds")) return 0;
-        }
+            planar_plane_clouds_set_plane_window(pc, 0, -1);
+            return PLANAR_OK;
+        });
+        if (!done) return 0;
+        if (total >= 0) return total;
         for (int k = 0; k < n_out; k++) append(k, coef.data(), off.data(), pts.data());
         return n_out;
     }
@@ -351,13 +540,10 @@ public:
         const size_t first = keylineFunctions.size();                  // the reference push_backs
         keylineFunctions.resize(first + lsdNFeatures);
         int32_t n = 0;
-        {
-            planar_adapter::Runtime& R = planar_adapter::Runtime::get();
-            planar_adapter::Runtime::Lane& L = R.lane(planar_adapter::LINES);
-            std::lock_guard<std::mutex> g(L.mu);
-            if (!planar_adapter::ok(planar_lsd_extract(R.lsd(W, H), img.data, 1, (int)img.step, (int64_t)img.step * H, lsdNFeatures, (planar_keyline*)keylines.data(), desc.data(),
-                                                       (double*)(keylineFunctions.data() + first), &n), "LineSegment")) n = 0;
-        }
+        if (!planar_adapter::on_lane(planar_adapter::LINES, "LineSegment", [&](planar_ctx*) {
+                return planar_lsd_extract(planar_adapter::Runtime::get().lsd(W, H), img.data, 1, (int)img.step, (int64_t)img.step * H, lsdNFeatures,
+                                          (planar_keyline*)keylines.data(), desc.data(), (double*)(keylineFunctions.data() + first), &n);
+            })) n = 0;
         keylines.resize(n);
         keylineFunctions.resize(first + n);
         if (n) { ldesc = cv::Mat(n, 32, CV_8UC1); std::memcpy(ldesc.data, desc.data(), (size_t)n * 32); }   // BinaryDescriptor::compute leaves ldesc untouched when there are no lines
@@ -370,34 +556,14 @@ public:
 #ifdef PLANAR_ADAPTERS_WITH_TRACKING
 namespace planar_adapter {
 
-// Frame fields of the guided matchers -> planar_frame_view (the vectors keep the storage alive)
-struct FrameGather {
-    int32_t n;
-    std::vector<planar_keypoint> keys;
-    std::vector<float> ur;
-    std::vector<uint8_t> desc, blocked;
-    float Tcw[16];
-    planar_frame_view view;
-    template <class FrameT> explicit FrameGather(FrameT& F, bool want_blocked) {
-        n = F.N;
-        keys.resize(n > 0 ? n : 1); ur.resize(keys.size()); desc.resize(keys.size() * 32); blocked.assign(keys.size(), 0);
-        for (int i = 0; i < n; i++) {
-            std::memcpy(&keys[i], &F.mvKeysUn[i], sizeof(planar_keypoint));
-            ur[i] = F.mvuRight.empty() ? -1.f : F.mvuRight[i];
-            std::memcpy(&desc[(size_t)i * 32], F.mDescriptors.ptr(i), 32);
-            if (want_blocked && F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) blocked[i] = 1;
-        }
-        std::memset(&view, 0, sizeof(view));
-        view.B = 1; view.stride = (int32_t)keys.size(); view.n = &n; view.keys_un = keys.data(); view.u_right = ur.data(); view.desc = desc.data();
-        view.blocked = want_blocked ? blocked.data() : nullptr;
-        if (!F.mTcw.empty()) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = F.mTcw.template at<float>(r, c); view.Tcw = Tcw; }
-        view.min_x = FrameT::mnMinX; view.max_x = FrameT::mnMaxX; view.min_y = FrameT::mnMinY; view.max_y = FrameT::mnMaxY;
-        view.grid_w_inv = FrameT::mfGridElementWidthInv; view.grid_h_inv = FrameT::mfGridElementHeightInv;
-        view.fx = FrameT::fx; view.fy = FrameT::fy; view.cx = FrameT::cx; view.cy = FrameT::cy; view.bf = F.mbf; view.b = F.mb;
-        for (size_t l = 0; l < F.mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = F.mvScaleFactors[l];
-    }
-};
-inline Runtime::Lane& tracking_lane() { return Runtime::get().lane(TRACKING); }
+// a Frame as the guided matchers read it: every part, the pose from F.mTcw (where it is set), blocked = the feature holds an observed map point.
+// (For a KeyFrame compose the parts yourself, with add_pose(pKF->GetPose()): ORBmatcher::Fuse below does.)
+template <class FrameT> inline ViewGather frame_view(FrameT& F) {
+    ViewGather g;
+    g.add_keys(F.mvKeysUn, F.N).add_u_right(F.mvuRight).add_desc(F.mDescriptors).add_blocked_observed(F.mvpMapPoints).add_pose(F.mTcw);
+    g.add_bounds(F).add_grid(F).add_intrinsics(F).add_stereo(F).add_scales(F.mvScaleFactors, false);
+    return g;
+}
 
 }  // namespace planar_adapter
 
@@ -405,36 +571,33 @@ namespace Planar_SLAM {
 
 // ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)  (src/ORBmatcher.cc:1396-1535)
 inline int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono) {
-    planar_adapter::FrameGather cur(CurrentFrame, true);
+    using namespace planar_adapter;
+    const ViewGather cur = frame_view(CurrentFrame);
     const int NL = LastFrame.N;
     int32_t nl = NL;
     std::vector<uint8_t> usable(NL > 0 ? NL : 1, 0), observed(usable.size(), 0), mpd(usable.size() * 32, 0);
     std::vector<float> xw(usable.size() * 3, 0.f), ang(usable.size(), 0.f);
     std::vector<int32_t> oct(usable.size(), 0);
     float Tl[16];
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tl[4 * r + c] = LastFrame.mTcw.at<float>(r, c);
+    mat_to_array(LastFrame.mTcw, Tl);
     for (int i = 0; i < NL; i++) {
         MapPoint* pMP = LastFrame.mvpMapPoints[i];
         oct[i] = LastFrame.mvKeys[i].octave; ang[i] = LastFrame.mvKeysUn[i].angle;
         if (pMP && !LastFrame.mvbOutlier[i]) {
             usable[i] = 1;
-            cv::Mat x = pMP->GetWorldPos(), d = pMP->GetDescriptor();
-            for (int k = 0; k < 3; k++) xw[3 * i + k] = x.at<float>(k);
-            std::memcpy(&mpd[(size_t)i * 32], d.ptr(0), 32);
+            vec3_to_array(pMP->GetWorldPos(), &xw[3 * i]);
+            copy_desc_rows(&mpd[(size_t)i * 32], pMP->GetDescriptor(), 1);
             observed[i] = pMP->Observations() > 0;
         }
     }
     planar_last_frame_view last;
     last.stride = (int32_t)usable.size(); last.n = &nl; last.Tcw = Tl; last.usable = usable.data(); last.xw = xw.data(); last.octave = oct.data(); last.angle = ang.data();
     last.mp_desc = mpd.data(); last.mp_observed = observed.data();
-    const int32_t UNTOUCHED = -2;
     std::vector<int32_t> match(cur.keys.size(), UNTOUCHED);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_search_by_projection_frame(L.ctx, &cur.view, &last, th, bMono ? 1 : 0, mbCheckOrientation ? 1 : 0, match.data(), &nmatches), "planar_search_by_projection_frame")) return 0;
-    }
+    if (!on_lane(TRACKING, "planar_search_by_projection_frame", [&](planar_ctx* ctx) {
+            return planar_search_by_projection_frame(ctx, &cur.view, &last, th, bMono ? 1 : 0, mbCheckOrientation ? 1 : 0, match.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < CurrentFrame.N; i++) {
         if (match[i] == UNTOUCHED) continue;
         CurrentFrame.mvpMapPoints[i] = match[i] >= 0 ? LastFrame.mvpMapPoints[match[i]] : static_cast<MapPoint*>(NULL);
@@ -444,7 +607,8 @@ inline int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& Last
 
 // ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th)  (src/ORBmatcher.cc:46-130)
 inline int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>& vpMapPoints, const float th) {
-    planar_adapter::FrameGather fr(F, true);
+    using namespace planar_adapter;
+    const ViewGather fr = frame_view(F);
     const size_t M = vpMapPoints.size();
     int32_t nm = (int32_t)M;
     std::vector<uint8_t> inview(M ? M : 1, 0), obs(inview.size(), 0), desc(inview.size() * 32, 0);
@@ -454,43 +618,37 @@ inline int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>
         MapPoint* p = vpMapPoints[j];
         if (!p->mbTrackInView || p->isBad()) continue;
         inview[j] = 1; px[j] = p->mTrackProjX; py[j] = p->mTrackProjY; pxr[j] = p->mTrackProjXR; lvl[j] = p->mnTrackScaleLevel; vc[j] = p->mTrackViewCos;
-        cv::Mat d = p->GetDescriptor();
-        std::memcpy(&desc[j * 32], d.ptr(0), 32);
+        copy_desc_rows(&desc[j * 32], p->GetDescriptor(), 1);
         obs[j] = p->Observations() > 0;
     }
     planar_map_probes pr;
     pr.stride = (int32_t)inview.size(); pr.n = &nm; pr.in_view = inview.data(); pr.proj_x = px.data(); pr.proj_y = py.data(); pr.proj_xr = pxr.data(); pr.level = lvl.data();
     pr.view_cos = vc.data(); pr.desc = desc.data(); pr.observed = obs.data();
-    const int32_t UNTOUCHED = -2;
     std::vector<int32_t> match(fr.keys.size(), UNTOUCHED);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_search_by_projection_map(L.ctx, &fr.view, &pr, th, mfNNratio, match.data(), &nmatches), "planar_search_by_projection_map")) return 0;
-    }
+    if (!on_lane(TRACKING, "planar_search_by_projection_map", [&](planar_ctx* ctx) {
+            return planar_search_by_projection_map(ctx, &fr.view, &pr, th, mfNNratio, match.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < F.N; i++) if (match[i] >= 0) F.mvpMapPoints[i] = vpMapPoints[match[i]];
     return nmatches;
 }
 
 // ORBmatcher::MatchORBPoints(Frame&, const Frame&)  (src/ORBmatcher.cc:1332-1394)
 inline int ORBmatcher::MatchORBPoints(Frame& CurrentFrame, const Frame& LastFrame) {
+    using namespace planar_adapter;
     int32_t nc = CurrentFrame.N, nl = LastFrame.N;
     std::vector<uint8_t> cd((size_t)(nc > 0 ? nc : 1) * 32), ld((size_t)(nl > 0 ? nl : 1) * 32), has(nl > 0 ? nl : 1, 0), outl(has.size(), 0);
-    for (int i = 0; i < nc; i++) std::memcpy(&cd[(size_t)i * 32], CurrentFrame.mDescriptors.ptr(i), 32);
+    copy_desc_rows(cd.data(), CurrentFrame.mDescriptors, nc);
+    copy_desc_rows(ld.data(), LastFrame.mDescriptors, nl);
     for (int j = 0; j < nl; j++) {
-        std::memcpy(&ld[(size_t)j * 32], LastFrame.mDescriptors.ptr(j), 32);
         has[j] = LastFrame.mvpMapPoints[j] != NULL;
         outl[j] = (size_t)j < LastFrame.mvbOutlier.size() && LastFrame.mvbOutlier[j];
     }
-    const int32_t UNTOUCHED = -2;
     std::vector<int32_t> match(nc > 0 ? nc : 1, UNTOUCHED);
     int32_t npair = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_match_orb_points(L.ctx, cd.data(), &nc, nc > 0 ? nc : 1, ld.data(), &nl, nl > 0 ? nl : 1, has.data(), outl.data(), 1, match.data(), &npair), "planar_match_orb_points")) return 0;
-    }
+    if (!on_lane(TRACKING, "planar_match_orb_points", [&](planar_ctx* ctx) {
+            return planar_match_orb_points(ctx, cd.data(), &nc, nc > 0 ? nc : 1, ld.data(), &nl, nl > 0 ? nl : 1, has.data(), outl.data(), 1, match.data(), &npair);
+        })) return 0;
     for (int i = 0; i < nc; i++) if (match[i] >= 0) CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[match[i]];
     return npair;
 }
@@ -507,20 +665,16 @@ inline int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint
     for (const auto& kv : F.mFeatVec) for (unsigned int i : kv.second) if ((int)i < nf) fnode[i] = (int32_t)kv.first;
     std::vector<uint8_t> kus(nk, 0), kd((size_t)nk * 32), fd((size_t)nf * 32);
     std::vector<float> kang(nk), fang(nf);
-    for (int i = 0; i < nk; i++) {
-        kus[i] = vpMapPointsKF[i] && !vpMapPointsKF[i]->isBad();
-        kang[i] = pKF->mvKeysUn[i].angle;
-        std::memcpy(&kd[(size_t)i * 32], pKF->mDescriptors.ptr(i), 32);
-    }
-    for (int i = 0; i < nf; i++) { fang[i] = F.mvKeys[i].angle; std::memcpy(&fd[(size_t)i * 32], F.mDescriptors.ptr(i), 32); }
+    for (int i = 0; i < nk; i++) { kus[i] = vpMapPointsKF[i] && !vpMapPointsKF[i]->isBad(); kang[i] = pKF->mvKeysUn[i].angle; }
+    for (int i = 0; i < nf; i++) fang[i] = F.mvKeys[i].angle;
+    planar_adapter::copy_desc_rows(kd.data(), pKF->mDescriptors, nk);
+    planar_adapter::copy_desc_rows(fd.data(), F.mDescriptors, nf);
     std::vector<int32_t> match(nf, -1);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_search_by_bow(L.ctx, 1, &nk, nk, knode.data(), kus.data(), kang.data(), kd.data(), &nf, nf, fnode.data(), fang.data(), fd.data(), mfNNratio,
-                                                   mbCheckOrientation ? 1 : 0, match.data(), &nmatches), "planar_search_by_bow")) return 0;
-    }
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_search_by_bow", [&](planar_ctx* ctx) {
+            return planar_search_by_bow(ctx, 1, &nk, nk, knode.data(), kus.data(), kang.data(), kd.data(), &nf, nf, fnode.data(), fang.data(), fd.data(), mfNNratio,
+                                        mbCheckOrientation ? 1 : 0, match.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < nf; i++) if (match[i] >= 0) vpMapPointMatches[i] = vpMapPointsKF[match[i]];
     return nmatches;
 }
@@ -532,15 +686,14 @@ inline int LSDmatcher::SearchByDescriptor(KeyFrame* pKF, Frame& currentF, std::v
     vpMapLineMatches = std::vector<MapLine*>(currentF.NL, static_cast<MapLine*>(NULL));
     if (nk == 0 || nc == 0) return 0;
     std::vector<uint8_t> kd((size_t)nk * 32), cd((size_t)nc * 32), has(nk, 0);
-    for (int i = 0; i < nk; i++) { std::memcpy(&kd[(size_t)i * 32], pKF->mLineDescriptors.ptr(i), 32); has[i] = vpMapLinesKF[i] != NULL; }
-    for (int i = 0; i < nc; i++) std::memcpy(&cd[(size_t)i * 32], currentF.mLdesc.ptr(i), 32);
+    planar_adapter::copy_desc_rows(kd.data(), pKF->mLineDescriptors, nk);
+    planar_adapter::copy_desc_rows(cd.data(), currentF.mLdesc, nc);
+    for (int i = 0; i < nk; i++) has[i] = vpMapLinesKF[i] != NULL;
     std::vector<int32_t> match(nc, -1);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_lsd_search_by_descriptor(L.ctx, kd.data(), &nk, nk, cd.data(), &nc, nc, has.data(), 1, match.data(), &nmatches), "planar_lsd_search_by_descriptor")) return 0;
-    }
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_lsd_search_by_descriptor", [&](planar_ctx* ctx) {
+            return planar_lsd_search_by_descriptor(ctx, kd.data(), &nk, nk, cd.data(), &nc, nc, has.data(), 1, match.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < nc && i < currentF.NL; i++) if (match[i] >= 0) vpMapLineMatches[i] = vpMapLinesKF[match[i]];
     return nmatches;
 }
@@ -553,26 +706,23 @@ inline int LSDmatcher::SearchByProjection(Frame& F, const std::vector<MapLine*>&
     std::vector<uint8_t> ldesc((size_t)nl * 32), blocked(nl, 0), inview(nm, 0), obs(nm, 0), mdesc((size_t)nm * 32, 0);
     std::vector<float> proj((size_t)nm * 4, 0.f), vc(nm, 0.f);
     std::vector<int32_t> lvl(nm, 0);
-    for (int i = 0; i < nl; i++) { std::memcpy(&ldesc[(size_t)i * 32], F.mLdesc.ptr(i), 32); blocked[i] = F.mvpMapLines[i] && F.mvpMapLines[i]->Observations() > 0; }
+    planar_adapter::copy_desc_rows(ldesc.data(), F.mLdesc, nl);
+    for (int i = 0; i < nl; i++) blocked[i] = F.mvpMapLines[i] && F.mvpMapLines[i]->Observations() > 0;
     for (int j = 0; j < nm; j++) {
         MapLine* p = vpMapLines[j];
         if (!p || p->isBad() || !p->mbTrackInView) continue;
         inview[j] = 1; proj[4 * j] = p->mTrackProjX1; proj[4 * j + 1] = p->mTrackProjY1; proj[4 * j + 2] = p->mTrackProjX2; proj[4 * j + 3] = p->mTrackProjY2;
         lvl[j] = p->mnTrackScaleLevel; vc[j] = p->mTrackViewCos;
-        cv::Mat d = p->GetDescriptor();
-        std::memcpy(&mdesc[(size_t)j * 32], d.ptr(0), 32);
+        planar_adapter::copy_desc_rows(&mdesc[(size_t)j * 32], p->GetDescriptor(), 1);
         obs[j] = p->Observations() > 0;
     }
-    const int32_t UNTOUCHED = -2;
-    std::vector<int32_t> match(nl, UNTOUCHED);
+    std::vector<int32_t> match(nl, planar_adapter::UNTOUCHED);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_lsd_search_by_projection(L.ctx, 1, &nl, nl, (const planar_keyline*)F.mvKeylinesUn.data(), ldesc.data(), blocked.data(), &nm, nm, inview.data(),
-                                                              proj.data(), lvl.data(), vc.data(), mdesc.data(), obs.data(), F.mvScaleFactors.data(), (int)F.mvScaleFactors.size(), th,
-                                                              mfNNratio, match.data(), &nmatches), "planar_lsd_search_by_projection")) return 0;
-    }
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_lsd_search_by_projection", [&](planar_ctx* ctx) {
+            return planar_lsd_search_by_projection(ctx, 1, &nl, nl, (const planar_keyline*)F.mvKeylinesUn.data(), ldesc.data(), blocked.data(), &nm, nm, inview.data(), proj.data(),
+                                                   lvl.data(), vc.data(), mdesc.data(), obs.data(), F.mvScaleFactors.data(), (int)F.mvScaleFactors.size(), th, mfNNratio,
+                                                   match.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < nl; i++) if (match[i] >= 0) F.mvpMapLines[i] = vpMapLines[match[i]];
     return nmatches;
 }
@@ -586,59 +736,21 @@ inline int LSDmatcher::SearchByProjection(Frame& F, const std::vector<MapLine*>&
 inline int ORBmatcher::Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th) {
     const int M = (int)vpMapPoints.size(), N = pKF->N;
     if (M == 0) return 0;
-    // the key frame's side (what FrameGather collects of a Frame; KeyFrame keeps the bounds / grid constants per object and the pose behind GetPose())
-    int32_t n = N;
-    std::vector<planar_keypoint> keys(N > 0 ? N : 1);
-    std::vector<float> ur(keys.size(), -1.f);
-    std::vector<uint8_t> kdesc(keys.size() * 32, 0);
-    for (int i = 0; i < N; i++) {
-        std::memcpy(&keys[i], &pKF->mvKeysUn[i], sizeof(planar_keypoint));
-        ur[i] = pKF->mvuRight.empty() ? -1.f : pKF->mvuRight[i];
-        std::memcpy(&kdesc[(size_t)i * 32], pKF->mDescriptors.ptr(i), 32);
-    }
-    float Tcw[16];
-    { cv::Mat T = pKF->GetPose(); for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = T.at<float>(r, c); }
-    planar_frame_view v;
-    std::memset(&v, 0, sizeof(v));
-    v.B = 1; v.stride = (int32_t)keys.size(); v.n = &n; v.keys_un = keys.data(); v.u_right = ur.data(); v.desc = kdesc.data(); v.Tcw = Tcw;
-    v.min_x = pKF->mnMinX; v.max_x = pKF->mnMaxX; v.min_y = pKF->mnMinY; v.max_y = pKF->mnMaxY;
-    v.grid_w_inv = pKF->mfGridElementWidthInv; v.grid_h_inv = pKF->mfGridElementHeightInv;
-    v.fx = pKF->fx; v.fy = pKF->fy; v.cx = pKF->cx; v.cy = pKF->cy; v.bf = pKF->mbf; v.b = pKF->mb;
-    for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) v.scale_factors[l] = pKF->mvScaleFactors[l];
-    // the map points' side
-    std::vector<uint8_t> usable(M, 0), desc((size_t)M * 32, 0);
-    std::vector<float> xw((size_t)M * 3, 0.f), nrm((size_t)M * 3, 0.f), mn(M, 0.f), mx(M, 0.f);
-    for (int j = 0; j < M; j++) {
-        MapPoint* p = vpMapPoints[j];
-        if (!p || p->isBad() || p->IsInKeyFrame(pKF)) continue;                     // :849-853
-        usable[j] = 1;
-        cv::Mat X = p->GetWorldPos(), nv = p->GetNormal(), d = p->GetDescriptor();
-        for (int k = 0; k < 3; k++) { xw[3 * j + k] = X.at<float>(k); nrm[3 * j + k] = nv.at<float>(k); }
-        std::memcpy(&desc[(size_t)j * 32], d.ptr(0), 32);
-        p->GetDistanceRange(mn[j], mx[j]);
-    }
+    using namespace planar_adapter;
+    // the key frame's side: every part of a Frame's view but `blocked`; KeyFrame keeps the bounds / grid constants per object and the pose behind GetPose()
+    ViewGather kf;
+    kf.add_keys(pKF->mvKeysUn, N).add_u_right(pKF->mvuRight).add_desc(pKF->mDescriptors).add_pose(pKF->GetPose());
+    kf.add_bounds(*pKF).add_grid(*pKF).add_intrinsics(*pKF).add_stereo(*pKF).add_scales(pKF->mvScaleFactors, false);
+    // the map points' side: not NULL, not bad, not in the key frame yet (:849-853)
+    PointGather pts;
+    pts.add_points(vpMapPoints, (size_t)M, [&](MapPoint* p) { return p->IsInKeyFrame(pKF); }).add_normals(vpMapPoints).add_desc(vpMapPoints).add_range(vpMapPoints);
     std::vector<int32_t> idx(M, -1);
     int32_t m = M, nFused = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_fuse_search(L.ctx, &v, pKF->mvInvLevelSigma2.data(), pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, usable.data(), xw.data(),
-                                                 nrm.data(), mn.data(), mx.data(), desc.data(), th, idx.data(), nullptr, &nFused), "planar_fuse_search")) return 0;
-    }
-    for (int j = 0; j < M; j++) {                                                   // :953-974
-        if (idx[j] < 0) continue;
-        MapPoint* pMP = vpMapPoints[j];
-        MapPoint* pMPinKF = pKF->GetMapPoint(idx[j]);
-        if (pMPinKF) {
-            if (!pMPinKF->isBad()) {
-                if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
-                else pMPinKF->Replace(pMP);
-            }
-        } else {
-            pMP->AddObservation(pKF, idx[j]);
-            pKF->AddMapPoint(pMP, idx[j]);
-        }
-    }
+    if (!on_lane(TRACKING, "planar_fuse_search", [&](planar_ctx* ctx) {
+            return planar_fuse_search(ctx, &kf.view, pKF->mvInvLevelSigma2.data(), pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), pts.xw.data(),
+                                      pts.nrm.data(), pts.mn.data(), pts.mx.data(), pts.desc.data(), th, idx.data(), nullptr, &nFused);
+        })) return 0;
+    apply_fuse_edits(pKF, vpMapPoints, idx, [&](int i) { return pKF->GetMapPoint(i); }, [&](MapPoint* p, int i) { pKF->AddMapPoint(p, i); });
     return nFused;
 }
 
@@ -648,17 +760,12 @@ inline int LSDmatcher::Fuse(KeyFrame* pKF, const std::vector<MapLine*>& vpMapLin
     int32_t nl = (int32_t)pKF->mvKeyLines.size();
     if (M == 0 || nl == 0) return 0;
     static_assert(sizeof(cv::line_descriptor::KeyLine) == sizeof(planar_keyline), "KeyLine layout");
+    using namespace planar_adapter;
     std::vector<uint8_t> ldesc((size_t)nl * 32);
-    for (int i = 0; i < nl; i++) std::memcpy(&ldesc[(size_t)i * 32], pKF->mLineDescriptors.ptr(i), 32);
-    float Tcw[16];
-    { cv::Mat T = pKF->GetPose(); for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = T.at<float>(r, c); }
-    planar_frame_view v;
-    std::memset(&v, 0, sizeof(v));
-    v.B = 1; v.stride = 1; v.Tcw = Tcw;
-    v.min_x = pKF->mnMinX; v.max_x = pKF->mnMaxX; v.min_y = pKF->mnMinY; v.max_y = pKF->mnMaxY;
-    v.fx = pKF->fx; v.fy = pKF->fy; v.cx = pKF->cx; v.cy = pKF->cy; v.bf = pKF->mbf; v.b = pKF->mb;
+    copy_desc_rows(ldesc.data(), pKF->mLineDescriptors, nl);
+    ViewGather kf;                                                                  // no key points: the pose, the bounds, the camera and the scale table
+    kf.add_pose(pKF->GetPose()).add_bounds(*pKF).add_intrinsics(*pKF).add_stereo(*pKF).add_scales(pKF->mvScaleFactors, false);
     const int n_levels = (int)std::min<size_t>(pKF->mvScaleFactors.size(), PLANAR_MAX_LEVELS);
-    for (int l = 0; l < n_levels; l++) v.scale_factors[l] = pKF->mvScaleFactors[l];
     std::vector<uint8_t> usable(M, 0), desc((size_t)M * 32, 0);
     std::vector<double> xw6((size_t)M * 6, 0.0), nrm((size_t)M * 3, 0.0);
     std::vector<float> mn(M, 0.f), mx(M, 0.f);
@@ -670,32 +777,16 @@ inline int LSDmatcher::Fuse(KeyFrame* pKF, const std::vector<MapLine*>& vpMapLin
         const Eigen::Vector3d Pn = p->GetNormal();
         for (int k = 0; k < 6; k++) xw6[6 * j + k] = P(k);
         for (int k = 0; k < 3; k++) nrm[3 * j + k] = Pn(k);
-        cv::Mat d = p->GetDescriptor();
-        std::memcpy(&desc[(size_t)j * 32], d.ptr(0), 32);
+        copy_desc_rows(&desc[(size_t)j * 32], p->GetDescriptor(), 1);
         p->GetDistanceRange(mn[j], mx[j]);
     }
     std::vector<int32_t> idx(M, -1);
     int32_t m = M, nFused = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_lsd_fuse_search(L.ctx, &v, pKF->mfLogScaleFactor, n_levels, &nl, nl, (const planar_keyline*)pKF->mvKeyLines.data(), ldesc.data(), &m, M, 0,
-                                                     usable.data(), xw6.data(), nrm.data(), mn.data(), mx.data(), desc.data(), th, idx.data(), nullptr, &nFused), "planar_lsd_fuse_search")) return 0;
-    }
-    for (int j = 0; j < M; j++) {                                                   // :993-1010
-        if (idx[j] < 0) continue;
-        MapLine* pML = vpMapLines[j];
-        MapLine* pMLinKF = pKF->GetMapLine(idx[j]);
-        if (pMLinKF) {
-            if (!pMLinKF->isBad()) {
-                if (pMLinKF->Observations() > pML->Observations()) pML->Replace(pMLinKF);
-                else pMLinKF->Replace(pML);
-            }
-        } else {
-            pML->AddObservation(pKF, idx[j]);
-            pKF->AddMapLine(pML, idx[j]);
-        }
-    }
+    if (!on_lane(TRACKING, "planar_lsd_fuse_search", [&](planar_ctx* ctx) {
+            return planar_lsd_fuse_search(ctx, &kf.view, pKF->mfLogScaleFactor, n_levels, &nl, nl, (const planar_keyline*)pKF->mvKeyLines.data(), ldesc.data(), &m, M, 0, usable.data(),
+                                          xw6.data(), nrm.data(), mn.data(), mx.data(), desc.data(), th, idx.data(), nullptr, &nFused);
+        })) return 0;
+    apply_fuse_edits(pKF, vpMapLines, idx, [&](int i) { return pKF->GetMapLine(i); }, [&](MapLine* p, int i) { pKF->AddMapLine(p, i); });
     return nFused;
 }
 #endif   // PLANAR_ADAPTERS_WITH_FUSE
@@ -707,7 +798,7 @@ inline int PlaneMatcher::SearchMapByCoefficients(Frame& pF, const std::vector<Ma
     if (np == 0) return 0;
     std::vector<float> coef((size_t)np * 4), T(16), mcoef((size_t)(nm ? nm : 1) * 4, 0.f);
     for (int i = 0; i < np; i++) for (int k = 0; k < 4; k++) coef[4 * i + k] = pF.mvPlaneCoefficients[i].template at<float>(k);
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T[4 * r + c] = pF.mTcw.template at<float>(r, c);
+    planar_adapter::mat_to_array(pF.mTcw, T.data());
     std::vector<uint8_t> valid(nm ? nm : 1, 0);
     std::vector<int32_t> npts(nm ? nm : 1, 0);
     int maxp = 1;
@@ -727,12 +818,10 @@ inline int PlaneMatcher::SearchMapByCoefficients(Frame& pF, const std::vector<Ma
     const float th[4] = {dTh, aTh, verTh, parTh};
     std::vector<int32_t> a(np, -1), v(np, -1), par(np, -1);
     int32_t nmatches = 0;
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_plane_search_by_coefficients(L.ctx, 1, &np, np, coef.data(), T.data(), 0, &nm, nm ? nm : 1, valid.data(), mcoef.data(), npts.data(), maxp, pts.data(),
-                                                                  th, a.data(), v.data(), par.data(), &nmatches), "planar_plane_search_by_coefficients")) return 0;
-    }
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_plane_search_by_coefficients", [&](planar_ctx* ctx) {
+            return planar_plane_search_by_coefficients(ctx, 1, &np, np, coef.data(), T.data(), 0, &nm, nm ? nm : 1, valid.data(), mcoef.data(), npts.data(), maxp, pts.data(), th,
+                                                       a.data(), v.data(), par.data(), &nmatches);
+        })) return 0;
     for (int i = 0; i < np; i++) {
         if (a[i] >= 0) pF.mvpMapPlanes[i] = vpMapPlanes[a[i]];
         if (v[i] >= 0) pF.mvpVerticalPlanes[i] = vpMapPlanes[v[i]];
@@ -755,7 +844,7 @@ template <class FrameT> inline int pose_opt(FrameT* pFrame, int mode) {
         const cv::KeyPoint& kp = pFrame->mvKeysUn[i];
         pt_obs[3 * i] = kp.pt.x; pt_obs[3 * i + 1] = kp.pt.y; pt_obs[3 * i + 2] = pFrame->mvuRight[i];
         pt_is2[i] = pFrame->mvInvLevelSigma2[kp.octave];
-        if (MapPoint* p = pFrame->mvpMapPoints[i]) { pt_valid[i] = 1; cv::Mat x = p->GetWorldPos(); for (int k = 0; k < 3; k++) pt_xw[3 * i + k] = x.at<float>(k); }
+        if (MapPoint* p = pFrame->mvpMapPoints[i]) { pt_valid[i] = 1; planar_adapter::vec3_to_array(p->GetWorldPos(), &pt_xw[3 * i]); }
     }
     for (int i = 0; i < NL; i++) {
         for (int k = 0; k < 3; k++) ln_obs[3 * i + k] = pFrame->mvKeyLineFunctions[i][k];
@@ -766,7 +855,7 @@ template <class FrameT> inline int pose_opt(FrameT* pFrame, int mode) {
         MapPlane* three[3] = {pFrame->mvpMapPlanes[i], pFrame->mvpParallelPlanes[i], pFrame->mvpVerticalPlanes[i]};
         for (int j = 0; j < 3; j++) if (three[j]) { pl_valid[3 * i + j] = 1; cv::Mat c = three[j]->GetWorldPos(); for (int k = 0; k < 4; k++) pl_world[(3 * i + j) * 4 + k] = c.at<float>(k); }
     }
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tin[4 * r + c] = pFrame->mTcw.template at<float>(r, c);
+    planar_adapter::mat_to_array(pFrame->mTcw, Tin.data());
     planar_pose_batch pb;
     std::memset(&pb, 0, sizeof(pb));
     pb.B = 1; pb.max_points = MP; pb.max_lines = ML; pb.max_planes = MM;
@@ -774,16 +863,8 @@ template <class FrameT> inline int pose_opt(FrameT* pFrame, int mode) {
     pb.pt_inv_sigma2 = pt_is2.data(); pb.ln_valid = ln_valid.data(); pb.ln_obs = ln_obs.data(); pb.ln_xw = ln_xw.data(); pb.pl_meas = pl_meas.data(); pb.pl_valid = pl_valid.data();
     pb.pl_world = pl_world.data(); pb.Tcw_in = Tin.data(); pb.Tcw_out = Tout.data(); pb.pt_outlier = pt_out.data(); pb.ln_outlier = ln_out.data(); pb.pl_outlier = pl_out.data();
     pb.n_inliers = &n_inliers; pb.lm_iters = nullptr;
-    planar_pose_params prm;
-    prm.fx = FrameT::fx; prm.fy = FrameT::fy; prm.cx = FrameT::cx; prm.cy = FrameT::cy; prm.bf = pFrame->mbf;
-    prm.angle_info = Config::Get<double>("Plane.AngleInfo"); prm.distance_info = Config::Get<double>("Plane.DistanceInfo");
-    prm.parallel_info = Config::Get<double>("Plane.ParallelInfo"); prm.vertical_info = Config::Get<double>("Plane.VerticalInfo");
-    prm.plane_chi = Config::Get<double>("Plane.Chi"); prm.vp_chi = Config::Get<double>("Plane.VPChi");
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::tracking_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_pose_opt(L.ctx, &pb, &prm, mode, 4, 10), "planar_pose_opt")) return 0;
-    }
+    const planar_pose_params prm = planar_adapter::plane_pose_params<Config>(pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy, pFrame->mbf);
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_pose_opt", [&](planar_ctx* ctx) { return planar_pose_opt(ctx, &pb, &prm, mode, 4, 10); })) return 0;
     // the reference writes the flags of the correspondences it used and the pose through Frame::SetPose
     for (int i = 0; i < N; i++) if (pt_valid[i]) pFrame->mvbOutlier[i] = pt_out[i] != 0;
     for (int i = 0; i < NL; i++) if (ln_valid[i]) pFrame->mvbLineOutlier[i] = ln_out[i] != 0;
@@ -794,9 +875,7 @@ template <class FrameT> inline int pose_opt(FrameT* pFrame, int mode) {
             if (pl_valid[3 * i + 2]) pFrame->mvbVerPlaneOutlier[i] = pl_out[3 * i + 2] != 0;
         }
     }
-    cv::Mat pose(4, 4, CV_32F);
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) pose.at<float>(r, c) = Tout[4 * r + c];
-    pFrame->SetPose(pose);
+    pFrame->SetPose(planar_adapter::array_to_mat(Tout.data()));
     return n_inliers;
 }
 }  // namespace planar_detail
@@ -837,19 +916,19 @@ struct TriPack {
         const size_t o = e * stride;
         const int N = kf->N;
         n[e] = N; mb[e] = kf->mb; mbf[e] = kf->mbf;
+        copy_keypoints(&keys_un[o], kf->mvKeysUn.data(), N > 0 ? N : 0);
+        copy_keypoints(&keys[o], kf->mvKeys.data(), N > 0 ? N : 0);
+        copy_desc_rows(&desc[o * 32], kf->mDescriptors, N);
         for (int i = 0; i < N; i++) {
-            std::memcpy(&keys_un[o + i], &kf->mvKeysUn[i], sizeof(planar_keypoint));
-            std::memcpy(&keys[o + i], &kf->mvKeys[i], sizeof(planar_keypoint));
             u_right[o + i] = kf->mvuRight[i];
             depth[o + i] = kf->mvDepth[i];
             // src/LocalMapping.cc:411, :413 in the host's float libm: the value decides a branch, so it is not left to the device
             cos_stereo[o + i] = std::cos(2 * std::atan2(kf->mb / 2, kf->mvDepth[i]));
-            std::memcpy(&desc[(o + i) * 32], kf->mDescriptors.ptr(i), 32);
             occupied[o + i] = kf->GetMapPoint(i) != NULL;
         }
         for (const auto& kv : kf->mFeatVec) for (unsigned int i : kv.second) if ((int)i < N) node[o + i] = (int32_t)kv.first;
-        const cv::Mat T = kf->GetPose(), Ti = kf->GetPoseInverse();
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { Tcw[e * 16 + 4 * r + c] = T.template at<float>(r, c); Twc[e * 16 + 4 * r + c] = Ti.template at<float>(r, c); }
+        mat_to_array(kf->GetPose(), &Tcw[e * 16]);
+        mat_to_array(kf->GetPoseInverse(), &Twc[e * 16]);
     }
     planar_tri_keyframes view() const {
         planar_tri_keyframes v;
@@ -869,11 +948,7 @@ inline std::vector<NewPointCandidate> CreateNewMapPoints(KeyFrameT* pKF, const s
     if (K > PLANAR_TRI_MAX_NEIGHBOURS) { std::fprintf(stderr, "planar (CreateNewMapPoints): more than %d neighbours - degraded to \"nothing found\"\n", PLANAR_TRI_MAX_NEIGHBOURS); return out; }
     int32_t stride = pKF->N;
     for (KeyFrameT* kf : vpNeighKFs) if (kf->N > stride) stride = kf->N;
-    planar_tri_camera cam;
-    std::memset(&cam, 0, sizeof(cam));
-    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.invfx = pKF->invfx; cam.invfy = pKF->invfy; cam.scale_factor = pKF->mfScaleFactor;
-    cam.n_levels = (int32_t)pKF->mvScaleFactors.size();
-    for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) { cam.scale_factors[l] = pKF->mvScaleFactors[l]; cam.level_sigma2[l] = pKF->mvLevelSigma2[l]; }
+    const planar_tri_camera cam = tri_camera(pKF);
     detail::TriPack cur(1, stride), nb((size_t)K, stride);
     cur.put(0, pKF);
     for (int k = 0; k < K; k++) nb.put((size_t)k, vpNeighKFs[k]);
@@ -881,11 +956,9 @@ inline std::vector<NewPointCandidate> CreateNewMapPoints(KeyFrameT* pKF, const s
     std::vector<int32_t> kk(stride, -1), i1(stride, -1), i2(stride, -1);
     std::vector<float> x((size_t)stride * 3, 0.f);
     int32_t n_neigh = K, n_new = 0;
-    {
-        Runtime::Lane& L = Runtime::get().lane(TRACKING);
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_create_new_map_points(L.ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data()), "planar_create_new_map_points")) return out;
-    }
+    if (!on_lane(TRACKING, "planar_create_new_map_points", [&](planar_ctx* ctx) {
+            return planar_create_new_map_points(ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data());
+        })) return out;
     out.resize(n_new);
     for (int j = 0; j < n_new; j++) { out[j].neighbour = kk[j]; out[j].idx1 = i1[j]; out[j].idx2 = i2[j]; for (int c = 0; c < 3; c++) out[j].x3D[c] = x[3 * j + c]; }
     return out;
@@ -936,10 +1009,8 @@ struct TriLinePack {
         const size_t o = e * stride;
         const int N = kf->mLineDescriptors.rows;
         n[e] = N;
-        for (int i = 0; i < N; i++) {
-            std::memcpy(ldesc + (o + i) * 32, kf->mLineDescriptors.ptr(i), 32);
-            occupied[o + i] = kf->GetMapLine(i) != NULL;
-        }
+        copy_desc_rows(ldesc + o * 32, kf->mLineDescriptors, N);
+        for (int i = 0; i < N; i++) occupied[o + i] = kf->GetMapLine(i) != NULL;
     }
     template <class KeyFrameT> void put(size_t e, KeyFrameT* kf) {
         put_search(e, kf);
@@ -955,8 +1026,8 @@ struct TriLinePack {
             depth_line[o + i] = kf->mvDepthLine[i];
             for (int c = 0; c < 6; c++) lines3d[(o + i) * 6 + c] = kf->mvLines3D[i](c);
         }
-        const cv::Mat T = kf->GetPose(), Ti = kf->GetPoseInverse();
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { Tcw[e * 16 + 4 * r + c] = T.template at<float>(r, c); Twc[e * 16 + 4 * r + c] = Ti.template at<float>(r, c); }
+        mat_to_array(kf->GetPose(), &Tcw[e * 16]);
+        mat_to_array(kf->GetPoseInverse(), &Twc[e * 16]);
     }
     planar_tri_line_keyframes view(bool search) const {
         planar_tri_line_keyframes v;
@@ -977,11 +1048,7 @@ inline std::vector<NewLineCandidate> CreateNewMapLines(KeyFrameT* pKF, const std
     int32_t stride = pKF->mLineDescriptors.rows;
     for (KeyFrameT* kf : vpNeighKFs) if (kf->mLineDescriptors.rows > stride) stride = kf->mLineDescriptors.rows;
     if (stride > PLANAR_MAX_KEYFRAME_LINES) { std::fprintf(stderr, "planar (CreateNewMapLines): more than %d lines in a key frame - degraded to \"nothing found\"\n", PLANAR_MAX_KEYFRAME_LINES); return out; }
-    planar_tri_camera cam;
-    std::memset(&cam, 0, sizeof(cam));
-    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.invfx = pKF->invfx; cam.invfy = pKF->invfy; cam.scale_factor = pKF->mfScaleFactor;
-    cam.n_levels = (int32_t)pKF->mvScaleFactors.size();
-    for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) { cam.scale_factors[l] = pKF->mvScaleFactors[l]; cam.level_sigma2[l] = pKF->mvLevelSigma2[l]; }
+    const planar_tri_camera cam = tri_camera(pKF);
     detail::TriLinePack cur(1, stride), nb((size_t)K, stride);
     cur.put(0, pKF);
     for (int k = 0; k < K; k++) nb.put((size_t)k, vpNeighKFs[k]);
@@ -989,11 +1056,9 @@ inline std::vector<NewLineCandidate> CreateNewMapLines(KeyFrameT* pKF, const std
     std::vector<int32_t> kk(stride, -1), i1(stride, -1), i2(stride, -1);
     std::vector<double> x((size_t)stride * 6, 0.0);
     int32_t n_neigh = K, n_new = 0;
-    {
-        Runtime::Lane& L = Runtime::get().lane(TRACKING);
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_create_new_map_lines(L.ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data()), "planar_create_new_map_lines")) return out;
-    }
+    if (!on_lane(TRACKING, "planar_create_new_map_lines", [&](planar_ctx* ctx) {
+            return planar_create_new_map_lines(ctx, &cam, &vc, &vn, &n_neigh, K, &n_new, kk.data(), i1.data(), i2.data(), x.data());
+        })) return out;
     out.resize(n_new);
     for (int j = 0; j < n_new; j++) { out[j].neighbour = kk[j]; out[j].idx1 = i1[j]; out[j].idx2 = i2[j]; for (int c = 0; c < 6; c++) out[j].line3D[c] = x[6 * j + c]; }
     return out;
@@ -1013,11 +1078,9 @@ inline int SearchLinesForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, std::ve
     const planar_tri_line_keyframes va = a.view(true), vb = b.view(true);
     std::vector<int32_t> match(stride, -1);
     int32_t nmatches = 0;
-    {
-        Runtime::Lane& L = Runtime::get().lane(TRACKING);
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_lsd_search_for_triangulation(L.ctx, &va, &vb, match.data(), &nmatches, NULL, NULL), "planar_lsd_search_for_triangulation")) return 0;
-    }
+    if (!on_lane(TRACKING, "planar_lsd_search_for_triangulation", [&](planar_ctx* ctx) {
+            return planar_lsd_search_for_triangulation(ctx, &va, &vb, match.data(), &nmatches, NULL, NULL);
+        })) return 0;
     for (int q = 0; q < n1; q++) if (match[q] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)q, (size_t)match[q]));
     return nmatches;
 }
@@ -1122,12 +1185,10 @@ protected:
         db.n_kf = &n_kf; db.present = present.data(); db.add_seq = add_seq.data(); db.bow_n = bow_n.data(); db.bow_word = bow_word.data(); db.bow_value = bow_value.data();
         db.covis = covis.data();
         int32_t n_cand = 0, n_scored = 0;
-        {
-            Runtime::Lane& L = Runtime::get().lane(TRACKING);
-            std::lock_guard<std::mutex> lg(L.mu);
-            if (!ok(planar_kfdb_detect(L.ctx, mode, &db, 1, &q_db, &q_n, qw.data(), qv.data(), (int)QW, mode ? excluded.data() : NULL, mode ? &minScore : NULL, score.data(),
-                                       common.data(), &n_cand, cand.data(), &n_scored), "planar_kfdb_detect")) return out;
-        }
+        if (!on_lane(TRACKING, "planar_kfdb_detect", [&](planar_ctx* ctx) {
+                return planar_kfdb_detect(ctx, mode, &db, 1, &q_db, &q_n, qw.data(), qv.data(), (int)QW, mode ? excluded.data() : NULL, mode ? &minScore : NULL, score.data(),
+                                          common.data(), &n_cand, cand.data(), &n_scored);
+            })) return out;
         for (size_t j = 0; j < n; j++) slots_[j].score[mode] = score[j];
         out.reserve(n_cand);
         for (int i = 0; i < n_cand; i++) out.push_back(slots_[cand[i]].kf);
@@ -1184,8 +1245,7 @@ inline void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Ma
     unsigned long maxKFid = 0;
     for (int k = 0; k < K; k++) {
         kf_index[kfs[k]] = k;
-        cv::Mat T = kfs[k]->GetPose();
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) kf_Tcw[(size_t)k * 16 + 4 * r + c] = T.at<float>(r, c);
+        planar_adapter::mat_to_array(kfs[k]->GetPose(), &kf_Tcw[(size_t)k * 16]);
         kf_fixed[k] = (size_t)k >= n_local || kfs[k]->mnId == 0;
         if (kfs[k]->mnId > maxKFid) maxKFid = kfs[k]->mnId;
     }
@@ -1251,17 +1311,11 @@ inline void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Ma
     std::vector<uint8_t> out_e(std::max(NE, 1));
     planar_ba_problem P{K, kf_Tcw.data(), kf_fixed.data(), NL, lm_type.data(), lm_init.data(), NE, e_kf.data(), e_lm.data(), e_type.data(), e_meas.data(), e_is2.data()};
     planar_ba_result R{out_T.data(), out_lm.data(), out_e.data(), 0, 0};
-    planar_pose_params prm;
-    prm.fx = pKF->fx; prm.fy = pKF->fy; prm.cx = pKF->cx; prm.cy = pKF->cy; prm.bf = pKF->mbf;
-    prm.angle_info = Config::Get<double>("Plane.AngleInfo"); prm.distance_info = Config::Get<double>("Plane.DistanceInfo");
-    prm.parallel_info = Config::Get<double>("Plane.ParallelInfo"); prm.vertical_info = Config::Get<double>("Plane.VerticalInfo");
-    prm.plane_chi = Config::Get<double>("Plane.Chi"); prm.vp_chi = Config::Get<double>("Plane.VPChi");
+    const planar_pose_params prm = planar_adapter::plane_pose_params<Config>(pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf);
     static_assert(sizeof(bool) == 1, "bool* pbStopFlag is passed as a byte flag");
-    {
-        planar_adapter::Runtime::Lane& L = planar_adapter::Runtime::get().lane(planar_adapter::TRACKING);
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!planar_adapter::ok(planar_local_ba(L.ctx, &P, &prm, 5, 10, &R, reinterpret_cast<const volatile unsigned char*>(pbStopFlag), nullptr), "planar_local_ba")) return;
-    }
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_local_ba", [&](planar_ctx* ctx) {
+            return planar_local_ba(ctx, &P, &prm, 5, 10, &R, reinterpret_cast<const volatile unsigned char*>(pbStopFlag), nullptr);
+        })) return;
     // erase lists (:2471-2620) and write-back (:2622-2680) under the map mutex
     std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
     for (int e = 0; e < NE; e++) {
@@ -1278,11 +1332,7 @@ inline void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Ma
             default: { MapPlane* p = (MapPlane*)assoc[e].lm; if (p->isBad()) break; k->EraseMapParallelPlaneMatch(p); p->EraseParObservation(k); break; }
         }
     }
-    for (size_t k = 0; k < n_local; k++) {
-        cv::Mat T(4, 4, CV_32F);
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.at<float>(r, c) = out_T[k * 16 + 4 * r + c];
-        kfs[k]->SetPose(T);
-    }
+    for (size_t k = 0; k < n_local; k++) kfs[k]->SetPose(planar_adapter::array_to_mat(&out_T[k * 16]));
     for (size_t i = 0; i < pts.size(); i++) {
         cv::Mat X(3, 1, CV_32F);
         for (int j = 0; j < 3; j++) X.at<float>(j) = (float)out_lm[(size_t)pt_lm[i] * 4 + j];
@@ -1318,56 +1368,25 @@ inline void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Ma
 #include <set>
 namespace planar_adapter {
 
-// the key frame's side: key points, descriptors, bounds, grid constants, intrinsics, scale factors; the pose only where asked (GetPose())
-struct KeyFrameGather {
-    int32_t n;
-    std::vector<planar_keypoint> keys;
-    std::vector<uint8_t> desc;
-    float Tcw[16];
-    planar_frame_view view;
-    template <class KeyFrameT> KeyFrameGather(KeyFrameT* pKF, bool with_pose) {
-        n = pKF->N;
-        keys.resize(n > 0 ? n : 1); desc.assign(keys.size() * 32, 0);
-        for (int i = 0; i < n; i++) { std::memcpy(&keys[i], &pKF->mvKeysUn[i], sizeof(planar_keypoint)); std::memcpy(&desc[(size_t)i * 32], pKF->mDescriptors.ptr(i), 32); }
-        std::memset(&view, 0, sizeof(view));
-        view.B = 1; view.stride = (int32_t)keys.size(); view.n = &n; view.keys_un = keys.data(); view.desc = desc.data();
-        if (with_pose) { cv::Mat T = pKF->GetPose(); for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw[4 * r + c] = T.template at<float>(r, c); view.Tcw = Tcw; }
-        view.min_x = pKF->mnMinX; view.max_x = pKF->mnMaxX; view.min_y = pKF->mnMinY; view.max_y = pKF->mnMaxY;
-        view.grid_w_inv = pKF->mfGridElementWidthInv; view.grid_h_inv = pKF->mfGridElementHeightInv;
-        view.fx = pKF->fx; view.fy = pKF->fy; view.cx = pKF->cx; view.cy = pKF->cy; view.bf = pKF->mbf; view.b = pKF->mb;
-        for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = pKF->mvScaleFactors[l];
-    }
-};
-
-// a list of map points as the arrays of the entries: usable = non-NULL && !isBad()
-struct PointGather {
-    std::vector<uint8_t> usable, desc;
-    std::vector<float> xw, nrm, mn, mx;
-    planar_kf_points kp;
-    template <class MapPointT> explicit PointGather(const std::vector<MapPointT*>& v, bool want_normal) {
-        const size_t M = v.size() ? v.size() : 1;
-        usable.assign(M, 0); desc.assign(M * 32, 0); xw.assign(M * 3, 0.f); nrm.assign(M * 3, 0.f); mn.assign(M, 0.f); mx.assign(M, 0.f);
-        for (size_t j = 0; j < v.size(); j++) {
-            MapPointT* p = v[j];
-            if (!p || p->isBad()) continue;
-            usable[j] = 1;
-            cv::Mat X = p->GetWorldPos(), d = p->GetDescriptor();
-            for (int k = 0; k < 3; k++) xw[3 * j + k] = X.template at<float>(k);
-            if (want_normal) { cv::Mat nv = p->GetNormal(); for (int k = 0; k < 3; k++) nrm[3 * j + k] = nv.template at<float>(k); }
-            std::memcpy(&desc[j * 32], d.ptr(0), 32);
-            p->GetDistanceRange(mn[j], mx[j]);
-        }
-        kp.usable = usable.data(); kp.xw = xw.data(); kp.min_dist = mn.data(); kp.max_dist = mx.data(); kp.desc = desc.data();
-    }
-};
-
-inline Runtime::Lane& loop_lane() { return Runtime::get().lane(TRACKING); }
+// the key frame's side: key points, descriptors, bounds, grid constants, intrinsics, scale factors.  No pose: a caller that needs it adds add_pose(pKF->GetPose())
+template <class KeyFrameT> inline ViewGather keyframe_view(KeyFrameT* pKF) {
+    ViewGather g;
+    g.add_keys(pKF->mvKeysUn, pKF->N).add_desc(pKF->mDescriptors);
+    g.add_bounds(*pKF).add_grid(*pKF).add_intrinsics(*pKF).add_stereo(*pKF).add_scales(pKF->mvScaleFactors, false);
+    return g;
+}
+// a list of map points for the searches: usable, xw, descriptor, distance range
+template <class MapPointT> inline PointGather search_points(const std::vector<MapPointT*>& v) {
+    PointGather p;
+    p.add_points(v).add_desc(v).add_range(v);
+    return p;
+}
 
 template <class KeyFrameT, class MapPointT>
 int SearchByBoWKF(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, float nn_ratio, bool check_orientation) {
     KeyFrameT* kf[2] = {pKF1, pKF2};
     std::vector<MapPointT*> mps[2] = {pKF1->GetMapPointMatches(), pKF2->GetMapPointMatches()};
-    KeyFrameGather g1(pKF1, false), g2(pKF2, false);
+    ViewGather g1 = keyframe_view(pKF1), g2 = keyframe_view(pKF2);
     std::vector<int32_t> node[2];
     std::vector<uint8_t> usable[2];
     for (int s = 0; s < 2; s++) {
@@ -1379,13 +1398,10 @@ int SearchByBoWKF(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpM
     }
     std::vector<int32_t> match(g1.keys.size(), -1);
     int32_t nmatches = 0;
-    {
-        Runtime::Lane& L = loop_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_search_by_bow_kf(L.ctx, 1, &g1.n, g1.view.stride, node[0].data(), usable[0].data(), g1.keys.data(), g1.desc.data(), &g2.n, g2.view.stride, node[1].data(),
-                                        usable[1].data(), g2.keys.data(), g2.desc.data(), nn_ratio, check_orientation ? 1 : 0, match.data(), &nmatches), "planar_search_by_bow_kf"))
-            return 0;
-    }
+    if (!on_lane(TRACKING, "planar_search_by_bow_kf", [&](planar_ctx* ctx) {
+            return planar_search_by_bow_kf(ctx, 1, &g1.n, g1.view.stride, node[0].data(), usable[0].data(), g1.keys.data(), g1.desc.data(), &g2.n, g2.view.stride, node[1].data(),
+                                           usable[1].data(), g2.keys.data(), g2.desc.data(), nn_ratio, check_orientation ? 1 : 0, match.data(), &nmatches);
+        })) return 0;
     vpMatches12 = std::vector<MapPointT*>(mps[0].size(), static_cast<MapPointT*>(NULL));
     for (size_t i = 0; i < mps[0].size(); i++) if (match[i] >= 0) vpMatches12[i] = mps[1][match[i]];
     return nmatches;
@@ -1395,52 +1411,46 @@ template <class KeyFrameT, class MapPointT>
 int SearchBySim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, float s12, const cv::Mat& R12, const cv::Mat& t12, float th) {
     const std::vector<MapPointT*> mps1 = pKF1->GetMapPointMatches(), mps2 = pKF2->GetMapPointMatches();
     const int N1 = (int)mps1.size(), N2 = (int)mps2.size();
-    KeyFrameGather g1(pKF1, true), g2(pKF2, true);
-    PointGather p1(mps1, false), p2(mps2, false);
-    const int32_t NOT_IN_KF2 = -2;                                                      // matched, index not in pKF2: blocks i1 only (:1143)
-    std::vector<int32_t> entry(g1.keys.size(), -1);
+    ViewGather g1 = keyframe_view(pKF1), g2 = keyframe_view(pKF2);
+    g1.add_pose(pKF1->GetPose());
+    g2.add_pose(pKF2->GetPose());
+    const PointGather p1 = search_points(mps1), p2 = search_points(mps2);
+    std::vector<int32_t> entry(g1.keys.size(), -1);                                     // NOT_IN_KF2 here: matched, index not in pKF2, which blocks i1 only (:1143)
     for (int i = 0; i < N1; i++)
         if (vpMatches12[i]) { const int idx2 = vpMatches12[i]->GetIndexInKeyFrame(pKF2); entry[i] = idx2 >= 0 && idx2 < N2 ? idx2 : NOT_IN_KF2; }
     std::vector<int32_t> match = entry;
     float R[9], t[3];
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[3 * r + c] = R12.at<float>(r, c); t[r] = t12.at<float>(r); }
+    rt_to_array(R12, t12, R, 3, t, 1);
     int32_t nFound = 0;
-    {
-        Runtime::Lane& L = loop_lane();
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_search_by_sim3(L.ctx, &g1.view, &p1.kp, pKF1->mfLogScaleFactor, pKF1->mnScaleLevels, &g2.view, &p2.kp, pKF2->mfLogScaleFactor, pKF2->mnScaleLevels, &s12, R, t,
-                                      th, match.data(), &nFound), "planar_search_by_sim3"))
-            return 0;
-    }
+    if (!on_lane(TRACKING, "planar_search_by_sim3", [&](planar_ctx* ctx) {
+            return planar_search_by_sim3(ctx, &g1.view, &p1.kp, pKF1->mfLogScaleFactor, pKF1->mnScaleLevels, &g2.view, &p2.kp, pKF2->mfLogScaleFactor, pKF2->mnScaleLevels, &s12, R, t,
+                                         th, match.data(), &nFound);
+        })) return 0;
     for (int i = 0; i < N1; i++) if (match[i] != entry[i]) vpMatches12[i] = mps2[match[i]];      // :1323
     return nFound;
 }
-
-inline void scw_to_array(const cv::Mat& Scw, float* S) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) S[4 * r + c] = Scw.at<float>(r, c); }
 
 template <class KeyFrameT, class MapPointT>
 int SearchByProjectionScw(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched, int th) {
     const int M = (int)vpPoints.size();
     if (M == 0) return 0;
-    KeyFrameGather g(pKF, false);
-    std::vector<uint8_t> blocked(g.keys.size(), 0), found(M, 0);
-    for (size_t i = 0; i < vpMatched.size() && i < blocked.size(); i++) blocked[i] = vpMatched[i] != NULL;
-    g.view.blocked = blocked.data();
+    ViewGather g = keyframe_view(pKF);
+    g.add_blocked();                                                                    // a feature that holds a match on entry
+    std::vector<uint8_t> found(M, 0);
+    for (size_t i = 0; i < vpMatched.size() && i < g.blocked.size(); i++) g.blocked[i] = vpMatched[i] != NULL;
     std::set<MapPointT*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
     spAlreadyFound.erase(static_cast<MapPointT*>(NULL));
-    PointGather pts(vpPoints, true);
+    PointGather pts = search_points(vpPoints);
+    pts.add_normals(vpPoints);
     for (int j = 0; j < M; j++) found[j] = spAlreadyFound.count(vpPoints[j]) ? 1 : 0;
     float S[16];
-    scw_to_array(Scw, S);
+    mat_to_array(Scw, S);
     std::vector<int32_t> match(g.keys.size(), -1);
     int32_t m = M, nmatches = 0;
-    {
-        Runtime::Lane& L = loop_lane();
-        std::lock_guard<std::mutex> lk(L.mu);
-        if (!ok(planar_search_by_projection_sim3(L.ctx, &g.view, S, pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), found.data(), pts.xw.data(), pts.nrm.data(),
-                                                 pts.mn.data(), pts.mx.data(), pts.desc.data(), th, match.data(), &nmatches), "planar_search_by_projection_sim3"))
-            return 0;
-    }
+    if (!on_lane(TRACKING, "planar_search_by_projection_sim3", [&](planar_ctx* ctx) {
+            return planar_search_by_projection_sim3(ctx, &g.view, S, pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), found.data(), pts.xw.data(),
+                                                    pts.nrm.data(), pts.mn.data(), pts.mx.data(), pts.desc.data(), th, match.data(), &nmatches);
+        })) return 0;
     for (size_t i = 0; i < vpMatched.size() && i < match.size(); i++) if (match[i] >= 0) vpMatched[i] = vpPoints[match[i]];   // :400
     return nmatches;
 }
@@ -1449,24 +1459,22 @@ template <class KeyFrameT, class MapPointT>
 int FuseScw(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
     const int M = (int)vpPoints.size();
     if (M == 0) return 0;
-    KeyFrameGather g(pKF, false);
+    const ViewGather g = keyframe_view(pKF);
     const std::set<MapPointT*> spAlreadyFound = pKF->GetMapPoints();                     // :997
     const std::vector<MapPointT*> inKF = pKF->GetMapPointMatches();
     std::vector<uint8_t> slot(g.keys.size(), 0);
     for (size_t i = 0; i < inKF.size() && i < slot.size(); i++) slot[i] = !inKF[i] ? 0 : inKF[i]->isBad() ? 2 : 1;
-    PointGather pts(vpPoints, true);
+    PointGather pts = search_points(vpPoints);
+    pts.add_normals(vpPoints);
     for (int j = 0; j < M; j++) if (pts.usable[j] && spAlreadyFound.count(vpPoints[j])) pts.usable[j] = 0;
     float S[16];
-    scw_to_array(Scw, S);
+    mat_to_array(Scw, S);
     std::vector<int32_t> idx(M, -1), owner(M, -1);
     int32_t m = M, nFused = 0;
-    {
-        Runtime::Lane& L = loop_lane();
-        std::lock_guard<std::mutex> lk(L.mu);
-        if (!ok(planar_fuse_sim3(L.ctx, &g.view, S, slot.data(), pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), pts.xw.data(), pts.nrm.data(), pts.mn.data(),
-                                 pts.mx.data(), pts.desc.data(), th, idx.data(), owner.data(), &nFused), "planar_fuse_sim3"))
-            return 0;
-    }
+    if (!on_lane(TRACKING, "planar_fuse_sim3", [&](planar_ctx* ctx) {
+            return planar_fuse_sim3(ctx, &g.view, S, slot.data(), pKF->mfLogScaleFactor, pKF->mnScaleLevels, &m, M, 0, pts.usable.data(), pts.xw.data(), pts.nrm.data(),
+                                    pts.mn.data(), pts.mx.data(), pts.desc.data(), th, idx.data(), owner.data(), &nFused);
+        })) return 0;
     for (int j = 0; j < M; j++) {                                                       // :1086-1100, in the order of the points
         if (idx[j] < 0) continue;
         MapPointT* pMP = vpPoints[j];
@@ -1505,35 +1513,13 @@ inline int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoi
 #if defined(PLANAR_ADAPTERS_WITH_SIM3_OPT) || defined(PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
 namespace planar_adapter {
 
-struct Sim3OptSide {   // one key frame as planar_optimize_sim3 and planar_horn_ransac read it
-    int32_t n;
-    std::vector<planar_keypoint> keys;
-    std::vector<uint8_t> usable;
-    std::vector<float> xw;
-    float Tcw[16];
-    planar_frame_view view;
-    planar_kf_points kp;
+struct Sim3OptSide {   // one key frame as planar_optimize_sim3 and planar_horn_ransac read it: freely copyable, a copy's views point into the copy
+    ViewGather g;      // key points, [R | t], the camera of mK, the scale table over ones
+    PointGather p;     // slot i = the key frame's map point i: usable, xw
     template <class KeyFrameT, class MapPointT> Sim3OptSide(KeyFrameT* pKF, const std::vector<MapPointT*>& mps) {
-        n = (int32_t)pKF->mvKeysUn.size();
-        const size_t S = n > 0 ? (size_t)n : 1;
-        keys.resize(S); usable.assign(S, 0); xw.assign(S * 3, 0.f);
-        for (int i = 0; i < n; i++) {
-            std::memcpy(&keys[i], &pKF->mvKeysUn[i], sizeof(planar_keypoint));
-            MapPointT* p = (size_t)i < mps.size() ? mps[i] : NULL;
-            if (!p || p->isBad()) continue;
-            usable[i] = 1;
-            cv::Mat X = p->GetWorldPos();
-            for (int k = 0; k < 3; k++) xw[3 * i + k] = X.template at<float>(k);
-        }
-        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Tcw[4 * r + c] = R.template at<float>(r, c); Tcw[4 * r + 3] = t.template at<float>(r); }
-        Tcw[12] = Tcw[13] = Tcw[14] = 0.f; Tcw[15] = 1.f;
-        std::memset(&view, 0, sizeof(view)); std::memset(&kp, 0, sizeof(kp));
-        view.B = 1; view.stride = (int32_t)S; view.n = &n; view.keys_un = keys.data(); view.Tcw = Tcw;
-        view.fx = pKF->mK.template at<float>(0, 0); view.fy = pKF->mK.template at<float>(1, 1); view.cx = pKF->mK.template at<float>(0, 2); view.cy = pKF->mK.template at<float>(1, 2);
-        for (int l = 0; l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = 1.f;
-        for (size_t l = 0; l < pKF->mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) view.scale_factors[l] = pKF->mvScaleFactors[l];
-        kp.usable = usable.data(); kp.xw = xw.data();
+        g.add_keys(pKF->mvKeysUn, (int)pKF->mvKeysUn.size()).add_pose(pKF->GetRotation(), pKF->GetTranslation());
+        g.add_intrinsics_K(pKF->mK).add_scales(pKF->mvScaleFactors, true);
+        p.add_points(mps, (size_t)g.n, NoExclusion());
     }
 };
 
@@ -1547,26 +1533,16 @@ template <class KeyFrameT, class MapPointT, class Sim3T>
 int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, float th2, bool bFixScale) {
     const std::vector<MapPointT*> mps1 = pKF1->GetMapPointMatches(), mps2 = pKF2->GetMapPointMatches();
     Sim3OptSide s1(pKF1, mps1), s2(pKF2, mps2);
-    if (s1.n > PLANAR_MAX_FRAME_KEYS || s2.n > PLANAR_MAX_FRAME_KEYS) return 0;
-    const int N = (int)vpMatches1.size() < s1.n ? (int)vpMatches1.size() : s1.n;
-    const int32_t NOT_IN_KF2 = -2;                                                      // i2 < 0: skipped (:3807)
-    std::vector<int32_t> match((size_t)s1.view.stride, -1);
-    for (int i = 0; i < N; i++) {
-        if (!vpMatches1[i]) continue;
-        const int i2 = vpMatches1[i]->GetIndexInKeyFrame(pKF2);
-        // usable2 describes pKF2's own slot: the matched point itself must be the one that is not bad
-        match[i] = (i2 >= 0 && i2 < s2.n && !vpMatches1[i]->isBad()) ? i2 : NOT_IN_KF2;
-        if (match[i] >= 0) { s2.usable[i2] = 1; cv::Mat X = vpMatches1[i]->GetWorldPos(); for (int k = 0; k < 3; k++) s2.xw[3 * i2 + k] = X.template at<float>(k); }
-    }
+    if (s1.g.n > PLANAR_MAX_FRAME_KEYS || s2.g.n > PLANAR_MAX_FRAME_KEYS) return 0;
+    const int N = (int)vpMatches1.size() < s1.g.n ? (int)vpMatches1.size() : s1.g.n;
+    std::vector<int32_t> match = sim3_entry_matches(vpMatches1, s1.g.n, (size_t)s1.g.view.stride, pKF2, s2.g.n, s2.p);      // NOT_IN_KF2: skipped (:3807)
     const std::vector<int32_t> entry = match;
     double S[8];
     for (int k = 0; k < 8; k++) S[k] = g2oS12[k];
     int32_t nIn = 0;
-    {
-        Runtime::Lane& L = Runtime::get().lane(TRACKING);
-        std::lock_guard<std::mutex> g(L.mu);
-        if (!ok(planar_optimize_sim3(L.ctx, &s1.view, &s1.kp, &s2.view, &s2.kp, S, th2, bFixScale ? 1 : 0, match.data(), &nIn, NULL), "planar_optimize_sim3")) return 0;
-    }
+    if (!on_lane(TRACKING, "planar_optimize_sim3", [&](planar_ctx* ctx) {
+            return planar_optimize_sim3(ctx, &s1.g.view, &s1.p.kp, &s2.g.view, &s2.p.kp, S, th2, bFixScale ? 1 : 0, match.data(), &nIn, NULL);
+        })) return 0;
     for (int i = 0; i < N; i++) if (match[i] != entry[i]) vpMatches1[i] = static_cast<MapPointT*>(NULL);
     for (int k = 0; k < 8; k++) g2oS12[k] = S[k];      // untouched on the early return: the entry leaves S as it was
     return nIn;
@@ -1593,21 +1569,9 @@ namespace Planar_SLAM {
 class Sim3Solver {
 public:
     Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const bool bFixScale = true)
-        : mnIterations(0), mnBestInliers(0), mBestScale(0.f), mbFixScale(bFixScale), mSeed(0) {
-        mN1 = (int)vpMatched12.size();
-        mpSide1.reset(new planar_adapter::Sim3OptSide(pKF1, pKF1->GetMapPointMatches()));
-        mpSide2.reset(new planar_adapter::Sim3OptSide(pKF2, pKF2->GetMapPointMatches()));
-        planar_adapter::Sim3OptSide &s1 = *mpSide1, &s2 = *mpSide2;
-        const int N = mN1 < s1.n ? mN1 : s1.n;
-        const int32_t NOT_IN_KF2 = -2;                                                      // indexKF2 < 0: skipped (:82)
-        mvMatch.assign((size_t)s1.view.stride, -1);
-        for (int i = 0; i < N; i++) {
-            if (!vpMatched12[i]) continue;
-            const int i2 = vpMatched12[i]->GetIndexInKeyFrame(pKF2);
-            // usable2 describes pKF2's own slot: the matched point itself must be the one that is not bad, and its position the one that is read
-            mvMatch[i] = (i2 >= 0 && i2 < s2.n && !vpMatched12[i]->isBad()) ? i2 : NOT_IN_KF2;
-            if (mvMatch[i] >= 0) { s2.usable[i2] = 1; cv::Mat X = vpMatched12[i]->GetWorldPos(); for (int k = 0; k < 3; k++) s2.xw[3 * i2 + k] = X.at<float>(k); }
-        }
+        : mN1((int)vpMatched12.size()), mSide1(pKF1, pKF1->GetMapPointMatches()), mSide2(pKF2, pKF2->GetMapPointMatches()), mnIterations(0), mnBestInliers(0), mBestScale(0.f),
+          mbFixScale(bFixScale), mSeed(0) {
+        mvMatch = planar_adapter::sim3_entry_matches(vpMatched12, mSide1.g.n, (size_t)mSide1.g.view.stride, pKF2, mSide2.g.n, mSide2.p);      // NOT_IN_KF2: skipped (:82)
         for (int k = 0; k < 9; k++) mBestR[k] = 0.f;
         for (int k = 0; k < 3; k++) mBestt[k] = 0.f;
         SetRansacParameters();
@@ -1623,47 +1587,33 @@ public:
     }
     cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
         using namespace planar_adapter;
-        Sim3OptSide &s1 = *mpSide1, &s2 = *mpSide2;
+        Sim3OptSide &s1 = mSide1, &s2 = mSide2;
         bNoMore = true;
         vbInliers = std::vector<bool>(mN1, false);
         nInliers = 0;
-        if (s1.n > PLANAR_MAX_FRAME_KEYS || s2.n > PLANAR_MAX_FRAME_KEYS) return cv::Mat();
+        if (s1.g.n > PLANAR_MAX_FRAME_KEYS || s2.g.n > PLANAR_MAX_FRAME_KEYS) return cv::Mat();
         int32_t found = 0, no_more = 1, n_inl = 0;
-        std::vector<uint8_t> inl((size_t)s1.view.stride, 0);
+        std::vector<uint8_t> inl((size_t)s1.g.view.stride, 0);
         float R[9], t[3], s = 0.f;
-        {
-            Runtime::Lane& L = Runtime::get().lane(TRACKING);
-            std::lock_guard<std::mutex> g(L.mu);
-            if (!ok(planar_horn_ransac(L.ctx, &s1.view, &s1.kp, &s2.view, &s2.kp, mvMatch.data(), mRansacProb, mRansacMinInliers, mRansacMaxIts, mbFixScale ? 1 : 0,
-                                       nIterations, &mSeed, &mnIterations, &mnBestInliers, mBestR, mBestt, &mBestScale, &found, &no_more, &n_inl, inl.data(), R, t, &s,
-                                       NULL, NULL), "planar_horn_ransac")) return cv::Mat();
-        }
+        if (!on_lane(TRACKING, "planar_horn_ransac", [&](planar_ctx* ctx) {
+                return planar_horn_ransac(ctx, &s1.g.view, &s1.p.kp, &s2.g.view, &s2.p.kp, mvMatch.data(), mRansacProb, mRansacMinInliers, mRansacMaxIts, mbFixScale ? 1 : 0,
+                                          nIterations, &mSeed, &mnIterations, &mnBestInliers, mBestR, mBestt, &mBestScale, &found, &no_more, &n_inl, inl.data(), R, t, &s,
+                                          NULL, NULL);
+            })) return cv::Mat();
         bNoMore = no_more != 0;
         if (!found) return cv::Mat();
         nInliers = n_inl;
-        for (int i = 0; i < mN1 && i < s1.n; i++) vbInliers[i] = inl[i] != 0;
-        cv::Mat T(4, 4, CV_32F);                                                            // mBestT12: [s R | t]
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T.at<float>(r, c) = R[3 * r + c] * s; T.at<float>(r, 3) = t[r]; }
-        T.at<float>(3, 0) = T.at<float>(3, 1) = T.at<float>(3, 2) = 0.f; T.at<float>(3, 3) = 1.f;
-        return T;
+        for (int i = 0; i < mN1 && i < s1.g.n; i++) vbInliers[i] = inl[i] != 0;
+        const float T[16] = {R[0] * s, R[1] * s, R[2] * s, t[0], R[3] * s, R[4] * s, R[5] * s, t[1], R[6] * s, R[7] * s, R[8] * s, t[2], 0.f, 0.f, 0.f, 1.f};
+        return array_to_mat(T);                                                             // mBestT12: [s R | t]
     }
-    cv::Mat GetEstimatedRotation() {
-        if (mnIterations <= 0) return cv::Mat();                                            // mBestRotation is empty until an iteration has run
-        cv::Mat R(3, 3, CV_32F);
-        for (int k = 0; k < 9; k++) R.at<float>(k / 3, k % 3) = mBestR[k];
-        return R;
-    }
-    cv::Mat GetEstimatedTranslation() {
-        if (mnIterations <= 0) return cv::Mat();
-        cv::Mat t(3, 1, CV_32F);
-        for (int k = 0; k < 3; k++) t.at<float>(k, 0) = mBestt[k];
-        return t;
-    }
+    cv::Mat GetEstimatedRotation() { return mnIterations <= 0 ? cv::Mat() : planar_adapter::array_to_mat(mBestR, 3, 3); }   // empty until an iteration has run
+    cv::Mat GetEstimatedTranslation() { return mnIterations <= 0 ? cv::Mat() : planar_adapter::array_to_mat(mBestt, 3, 1); }
     float GetEstimatedScale() { return mBestScale; }
 
 protected:
     int mN1;
-    std::shared_ptr<planar_adapter::Sim3OptSide> mpSide1, mpSide2;                           // (shared: the views point into them, and the reference copies nothing here)
+    planar_adapter::Sim3OptSide mSide1, mSide2;                                              // (by value: a copied solver's views point into its own sides)
     std::vector<int32_t> mvMatch;
     int32_t mnIterations, mnBestInliers;
     float mBestR[9], mBestt[3], mBestScale;
@@ -1691,25 +1641,14 @@ class PnPsolver {
 public:
     PnPsolver(const Frame& F, const std::vector<MapPoint*>& vpMapPointMatches) : mnIterations(0), mnBestInliers(0), N(0), mSeed(0) {
         mnMatches = vpMapPointMatches.size();
-        mn = (int32_t)(mnMatches < F.mvKeysUn.size() ? mnMatches : F.mvKeysUn.size());
-        const size_t S = mn > 0 ? (size_t)mn : 1;
-        mvKeys.resize(S); mvUsable.assign(S, 0); mvXw.assign(S * 3, 0.f); mvMatch.assign(S, -1); mvbBestInliers.assign(S, 0);
-        for (int i = 0; i < mn; i++) {
-            std::memcpy(&mvKeys[i], &F.mvKeysUn[i], sizeof(planar_keypoint));
-            MapPoint* pMP = vpMapPointMatches[i];
-            if (!pMP) continue;
-            mvMatch[i] = i;
-            if (pMP->isBad()) continue;
-            mvUsable[i] = 1;
-            cv::Mat Pos = pMP->GetWorldPos();
-            for (int k = 0; k < 3; k++) mvXw[3 * i + k] = Pos.at<float>(k);
-            N++;
+        const int mn = (int)(mnMatches < F.mvKeysUn.size() ? mnMatches : F.mvKeysUn.size());
+        mView.add_keys(F.mvKeysUn, mn).add_intrinsics(F).add_scales(F.mvScaleFactors, true);
+        mPoints.add_points(vpMapPointMatches, (size_t)mn, planar_adapter::NoExclusion());
+        mvMatch.assign((size_t)mView.view.stride, -1); mvbBestInliers.assign((size_t)mView.view.stride, 0);
+        for (int i = 0; i < mn; i++) {                                                      // a bad point is matched (match = i) but not usable
+            if (vpMapPointMatches[i]) mvMatch[i] = i;
+            N += mPoints.usable[i];
         }
-        std::memset(&mView, 0, sizeof(mView));
-        mView.B = 1; mView.stride = (int32_t)S;
-        mView.fx = F.fx; mView.fy = F.fy; mView.cx = F.cx; mView.cy = F.cy;
-        for (int l = 0; l < PLANAR_MAX_LEVELS; l++) mView.scale_factors[l] = 1.f;
-        for (size_t l = 0; l < F.mvScaleFactors.size() && l < PLANAR_MAX_LEVELS; l++) mView.scale_factors[l] = F.mvScaleFactors[l];
         for (int k = 0; k < 16; k++) mBestTcw[k] = 0.f;
         SetRansacParameters();
     }
@@ -1740,36 +1679,30 @@ public:
         bNoMore = true;
         vbInliers.clear();
         nInliers = 0;
+        const int mn = mView.n;
         if (mn > PLANAR_MAX_FRAME_KEYS) return cv::Mat();
         int32_t found = 0, no_more = 1, n_inl = 0;
-        std::vector<uint8_t> inl((size_t)mView.stride, 0);
+        std::vector<uint8_t> inl((size_t)mView.view.stride, 0);
         float T[16];
-        mView.n = &mn; mView.keys_un = mvKeys.data();                                       // here, not in the constructor: the object may have been copied
-        {
-            Runtime::Lane& L = Runtime::get().lane(TRACKING);
-            std::lock_guard<std::mutex> g(L.mu);
-            if (!ok(planar_pnp_ransac(L.ctx, &mView, mvUsable.data(), mvXw.data(), mView.stride, mvMatch.data(), mRansacProb, mMinInliersGiven, mMaxItsGiven,
-                                      mRansacMinSet, mRansacEpsilon, mRansacTh, nIterations, &mSeed, &mnIterations, &mnBestInliers, mvbBestInliers.data(), mBestTcw,
-                                      &found, &no_more, &n_inl, inl.data(), T), "planar_pnp_ransac")) return cv::Mat();
-        }
+        if (!on_lane(TRACKING, "planar_pnp_ransac", [&](planar_ctx* ctx) {
+                return planar_pnp_ransac(ctx, &mView.view, mPoints.usable.data(), mPoints.xw.data(), mView.view.stride, mvMatch.data(), mRansacProb, mMinInliersGiven,
+                                         mMaxItsGiven, mRansacMinSet, mRansacEpsilon, mRansacTh, nIterations, &mSeed, &mnIterations, &mnBestInliers, mvbBestInliers.data(),
+                                         mBestTcw, &found, &no_more, &n_inl, inl.data(), T);
+            })) return cv::Mat();
         bNoMore = no_more != 0;
         if (!found) return cv::Mat();
         nInliers = n_inl;
         vbInliers = std::vector<bool>(mnMatches, false);
         for (int i = 0; i < mn; i++) vbInliers[i] = inl[i] != 0;
-        cv::Mat Tcw(4, 4, CV_32F);
-        for (int k = 0; k < 16; k++) Tcw.at<float>(k / 4, k % 4) = T[k];
-        return Tcw;
+        return array_to_mat(T);
     }
 
 protected:
     size_t mnMatches;
-    int32_t mn;
-    std::vector<planar_keypoint> mvKeys;
-    std::vector<uint8_t> mvUsable, mvbBestInliers;
-    std::vector<float> mvXw;
+    planar_adapter::ViewGather mView;                                                      // key points (mView.n of them), fx fy cx cy, the scale table over ones
+    planar_adapter::PointGather mPoints;                                                   // slot i = vpMapPointMatches[i]: usable, xw
+    std::vector<uint8_t> mvbBestInliers;
     std::vector<int32_t> mvMatch;
-    planar_frame_view mView;
     int32_t mnIterations, mnBestInliers;
     float mBestTcw[16];
     int N;

@@ -3,15 +3,11 @@
 // fixture generator's driver (tools/loop_match_golden/ref_loop_match_main.cpp; written by tests/loop_match_cases.py) and the same output blocks, so the result is
 // compared with tests/golden/loop_match_ref.npz.
 //   adapter_loop_match <bow|sim3|proj|fuse> <in.bin> <out.bin>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <map>
 #include <set>
 #include <string>
-#include <vector>
 
-#include "cvshim.hpp"
+#include "adapter_io.hpp"
 
 namespace Planar_SLAM {
 class KeyFrame;
@@ -64,29 +60,11 @@ protected:
 #include "planar_adapters.hpp"
 
 using namespace Planar_SLAM;
+using namespace adapter_io;
 
 namespace {
-struct Blocks {
-    std::vector<std::vector<uint8_t>> b;
-    size_t next = 0;
-    bool load(const char* path) {
-        FILE* f = std::fopen(path, "rb");
-        if (!f) return false;
-        int64_t n;
-        while (std::fread(&n, 8, 1, f) == 1) { b.emplace_back((size_t)n); if (n && std::fread(b.back().data(), 1, (size_t)n, f) != (size_t)n) return false; }
-        std::fclose(f);
-        return true;
-    }
-    template <typename T> const T* get(size_t* count = nullptr) { auto& v = b.at(next++); if (count) *count = v.size() / sizeof(T); return (const T*)v.data(); }
-};
-struct KP7 { float x, y, size, angle, response; int32_t octave, class_id; };
-cv::Mat mat_f32(int r, int c, const float* src) { cv::Mat m(r, c, CV_32F); std::memcpy(m.data, src, sizeof(float) * r * c); return m; }
-cv::Mat desc_mat(int n, const uint8_t* src) { cv::Mat m(n, 32, CV_8UC1); if (n) std::memcpy(m.data, src, (size_t)n * 32); return m; }
-void put(FILE* out, const void* p, size_t bytes) { int64_t nb = (int64_t)bytes; std::fwrite(&nb, 8, 1, out); if (bytes) std::fwrite(p, 1, bytes, out); }
-
 void set_view(KeyFrame& kf, const KP7* k, int N, const uint8_t* desc, const float* intr, const float* sf, size_t nl) {
-    kf.N = N; kf.mvKeysUn.resize(N); kf.mDescriptors = desc_mat(N, desc);
-    for (int i = 0; i < N; i++) kf.mvKeysUn[i] = cv::KeyPoint(k[i].x, k[i].y, k[i].size, k[i].angle, k[i].response, k[i].octave, k[i].class_id);
+    kf.N = N; to_keypoints(k, N, kf.mvKeysUn); kf.mDescriptors = desc_mat(N, desc);
     kf.mnMinX = intr[0]; kf.mnMaxX = intr[1]; kf.mnMinY = intr[2]; kf.mnMaxY = intr[3]; kf.mfGridElementWidthInv = intr[4]; kf.mfGridElementHeightInv = intr[5];
     kf.fx = intr[6]; kf.fy = intr[7]; kf.cx = intr[8]; kf.cy = intr[9]; kf.mfLogScaleFactor = intr[10];
     kf.mnScaleLevels = (int)nl; kf.mvScaleFactors.assign(sf, sf + nl);
@@ -137,7 +115,7 @@ int run_sim3(Blocks& in, FILE* out) {
         if (!p) continue;
         match[i] = p == &before[i] ? entry[i] : (int32_t)(p - mps2.data());
     }
-    put(out, match.data(), (size_t)N1 * 4); put(out, &nFound, 4);
+    write_block(out, match.data(), (size_t)N1); write_block(out, &nFound, 1);
     return 0;
 }
 
@@ -155,7 +133,7 @@ int run_bow(Blocks& in, FILE* out) {
         kf[s].N = N; kf[s].mvKeysUn.resize(N); kf[s].mDescriptors = desc_mat(N, desc);
         mps[s].assign(N, MapPoint()); kf[s].mps.assign(N, nullptr);
         for (int i = 0; i < N; i++) {
-            kf[s].mvKeysUn[i] = cv::KeyPoint(k[i].x, k[i].y, k[i].size, k[i].angle, k[i].response, k[i].octave, k[i].class_id);
+            kf[s].mvKeysUn[i] = to_keypoint(k[i]);
             if (node[i] >= 0) kf[s].mFeatVec[(unsigned)node[i]].push_back((unsigned)i);
             if (!usable[i] && !(i & 1)) continue;
             mps[s][i].bad = !usable[i];
@@ -167,7 +145,7 @@ int run_bow(Blocks& in, FILE* out) {
     const int nm = matcher.SearchByBoW(&kf[0], &kf[1], vpMatches12);
     std::vector<int32_t> match(kf[0].N, -1);
     for (int i = 0; i < kf[0].N && i < (int)vpMatches12.size(); i++) if (vpMatches12[i]) match[i] = (int32_t)(vpMatches12[i] - mps[1].data());
-    put(out, match.data(), match.size() * 4); put(out, &nm, 4);
+    write_block(out, match.data(), match.size()); write_block(out, &nm, 1);
     return 0;
 }
 
@@ -222,7 +200,7 @@ int run_proj(Blocks& in, FILE* out) {
     const int nm = matcher.SearchByProjection(&q.kf, q.Scw, q.vp, vpMatched, (int)q.th);
     std::vector<int32_t> match(q.N, -1);
     for (int i = 0; i < q.N; i++) if (!q.state[i] && vpMatched[i]) match[i] = (int32_t)(vpMatched[i] - q.pts.data());
-    put(out, match.data(), match.size() * 4); put(out, &nm, 4);
+    write_block(out, match.data(), match.size()); write_block(out, &nm, 1);
     return 0;
 }
 
@@ -253,7 +231,7 @@ int run_fuse(Blocks& in, FILE* out) {
         else rep[j] = -2 - (int32_t)(r - q.holders.data());
     }
     for (int i = 0; i < q.N; i++) if (!q.state[i] && q.kf.mps[i]) slots[i] = (int32_t)(q.kf.mps[i] - q.pts.data());
-    put(out, rep.data(), rep.size() * 4); put(out, added.data(), added.size() * 4); put(out, slots.data(), slots.size() * 4); put(out, &nFused, 4);
+    write_block(out, rep.data(), rep.size()); write_block(out, added.data(), added.size()); write_block(out, slots.data(), slots.size()); write_block(out, &nFused, 1);
     return 0;
 }
 }  // namespace

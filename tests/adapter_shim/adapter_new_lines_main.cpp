@@ -4,10 +4,9 @@
 // generator's driver (tools/new_lines_golden/ref_new_lines_main.cpp): mode 0 writes {n_new; (neighbour, idx1, idx2) triples; the six doubles per line}, mode 1
 // {match12 of the current key frame against neighbour 0; nmatches}.
 //   adapter_new_lines <in.bin> <out.bin>      in/out: sequences of blocks {int64 nbytes; bytes}
-#include <cstdio>
-#include <cstring>
 #include <memory>
-#include <vector>
+
+#include "adapter_io.hpp"
 
 namespace Planar_SLAM {
 // include/LSDmatcher.h:28, the one declaration the adapter defines here
@@ -22,6 +21,7 @@ public:
 #include "planar_adapters.hpp"
 
 using namespace Planar_SLAM;
+using namespace adapter_io;
 
 namespace {
 struct KeyFrameX : KeyFrame {
@@ -31,21 +31,6 @@ struct KeyFrameX : KeyFrame {
     cv::Mat Twc;
     cv::Mat GetPoseInverse() { return Twc.clone(); }
 };
-struct Blocks {
-    std::vector<std::vector<uint8_t>> b;
-    size_t next = 0;
-    bool load(const char* path) {
-        FILE* f = std::fopen(path, "rb");
-        if (!f) return false;
-        int64_t n;
-        while (std::fread(&n, 8, 1, f) == 1) { b.emplace_back((size_t)n); if (n && std::fread(b.back().data(), 1, (size_t)n, f) != (size_t)n) return false; }
-        std::fclose(f);
-        return true;
-    }
-    template <typename T> const T* get(size_t* count = nullptr) { auto& v = b.at(next++); if (count) *count = v.size() / sizeof(T); return (const T*)v.data(); }
-};
-void put(FILE* out, const void* p, size_t bytes) { int64_t nb = (int64_t)bytes; std::fwrite(&nb, 8, 1, out); if (bytes) std::fwrite(p, 1, bytes, out); }
-
 // cam = {fx, fy, cx, cy, invfx, invfy, mfScaleFactor, n_levels, scale_factors[16], level_sigma2[16]}
 std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vector<std::unique_ptr<MapLine>>& blockers) {
     static_assert(sizeof(cv::line_descriptor::KeyLine) == sizeof(planar_keyline), "KeyLine layout");
@@ -61,8 +46,7 @@ std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vect
     const int N = (int)n, L = (int)cam[7];
     kf->mvKeyLines.resize(N);
     if (N) std::memcpy((void*)kf->mvKeyLines.data(), kl, (size_t)N * sizeof(planar_keyline));
-    kf->mLineDescriptors = cv::Mat(N, 32, CV_8UC1);
-    if (N) std::memcpy(kf->mLineDescriptors.data, desc, (size_t)N * 32);
+    kf->mLineDescriptors = desc_mat(N, desc);
     kf->mvDepthLine.assign(dl, dl + N);
     kf->mvLines3D.resize(N);
     for (int i = 0; i < N; i++) for (int c = 0; c < 6; c++) kf->mvLines3D[i](c) = l3[6 * i + c];
@@ -73,8 +57,7 @@ std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vect
     kf->mvScaleFactors.assign(cam + 8, cam + 8 + L); kf->mvLevelSigma2.assign(cam + 24, cam + 24 + L);
     kf->mb = mb[0];
     // KeyFrame::SetPose (src/KeyFrame.cc:79-93): Rwc = Rcw.t(), Ow = -Rwc * tcw on cv::gemm's small-matrix path
-    kf->Tcw = cv::Mat(4, 4, CV_32F);
-    std::memcpy(kf->Tcw.data, Tcw, 64);
+    kf->Tcw = mat_f32(4, 4, Tcw);
     kf->Twc = cv::Mat::eye(4, 4, CV_32F);
     for (int i = 0; i < 3; i++) {
         float t = Tcw[i] * Tcw[3];
@@ -106,14 +89,14 @@ int main(int argc, char** argv) {
         std::vector<double> x;
         for (const auto& p : c) { tri.push_back(p.neighbour); tri.push_back(p.idx1); tri.push_back(p.idx2); for (int i = 0; i < 6; i++) x.push_back(p.line3D[i]); }
         const int32_t n = (int32_t)c.size();
-        put(out, &n, 4); put(out, tri.data(), tri.size() * 4); put(out, x.data(), x.size() * 8);
+        write_block(out, &n, 1); write_block(out, tri.data(), tri.size()); write_block(out, x.data(), x.size());
     } else {
         LSDmatcher matcher;
         std::vector<std::pair<size_t, size_t>> pairs;
         const int32_t nm = matcher.SearchForTriangulation(cur.get(), nb[0], pairs);
         std::vector<int32_t> m(cur->mvKeyLines.size(), -1);
         for (const auto& pr : pairs) m[pr.first] = (int32_t)pr.second;
-        put(out, m.data(), m.size() * 4); put(out, &nm, 4);
+        write_block(out, m.data(), m.size()); write_block(out, &nm, 1);
     }
     std::fclose(out);
     // an empty neighbour list creates nothing and touches no device

@@ -3,15 +3,15 @@
 // force-included) plus the members of include/KeyFrame.h the adapter reads and that stand-in lacks.  Same input blocks as the fixture generator's driver
 // (tools/new_points_golden/ref_new_points_main.cpp), same output: {n_new; (neighbour, idx1, idx2) triples; x3D}.
 //   adapter_new_points <in.bin> <out.bin>      in/out: sequences of blocks {int64 nbytes; bytes}
-#include <cstdio>
-#include <cstring>
 #include <memory>
-#include <vector>
+
+#include "adapter_io.hpp"
 
 #define PLANAR_ADAPTERS_WITH_NEW_POINTS
 #include "planar_adapters.hpp"
 
 using namespace Planar_SLAM;
+using namespace adapter_io;
 
 namespace {
 struct KeyFrameX : KeyFrame {
@@ -20,22 +20,6 @@ struct KeyFrameX : KeyFrame {
     cv::Mat Twc;
     cv::Mat GetPoseInverse() { return Twc.clone(); }
 };
-struct Blocks {
-    std::vector<std::vector<uint8_t>> b;
-    size_t next = 0;
-    bool load(const char* path) {
-        FILE* f = std::fopen(path, "rb");
-        if (!f) return false;
-        int64_t n;
-        while (std::fread(&n, 8, 1, f) == 1) { b.emplace_back((size_t)n); if (n && std::fread(b.back().data(), 1, (size_t)n, f) != (size_t)n) return false; }
-        std::fclose(f);
-        return true;
-    }
-    template <typename T> const T* get(size_t* count = nullptr) { auto& v = b.at(next++); if (count) *count = v.size() / sizeof(T); return (const T*)v.data(); }
-};
-struct KP7 { float x, y, size, angle, response; int32_t octave, class_id; };
-void put(FILE* out, const void* p, size_t bytes) { int64_t nb = (int64_t)bytes; std::fwrite(&nb, 8, 1, out); if (bytes) std::fwrite(p, 1, bytes, out); }
-
 // cam = {fx, fy, cx, cy, invfx, invfy, mfScaleFactor, n_levels, scale_factors[16], level_sigma2[16]}
 std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vector<std::unique_ptr<MapPoint>>& blockers) {
     std::unique_ptr<KeyFrameX> kf(new KeyFrameX);
@@ -51,14 +35,9 @@ std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vect
     const float* bb = in.get<float>();   // {mb, mbf}
     const int N = (int)n, L = (int)cam[7];
     kf->N = N;
-    kf->mvKeysUn.resize(N); kf->mvKeys.resize(N);
-    for (int i = 0; i < N; i++) {
-        kf->mvKeysUn[i] = cv::KeyPoint(ku[i].x, ku[i].y, ku[i].size, ku[i].angle, ku[i].response, ku[i].octave, ku[i].class_id);
-        kf->mvKeys[i] = cv::KeyPoint(kd[i].x, kd[i].y, kd[i].size, kd[i].angle, kd[i].response, kd[i].octave, kd[i].class_id);
-    }
+    to_keypoints(ku, N, kf->mvKeysUn); to_keypoints(kd, N, kf->mvKeys);
     kf->mvuRight.assign(ur, ur + N); kf->mvDepth.assign(depth, depth + N);
-    kf->mDescriptors = cv::Mat(N, 32, CV_8UC1);
-    if (N) std::memcpy(kf->mDescriptors.data, desc, (size_t)N * 32);
+    kf->mDescriptors = desc_mat(N, desc);
     for (int i = 0; i < N; i++) if (node[i] >= 0) kf->mFeatVec.addFeature((DBoW2::NodeId)node[i], (unsigned)i);
     kf->mps.assign(N, nullptr);
     for (int i = 0; i < N; i++) if (occ[i]) { blockers.emplace_back(new MapPoint); kf->mps[i] = blockers.back().get(); }
@@ -67,8 +46,7 @@ std::unique_ptr<KeyFrameX> read_keyframe(Blocks& in, const float* cam, std::vect
     kf->mvScaleFactors.assign(cam + 8, cam + 8 + L); kf->mvLevelSigma2.assign(cam + 24, cam + 24 + L);
     kf->mb = bb[0]; kf->mbf = bb[1];
     // KeyFrame::SetPose (src/KeyFrame.cc:79-93): Rwc = Rcw.t(), Ow = -Rwc * tcw on cv::gemm's small-matrix path
-    kf->Tcw = cv::Mat(4, 4, CV_32F);
-    std::memcpy(kf->Tcw.data, Tcw, 64);
+    kf->Tcw = mat_f32(4, 4, Tcw);
     kf->Twc = cv::Mat::eye(4, 4, CV_32F);
     for (int i = 0; i < 3; i++) {
         float t = Tcw[i] * Tcw[3];
@@ -99,7 +77,7 @@ int main(int argc, char** argv) {
     std::vector<float> x;
     for (const auto& p : c) { tri.push_back(p.neighbour); tri.push_back(p.idx1); tri.push_back(p.idx2); for (int i = 0; i < 3; i++) x.push_back(p.x3D[i]); }
     const int32_t n = (int32_t)c.size();
-    put(out, &n, 4); put(out, tri.data(), tri.size() * 4); put(out, x.data(), x.size() * 4);
+    write_block(out, &n, 1); write_block(out, tri.data(), tri.size()); write_block(out, x.data(), x.size());
     std::fclose(out);
     // an empty neighbour list creates nothing and touches no device
     return planar_adapter::CreateNewMapPoints(cur.get(), std::vector<KeyFrameX*>()).empty() ? 0 : 3;

@@ -5,12 +5,7 @@
 //   a call of 0 iterations goes through find(), which reports no bNoMore: -1 is written for it
 //   out: blocks: i32[ncalls][3] = a matrix was returned, bNoMore, nInliers;  vbInliers u8[ncalls][n] (zero where the vector came back empty);  the returned 4x4 matrix
 //        f32[ncalls][16] (zero when empty)
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-#include "cvshim.hpp"
+#include "adapter_io.hpp"
 
 namespace Planar_SLAM {
 class MapPoint {
@@ -35,25 +30,12 @@ float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
 
 using namespace Planar_SLAM;
 
-namespace {
-struct KP7 { float x, y, size, angle, response; int32_t octave, class_id; };
-typedef std::vector<std::vector<uint8_t>> Blocks;
-bool load(const char* path, Blocks& b) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    int64_t n;
-    while (std::fread(&n, 8, 1, f) == 1) { b.emplace_back((size_t)n); if (n && std::fread(b.back().data(), 1, (size_t)n, f) != (size_t)n) return false; }
-    std::fclose(f);
-    return true;
-}
-template <class T> void write_block(FILE* f, const T* p, size_t n) { const int64_t k = (int64_t)(n * sizeof(T)); std::fwrite(&k, 8, 1, f); if (n) std::fwrite(p, sizeof(T), n, f); }
-cv::Mat mat_f32(int r, int c, const float* p) { cv::Mat m(r, c, CV_32F); std::memcpy(m.data, p, sizeof(float) * r * c); return m; }
-}  // namespace
+using namespace adapter_io;
 
 int main(int argc, char** argv) {
     if (argc != 3) { std::fprintf(stderr, "usage: %s in.bin out.bin\n", argv[0]); return 2; }
     Blocks bl;
-    if (!load(argv[1], bl) || bl.size() != 7) { std::fprintf(stderr, "cannot read 7 blocks from %s\n", argv[1]); return 2; }
+    if (!bl.load(argv[1]) || bl.size() != 7) { std::fprintf(stderr, "cannot read 7 blocks from %s\n", argv[1]); return 2; }
     const double* prm = (const double*)bl[0].data();
     const int ncalls = (int)prm[7];
     const float* K = (const float*)bl[1].data();
@@ -69,11 +51,7 @@ int main(int argc, char** argv) {
     Frame::fx = K[0]; Frame::fy = K[1]; Frame::cx = K[2]; Frame::cy = K[3];
     F.mvScaleFactors.assign(sf, sf + bl[2].size() / 4);
     for (float s : F.mvScaleFactors) F.mvLevelSigma2.push_back(s * s);
-    F.mvKeysUn.resize(n); F.mvpMapPoints.assign(n, nullptr);
-    for (int i = 0; i < n; i++) {
-        F.mvKeysUn[i].pt.x = keys[i].x; F.mvKeysUn[i].pt.y = keys[i].y; F.mvKeysUn[i].size = keys[i].size; F.mvKeysUn[i].angle = keys[i].angle;
-        F.mvKeysUn[i].response = keys[i].response; F.mvKeysUn[i].octave = keys[i].octave; F.mvKeysUn[i].class_id = keys[i].class_id;
-    }
+    to_keypoints(keys, n, F.mvKeysUn); F.mvpMapPoints.assign(n, nullptr);
     std::vector<MapPoint> pts(kf_n);
     for (int j = 0; j < kf_n; j++) { pts[j].pos = mat_f32(3, 1, kf_xw + 3 * j); pts[j].bad = !kf_usable[j]; }
     std::vector<MapPoint*> vp(n, nullptr);

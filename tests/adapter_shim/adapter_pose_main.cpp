@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "Optimizer.h"
+#include "adapter_io.hpp"
 
 using namespace Planar_SLAM;
 
@@ -28,7 +29,7 @@ struct Reader {
     template <typename T> const T* arr(size_t n) { const T* p = (const T*)&buf[off]; off += n * sizeof(T); return p; }
 };
 
-static cv::Mat mat_f32(int r, int c, const float* src) { cv::Mat m(r, c, CV_32F); std::memcpy(m.data, src, sizeof(float) * r * c); return m; }
+using adapter_io::mat_f32;
 
 int main(int argc, char** argv) {
     if (argc != 4 || std::string(argv[1]) != "pose") { std::fprintf(stderr, "usage: adapter_pose pose <in> <out>\n"); return 2; }

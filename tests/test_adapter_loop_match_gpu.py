@@ -7,18 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import adapter_build as AB
 import loop_match_cases as LC
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "adapter_shim")
-
 
 def build_command(out):
-    lib = os.path.join(ROOT, "planarslam_amd", "libplanar_hip.so")
-    return ["g++", "-O1", "-std=c++14", "-w", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "shim"), "-o", out,
-            os.path.join(SHIM, "adapter_loop_match_main.cpp"), os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib",
-            "-Wl,-rpath,/opt/rocm/lib"]
+    return AB.build_command(out, [AB.shim_source("adapter_loop_match_main.cpp")])
 
 
 @pytest.fixture(scope="module")

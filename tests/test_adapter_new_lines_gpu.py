@@ -8,19 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import adapter_build as AB
 import new_lines_cases as LC
 from new_lines_host import golden, golden_create
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "adapter_shim")
 
 
 def build_command(out):
-    lib = os.path.join(ROOT, "planarslam_amd", "libplanar_hip.so")
-    return ["g++", "-O1", "-std=c++14", "-w", "-pthread", "-DCVSHIM_ALGEBRA", "-I" + SHIM, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "shim"),
-            "-DSTANDINS_NO_REFERENCE", "-include", os.path.join(ROOT, "oracle", "shim", "match_standins.hpp"), "-o", out, os.path.join(SHIM, "adapter_new_lines_main.cpp"),
-            os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
+    return AB.build_command(out, [AB.shim_source("adapter_new_lines_main.cpp")], algebra=True, shim="first", standins="match")
 
 
 @pytest.fixture(scope="module")

@@ -51,10 +51,9 @@ int main(int argc, char** argv) {
     return 0;
 }
 ''')
-    lib = os.path.join(ROOT, "planarslam_amd", "libplanar_hip.so")
+    from adapter_build import build_command
     exe = str(tmp_path / "table")
-    subprocess.check_call(["g++", "-O1", "-std=c++14", "-w", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "shim"), "-o", exe, str(src),
-                           os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    subprocess.check_call(build_command(exe, [str(src)]))
     H = PC.load_host()
     for params in (PC.RELOC, (0.99, 10, 300, 4, 0.3, 5.991), (0.99, 8, 300, 4, 0.4, 5.991)):
         out = subprocess.check_output([exe, repr(params[0]), str(params[1]), str(params[2]), repr(params[4])], text=True).split()

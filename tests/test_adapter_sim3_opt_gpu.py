@@ -7,19 +7,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import adapter_build as AB
 import loop_match_cases as LC
 import sim3_opt_cases as SC
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "adapter_shim")
 
 
 def build_command(out):
-    lib = os.path.join(ROOT, "planarslam_amd", "libplanar_hip.so")
-    return ["g++", "-O1", "-std=c++14", "-w", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "shim"), "-I" + SHIM, "-o", out,
-            os.path.join(SHIM, "adapter_sim3_opt_main.cpp"), os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib",
-            "-Wl,-rpath,/opt/rocm/lib"]
+    return AB.build_command(out, [AB.shim_source("adapter_sim3_opt_main.cpp")], shim="last")
 
 
 @pytest.fixture(scope="module")

@@ -5,6 +5,8 @@ import os
 import subprocess
 import tempfile
 
+from adapter_build import build_command
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SRC = r'''
@@ -38,7 +40,5 @@ def test_adapters_compile_and_link():
         src = os.path.join(d, "t.cpp")
         open(src, "w").write(SRC)
         exe = os.path.join(d, "t")
-        subprocess.check_call(["g++", "-std=c++14", "-w", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "shim"),
-                               src, os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib),
-                               "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+        subprocess.check_call(build_command(exe, [src], plain=True))
         subprocess.check_call([exe])

@@ -21,6 +21,7 @@ import pytest
 
 import opt_cases as cases
 import oracle_lib as O
+from adapter_build import build_command
 from planarslam_amd import synth
 from planarslam_amd.synth import TUM3
 from test_oracle_opt_ref import golden_pose
@@ -31,16 +32,8 @@ SHIM = os.path.join(ROOT, "tests", "adapter_shim")
 
 
 def _build(tmp, name, sources, standins="match"):
-    lib = os.path.join(ROOT, "planarslam_amd", "libplanar_hip.so")
     exe = os.path.join(tmp, name)
-    cmd = ["g++", "-O1", "-std=c++14", "-w", "-pthread", "-DCVSHIM_ALGEBRA", "-I" + SHIM, "-I" + os.path.join(ROOT, "include")]
-    if standins == "opt":        # the optimiser stand-ins use the mini-Eigen (must precede oracle/shim, whose <Eigen/Core> is the 3-type stub)
-        cmd += ["-I" + os.path.join(ROOT, "oracle"), "-I" + os.path.join(ROOT, "oracle", "shim", "minieigen")]
-    cmd += ["-I" + os.path.join(ROOT, "oracle", "shim")]
-    if standins:
-        cmd += ["-DSTANDINS_NO_REFERENCE", "-include", os.path.join(ROOT, "oracle", "shim", standins + "_standins.hpp")]
-    cmd += ["-o", exe] + sources + [os.path.join(ROOT, "oracle", "cvprim.cpp"), lib, "-Wl,-rpath," + os.path.dirname(lib), "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.check_call(cmd)
+    subprocess.check_call(build_command(exe, sources, algebra=True, shim="first", standins=standins))
     return exe
 
 
