@@ -624,6 +624,56 @@ int planar_optimize_sim3(planar_ctx* ctx, const planar_frame_view* kf1, const pl
 int planar_optimize_sim3_dev(planar_ctx* ctx, const planar_frame_view* d_kf1, const planar_kf_points* d_mp1, const planar_frame_view* d_kf2,
                              const planar_kf_points* d_mp2, double* d_S12, float th2, int fix_scale, int32_t* d_match12, int32_t* d_n_inliers, int32_t* d_lm_iters);
 
+/* Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) (src/Optimizer.cc:2680-2991, called from
+ * LoopClosing::CorrectLoop, src/LoopClosing.cc:567), batched over B independent pose graphs with ragged sizes: one VertexSim3Expmap per key frame (array index =
+ * rank of mnId), an EdgeSim3 with identity information and g2o's numeric Jacobians per edge, BlockSolver_7_3 + Levenberg with setUserLambdaInit(1e-16), then the
+ * SE3 recovery and the correction of points, lines and planes.  The system (7 rows per free key frame) is factored on the device in tiles of 8 key frames.
+ *   g: the graphs (below).  Arrays are [B][stride] rows; what lies beyond a graph's count is not read, and the matching output rows are not written.
+ *   fix_scale, iterations: bFixScale and the argument of optimize() (the reference passes 20), 0 <= iterations <= PLANAR_ESSGRAPH_MAX_ITERATIONS.
+ *   sim3_out [B][kf_stride][8] (double): the optimised vertex estimates Siw in g2o::Sim3::operator[] order (quaternion x y z w, t, s).
+ *   poses_out [B][kf_stride][16] (float): Tiw = [R | t / s], what SetPose receives.
+ *   points_out / lines_out / planes_out: the corrected landmarks in the layout of their inputs, correctedSwr.map(Srw.map(P)) in double for points and for both end
+ *       points of a line, the float cv::Mat algebra with its two d < 0 sign flips for planes.  May be NULL where the input array is NULL.
+ *   info [B][5] (double): Levenberg iterations run, trials, final chi2, final lambda, status (PLANAR_ESSGRAPH_*).
+ * UpdateNormalAndDepth, ComputeDistinctiveDescriptors, UpdateAverageDir and UpdateCoefficientsAndPoints stay with the caller, as does every map edit of CorrectLoop.
+ * Preconditions taken from the reference: no bad key frame among the inputs (the reference dereferences a null vertex there), landmarks not bad.
+ * Launch budget: iterations + PLANAR_ESSGRAPH_EXTRA_TRIALS trial slots are enqueued with no host decision between them; an iteration costs one and so does each
+ * rejected trial.  A graph whose protocol has not ended by then reports PLANAR_ESSGRAPH_RUNNING and the estimates of its last accepted trial.
+ * PLANAR_EINVAL (nothing written): a null required argument, B < 1, kf_stride outside [1, PLANAR_ESSGRAPH_MAX_KF], edge_stride < 1, a Sim3 array without its mask,
+ * a landmark array without its count, references, stride or output, iterations out of range; and, in the host flavour, n_kf[b] outside [1, kf_stride], n_edges[b]
+ * outside [0, edge_stride], a fixed index outside [0, n_kf), an edge naming a vertex outside [0, n_kf) or the same vertex twice, a landmark count beyond its stride
+ * or a reference key frame outside [0, n_kf).  The _dev flavour cannot read those without a copy: such a graph gets status PLANAR_ESSGRAPH_INVALID and no other
+ * output, the other graphs of the batch run, and a landmark with a reference out of range is left unwritten. */
+#define PLANAR_ESSGRAPH_MAX_KF 256          /* key frames per graph */
+#define PLANAR_ESSGRAPH_MAX_ITERATIONS 100
+#define PLANAR_ESSGRAPH_EXTRA_TRIALS 20     /* trial slots beyond one per iteration */
+#define PLANAR_ESSGRAPH_LOOP 0              /* edge kind: loop connection (:2748-2774), both measurement ends from the start estimates */
+#define PLANAR_ESSGRAPH_NORMAL 1            /* edge kind: spanning tree, old loop edge, covisibility (:2777-2866), each end from noncorrected where present */
+#define PLANAR_ESSGRAPH_RUNNING 0           /* status: the launch budget ran out first */
+#define PLANAR_ESSGRAPH_MAX_ITERATIONS_RUN 1 /* status: optimize() ran all its iterations */
+#define PLANAR_ESSGRAPH_TERMINATED 2        /* status: ten rejected trials, rho == 0 or the _nBad >= 3 stop */
+#define PLANAR_ESSGRAPH_NOTHING 3           /* status: no free vertex or no edge */
+#define PLANAR_ESSGRAPH_INVALID (-1)        /* status (_dev flavour): see PLANAR_EINVAL above */
+typedef struct planar_essgraph {
+    int32_t B, kf_stride, edge_stride, point_stride, line_stride, plane_stride;
+    const int32_t* n_kf;               /* [B] */
+    const float* poses;                /* [B][kf_stride][16] Tcw of GetPose(), row-major */
+    const double* corrected;           /* [B][kf_stride][8] CorrectedSim3 in g2o::Sim3::operator[] order, or NULL */
+    const uint8_t* corrected_mask;     /* [B][kf_stride] non-zero where the key frame is in CorrectedSim3 */
+    const double* noncorrected;        /* NonCorrectedSim3, the same way, or NULL */
+    const uint8_t* noncorrected_mask;
+    const int32_t* fixed;              /* [B] index of pLoopKF */
+    const int32_t* n_edges;            /* [B] */
+    const int32_t* edges;              /* [B][edge_stride][3]: vertex 0, vertex 1, kind; planar_adapter::essential_graph_edges (planar_adapters.hpp) builds the reference's list */
+    const int32_t* n_points;  const float* points;  const int32_t* point_ref;   /* [B], [B][point_stride][3], [B][point_stride] reference key-frame index; or NULL */
+    const int32_t* n_lines;   const double* lines;  const int32_t* line_ref;    /* [B][line_stride][6] start and end point */
+    const int32_t* n_planes;  const float* planes;  const int32_t* plane_ref;   /* [B][plane_stride][4] */
+} planar_essgraph;
+int planar_optimize_essential_graph(planar_ctx* ctx, const planar_essgraph* g, int fix_scale, int iterations, double* sim3_out, float* poses_out, float* points_out,
+                                    double* lines_out, float* planes_out, double* info);
+int planar_optimize_essential_graph_dev(planar_ctx* ctx, const planar_essgraph* d_g, int fix_scale, int iterations, double* d_sim3_out, float* d_poses_out,
+                                        float* d_points_out, double* d_lines_out, float* d_planes_out, double* d_info);
+
 /* Sim3Solver (src/Sim3Solver.cc), batched over B independent key-frame pairs: step 2 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:274-301), between
  * planar_search_by_bow_kf and planar_search_by_sim3 and on the views of the latter, so the calls chain on the device.  Each pair has the semantics of one
  * Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale), SetRansacParameters(prob, min_inliers, max_its) and ONE iterate(n_iterations, bNoMore, vbInliers, nInliers); the

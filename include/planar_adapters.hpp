@@ -12,6 +12,7 @@
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
 //   Planar_SLAM::PnPsolver  <- include/PnPsolver.h, src/PnPsolver.cc                                    (PLANAR_ADAPTERS_WITH_PNP_SOLVER)
+//   Optimizer::OptimizeEssentialGraph                                                                 (PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1714,3 +1715,174 @@ protected:
 
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_PNP_SOLVER
+
+
+// ---- Optimizer::OptimizeEssentialGraph: the DEFINITION of the static member with the reference's signature
+//          void OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+//                                      const LoopClosing::KeyFrameAndPose& CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>>& LoopConnections,
+//                                      const bool& bFixScale)                                                                       src/Optimizer.cc:2680-2991
+//      Enabled with PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH, after the reference's Optimizer.h, LoopClosing.h, Map.h, KeyFrame.h, MapPoint.h, MapLine.h and MapPlane.h;
+//      leave that body of src/Optimizer.cc out.  The key frames of Map::GetAllKeyFrames() are numbered by the rank of their mnId; essential_graph_edges applies the
+//      reference's selection rules to plain arrays (so they can be tested without a KeyFrame); planar_optimize_essential_graph runs with B = 1 on the tracking
+//      context; SetPose, then SetWorldPos of points, lines and planes follow in the reference's order with its UpdateNormalAndDepth /
+//      ComputeDistinctiveDescriptors / UpdateAverageDir / UpdateCoefficientsAndPoints calls.  A failing call, or a map of more than PLANAR_ESSGRAPH_MAX_KF key
+//      frames, changes nothing.  Precondition (the reference's own): no bad key frame in GetAllKeyFrames().
+#ifdef PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH
+#include <algorithm>
+#include <set>
+namespace planar_adapter {
+
+// A list per key frame: item k of key frame i is idx[off[i] + k] (and weight[off[i] + k] where the list has weights); off has n + 1 entries.
+struct EssGraphLists { const int32_t* off; const int32_t* idx; const int32_t* weight; };
+
+// The edge list of OptimizeEssentialGraph over key frames 0 .. n - 1 in mnId order -> (vertex 0, vertex 1, kind) triples in the reference's order of insertion.
+//   parent[i]: index of GetParent() or -1.            loop_edges: GetLoopEdges() of i (no weights).
+//   covisible: GetVectorCovisibleKeyFrames() of i in its order, with GetWeight(); the function applies minFeat = 100 as GetCovisiblesByWeight(minFeat) does.
+//   loop_connections: LoopConnections[i] with pKF->GetWeight(connection) as weight; a key frame without an entry has an empty list.
+// std::set<KeyFrame*> iterates in pointer order, which no array can carry: lists are taken in the order given.  That order only decides the order of the sums.
+inline std::vector<int32_t> essential_graph_edges(int n, const int32_t* parent, const EssGraphLists& loop_edges, const EssGraphLists& covisible,
+                                                  const EssGraphLists& loop_connections, int cur, int loop) {
+    const int minFeat = 100;                                                                                   // :2707
+    std::vector<int32_t> e;
+    std::set<std::pair<int, int> > inserted;                                                                   // sInsertedEdges
+    auto add = [&](int v0, int v1, int kind) { e.push_back(v0); e.push_back(v1); e.push_back(kind); };
+    for (int i = 0; i < n; i++)                                                                                // loop connections (:2748-2774)
+        for (int k = loop_connections.off[i]; k < loop_connections.off[i + 1]; k++) {
+            const int j = loop_connections.idx[k];
+            if ((i != cur || j != loop) && loop_connections.weight[k] < minFeat) continue;                     // the (current, loop) exemption (:2757)
+            add(i, j, PLANAR_ESSGRAPH_LOOP);
+            inserted.insert(std::make_pair(std::min(i, j), std::max(i, j)));
+        }
+    for (int i = 0; i < n; i++) {                                                                              // normal edges (:2777-2866)
+        if (parent[i] >= 0) add(i, parent[i], PLANAR_ESSGRAPH_NORMAL);                                         // spanning tree (:2792-2813): no exclusion applies
+        auto is_loop_edge = [&](int j) { for (int k = loop_edges.off[i]; k < loop_edges.off[i + 1]; k++) if (loop_edges.idx[k] == j) return true; return false; };
+        for (int k = loop_edges.off[i]; k < loop_edges.off[i + 1]; k++)                                        // old loop edges towards lower ids (:2816-2836)
+            if (loop_edges.idx[k] < i) add(i, loop_edges.idx[k], PLANAR_ESSGRAPH_NORMAL);
+        for (int k = covisible.off[i]; k < covisible.off[i + 1]; k++) {                                        // covisibility (:2839-2865)
+            const int j = covisible.idx[k];
+            if (covisible.weight[k] < minFeat) continue;                                                       // GetCovisiblesByWeight(minFeat)
+            if (j == parent[i] || parent[j] == i || is_loop_edge(j)) continue;                                 // != pParentKF, !hasChild, !sLoopEdges.count (:2841)
+            if (!(j < i)) continue;                                                                            // mnId ordering (:2842)
+            if (inserted.count(std::make_pair(std::min(i, j), std::max(i, j)))) continue;                      // :2843
+            add(i, j, PLANAR_ESSGRAPH_NORMAL);
+        }
+    }
+    return e;
+}
+
+template <class MapT, class KeyFrameT, class PoseMapT, class ConnMapT>
+void OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const PoseMapT& NonCorrectedSim3, const PoseMapT& CorrectedSim3,
+                            const ConnMapT& LoopConnections, bool bFixScale) {
+    std::vector<KeyFrameT*> vpKFs = pMap->GetAllKeyFrames();
+    const auto vpMPs = pMap->GetAllMapPoints();
+    const auto vpMLs = pMap->GetAllMapLines();
+    const auto vpMPLs = pMap->GetAllMapPlanes();
+    const int n = (int)vpKFs.size();
+    if (n < 1 || n > PLANAR_ESSGRAPH_MAX_KF) { std::fprintf(stderr, "planar (OptimizeEssentialGraph): %d key frames, 1 .. %d supported - nothing optimised\n", n, PLANAR_ESSGRAPH_MAX_KF); return; }
+    std::vector<KeyFrameT*> order = vpKFs;
+    std::sort(order.begin(), order.end(), [](KeyFrameT* a, KeyFrameT* b) { return a->mnId < b->mnId; });
+    std::map<KeyFrameT*, int> index;
+    std::map<unsigned long, int> index_of_id;
+    for (int i = 0; i < n; i++) { index[order[i]] = i; index_of_id[order[i]->mnId] = i; }
+    auto at = [&](KeyFrameT* k) { auto it = index.find(k); return it == index.end() ? -1 : it->second; };
+    if (at(pLoopKF) < 0 || at(pCurKF) < 0) return;
+    std::vector<float> poses(16 * (size_t)n);
+    std::vector<double> corr(8 * (size_t)n, 0.0), nc(8 * (size_t)n, 0.0);
+    std::vector<uint8_t> cm(n, 0), nm(n, 0);
+    std::vector<int32_t> parent(n, -1), le_off(1, 0), le_idx, cv_off(1, 0), cv_idx, cv_w, lc_off(1, 0), lc_idx, lc_w;
+    for (int i = 0; i < n; i++) {
+        KeyFrameT* pKF = order[i];
+        mat_to_array(pKF->GetPose(), &poses[16 * (size_t)i]);
+        auto ic = CorrectedSim3.find(pKF);
+        if (ic != CorrectedSim3.end()) { cm[i] = 1; for (int k = 0; k < 8; k++) corr[8 * (size_t)i + k] = ic->second[k]; }
+        auto in = NonCorrectedSim3.find(pKF);
+        if (in != NonCorrectedSim3.end()) { nm[i] = 1; for (int k = 0; k < 8; k++) nc[8 * (size_t)i + k] = in->second[k]; }
+        KeyFrameT* par = pKF->GetParent();
+        parent[i] = par ? at(par) : -1;
+        for (KeyFrameT* l : pKF->GetLoopEdges()) if (at(l) >= 0) le_idx.push_back(at(l));
+        le_off.push_back((int32_t)le_idx.size());
+        for (KeyFrameT* c : pKF->GetCovisiblesByWeight(100)) if (c && at(c) >= 0 && !c->isBad()) { cv_idx.push_back(at(c)); cv_w.push_back(100); }   // the list is already cut at minFeat
+        cv_off.push_back((int32_t)cv_idx.size());
+        auto il = LoopConnections.find(pKF);
+        if (il != LoopConnections.end()) for (KeyFrameT* c : il->second) if (at(c) >= 0) { lc_idx.push_back(at(c)); lc_w.push_back(pKF->GetWeight(c)); }
+        lc_off.push_back((int32_t)lc_idx.size());
+    }
+    const int cur = at(pCurKF), loop = at(pLoopKF);
+    std::vector<int32_t> edges = essential_graph_edges(n, parent.data(), EssGraphLists{le_off.data(), le_idx.data(), NULL}, EssGraphLists{cv_off.data(), cv_idx.data(), cv_w.data()},
+                                                       EssGraphLists{lc_off.data(), lc_idx.data(), lc_w.data()}, cur, loop);
+    // landmarks that are not bad, with the reference key frame of :2897-2903
+    auto ref_of = [&](unsigned long by, unsigned long ref, KeyFrameT* rk) {
+        const unsigned long id = by == pCurKF->mnId ? ref : rk->mnId;
+        auto it = index_of_id.find(id);
+        return it == index_of_id.end() ? -1 : it->second;
+    };
+    std::vector<float> pts, pls; std::vector<double> lns; std::vector<int32_t> pt_ref, ln_ref, pl_ref;
+    std::vector<size_t> pt_of, ln_of, pl_of;
+    bool refs_ok = true;
+    for (size_t i = 0; i < vpMPs.size(); i++) {
+        auto* p = vpMPs[i];
+        if (p->isBad()) continue;
+        const int r = ref_of(p->mnCorrectedByKF, p->mnCorrectedReference, p->mnCorrectedByKF == pCurKF->mnId ? (KeyFrameT*)NULL : p->GetReferenceKeyFrame());
+        refs_ok = refs_ok && r >= 0;
+        const cv::Mat P = p->GetWorldPos();
+        for (int k = 0; k < 3; k++) pts.push_back(P.at<float>(k));
+        pt_ref.push_back(r); pt_of.push_back(i);
+    }
+    for (size_t i = 0; i < vpMLs.size(); i++) {
+        auto* p = vpMLs[i];
+        if (p->isBad()) continue;
+        const int r = ref_of(p->mnCorrectedByKF, p->mnCorrectedReference, p->mnCorrectedByKF == pCurKF->mnId ? (KeyFrameT*)NULL : p->GetReferenceKeyFrame());
+        refs_ok = refs_ok && r >= 0;
+        const auto P = p->GetWorldPos();
+        for (int k = 0; k < 6; k++) lns.push_back(P(k));
+        ln_ref.push_back(r); ln_of.push_back(i);
+    }
+    for (size_t i = 0; i < vpMPLs.size(); i++) {
+        auto* p = vpMPLs[i];
+        if (p->isBad()) continue;
+        const int r = ref_of(p->mnCorrectedByKF, p->mnCorrectedReference, p->mnCorrectedByKF == pCurKF->mnId ? (KeyFrameT*)NULL : p->GetReferenceKeyFrame());
+        refs_ok = refs_ok && r >= 0;
+        const cv::Mat P = p->GetWorldPos();
+        for (int k = 0; k < 4; k++) pls.push_back(P.at<float>(k));
+        pl_ref.push_back(r); pl_of.push_back(i);
+    }
+    if (!refs_ok) { std::fprintf(stderr, "planar (OptimizeEssentialGraph): a landmark's reference key frame is not in the map - nothing optimised\n"); return; }
+    const int32_t n_kf = n, n_e = (int32_t)(edges.size() / 3), n_pt = (int32_t)pt_ref.size(), n_ln = (int32_t)ln_ref.size(), n_pl = (int32_t)pl_ref.size();
+    if (edges.empty()) edges.resize(3, 0);
+    planar_essgraph g;
+    std::memset(&g, 0, sizeof g);
+    g.B = 1; g.kf_stride = n; g.edge_stride = n_e > 0 ? n_e : 1; g.point_stride = n_pt; g.line_stride = n_ln; g.plane_stride = n_pl;
+    g.n_kf = &n_kf; g.poses = poses.data(); g.corrected = corr.data(); g.corrected_mask = cm.data(); g.noncorrected = nc.data(); g.noncorrected_mask = nm.data();
+    g.fixed = &loop; g.n_edges = &n_e; g.edges = edges.data();
+    if (n_pt) { g.n_points = &n_pt; g.points = pts.data(); g.point_ref = pt_ref.data(); }
+    if (n_ln) { g.n_lines = &n_ln; g.lines = lns.data(); g.line_ref = ln_ref.data(); }
+    if (n_pl) { g.n_planes = &n_pl; g.planes = pls.data(); g.plane_ref = pl_ref.data(); }
+    std::vector<double> sim3(8 * (size_t)n), lns_out(lns.size());
+    std::vector<float> poses_out(16 * (size_t)n), pts_out(pts.size()), pls_out(pls.size());
+    double info[5];
+    if (!on_lane(TRACKING, "planar_optimize_essential_graph", [&](planar_ctx* ctx) {
+            return planar_optimize_essential_graph(ctx, &g, bFixScale ? 1 : 0, 20, sim3.data(), poses_out.data(), n_pt ? pts_out.data() : NULL, n_ln ? lns_out.data() : NULL,
+                                                   n_pl ? pls_out.data() : NULL, info);
+        })) return;
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (KeyFrameT* pKFi : vpKFs) pKFi->SetPose(array_to_mat(&poses_out[16 * (size_t)index[pKFi]]));
+    for (size_t k = 0; k < pt_of.size(); k++) { auto* p = vpMPs[pt_of[k]]; p->SetWorldPos(array_to_mat(&pts_out[3 * k], 3, 1)); p->UpdateNormalAndDepth(); }
+    for (size_t k = 0; k < ln_of.size(); k++) {
+        auto* p = vpMLs[ln_of[k]];
+        auto P = p->GetWorldPos();
+        for (int c = 0; c < 6; c++) P(c) = lns_out[6 * k + c];
+        p->SetWorldPos(P); p->ComputeDistinctiveDescriptors(); p->UpdateAverageDir();
+    }
+    for (size_t k = 0; k < pl_of.size(); k++) { auto* p = vpMPLs[pl_of[k]]; p->SetWorldPos(array_to_mat(&pls_out[4 * k], 4, 1)); p->UpdateCoefficientsAndPoints(); }
+}
+
+}  // namespace planar_adapter
+
+namespace Planar_SLAM {
+inline void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                              const LoopClosing::KeyFrameAndPose& CorrectedSim3, const std::map<KeyFrame*, std::set<KeyFrame*> >& LoopConnections,
+                                              const bool& bFixScale) {
+    planar_adapter::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH

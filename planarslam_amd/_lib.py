@@ -86,6 +86,13 @@ class KfPoints(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("usable", "xw", "min_dist", "max_dist", "desc")]
 
 
+class EssGraph(C.Structure):
+    """planar_essgraph: a batch of pose graphs for planar_optimize_essential_graph"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "kf_stride", "edge_stride", "point_stride", "line_stride", "plane_stride")] + \
+               [(n, C.c_void_p) for n in ("n_kf", "poses", "corrected", "corrected_mask", "noncorrected", "noncorrected_mask", "fixed", "n_edges", "edges", "n_points",
+                                          "points", "point_ref", "n_lines", "lines", "line_ref", "n_planes", "planes", "plane_ref")]
+
+
 class TriCamera(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
                 ("scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
@@ -254,6 +261,8 @@ _SIGS = {
     "planar_search_by_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int, C.POINTER(FrameView), C.POINTER(KfPoints), C.c_float, C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 2),
     "planar_optimize_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_float, C.c_int] + [C.c_void_p] * 3),
     "planar_optimize_sim3_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_float, C.c_int] + [C.c_void_p] * 3),
+    "planar_optimize_essential_graph": (C.c_int, [C.c_void_p, C.POINTER(EssGraph), C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "planar_optimize_essential_graph_dev": (C.c_int, [C.c_void_p, C.POINTER(EssGraph), C.c_int, C.c_int] + [C.c_void_p] * 6),
     "planar_horn_ransac": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 15),
     "planar_horn_ransac_dev": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.POINTER(KfPoints), C.POINTER(FrameView), C.POINTER(KfPoints), C.c_void_p, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 15),
     "planar_pnp_ransac": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int] + [C.c_void_p] * 10),

@@ -14,7 +14,7 @@ void set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* planar_last_error(void) { return planar::g_err; }
-int planar_abi_version(void) { return 215; }
+int planar_abi_version(void) { return 216; }
 
 int planar_ctx_create(planar_ctx** out, int device) {
     PLANAR_REQUIRE(out != nullptr, PLANAR_EINVAL, "out is null");
