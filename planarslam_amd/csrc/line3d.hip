@@ -59,17 +59,19 @@ __device__ void jacobi3(double At[3][3], double W[3]) {
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) W[i] = sqrt(At[i][0] * At[i][0] + At[i][1] * At[i][1] + At[i][2] * At[i][2]);
-    // selection sort, descending (rows move with their singular values); written out so that every index is a constant
-    auto swap_rows = [&](int x, int y) {
-        const double t = W[x]; W[x] = W[y]; W[y] = t;
+    // selection sort, descending (rows move with their singular values); written out as conditional moves so that every index is a constant and nothing
+    // is addressed through memory
+    auto swap_rows_if = [&](bool sw, int x, int y) {
+        const double wx = W[x], wy = W[y];
+        W[x] = sw ? wy : wx; W[y] = sw ? wx : wy;
 #pragma unroll
-        for (int k = 0; k < 3; k++) { const double u = At[x][k]; At[x][k] = At[y][k]; At[y][k] = u; }
+        for (int k = 0; k < 3; k++) { const double ax = At[x][k], ay = At[y][k]; At[x][k] = sw ? ay : ax; At[y][k] = sw ? ax : ay; }
     };
     {
         const bool j1 = W[0] < W[1];                          // i = 0: j = first maximum of W[0..2]
         const bool j2 = (j1 ? W[1] : W[0]) < W[2];
-        if (j2) swap_rows(0, 2); else if (j1) swap_rows(0, 1);
-        if (W[1] < W[2]) swap_rows(1, 2);                     // i = 1
+        swap_rows_if(j2, 0, 2); swap_rows_if(!j2 && j1, 0, 1);
+        swap_rows_if(W[1] < W[2], 1, 2);                      // i = 1
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -99,11 +101,20 @@ __device__ __forceinline__ P3 project_pt(const P3& P, const P3& mid, const P3& d
     return A + AB * (dot(AB, AP) / (dot(AB, AB)));
 }
 
-// sum of s[0..m) in index order (the order of the reference's loops); every lane walks the array (broadcast LDS reads)
-__device__ __forceinline__ double chain_sum(const double* s, int m) {
+// NC <= 3 sums of s[j][0..m), each in index order (the order of the reference's loops), formed in ONE walk: lane j < NC owns the accumulator of chain j, all
+// lanes walk the index together (the lanes past NC repeat the last chain), the sums are handed out by lane reads.  The loads do not depend on the chain.
+template <int NC>
+__device__ __forceinline__ void chain_sums(const double (*s)[64], int m, int lane, double* out) {
+    const double* row = s[min(lane, NC - 1)];
     double acc = 0;
-    for (int k = 0; k < m; k++) acc += s[k];
-    return acc;
+    int k = 0;
+    for (; k + 4 <= m; k += 4) {
+        const double a0 = row[k], a1 = row[k + 1], a2 = row[k + 2], a3 = row[k + 3];
+        acc += a0; acc += a1; acc += a2; acc += a3;
+    }
+    for (; k < m; k++) acc += row[k];
+#pragma unroll
+    for (int j = 0; j < NC; j++) out[j] = __shfl(acc, j);
 }
 
 // first lane (in lane order) among `mask` whose value equals the extreme one: what a running strict < / > comparison keeps
@@ -122,7 +133,8 @@ struct Args {
     float* depth_line; double* lines3d; uint8_t* good; double* direction; int32_t* n_inliers; int32_t* n_good;
 };
 
-__global__ __launch_bounds__(64) void line3d_kernel(Args a) {
+// four wavefronts per SIMD: 128 registers hold the kernel without scratch
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void line3d_kernel(Args a) {
     __shared__ double s_pos[3][64];
     __shared__ double s_ch[3][64];
     __shared__ unsigned char s_idx[64], s_rank[64];
@@ -296,7 +308,9 @@ __global__ __launch_bounds__(64) void line3d_kernel(Args a) {
             if (in) { s_ch[0][rk] = pos.x; s_ch[1][rk] = pos.y; s_ch[2][rk] = pos.z; s_rank[rk] = (unsigned char)lane; }
             __syncthreads();
             const int mI = best_cnt;
-            P3 mean = {chain_sum(s_ch[0], mI), chain_sum(s_ch[1], mI), chain_sum(s_ch[2], mI)};
+            double sum3[3];
+            chain_sums<3>(s_ch, mI, lane, sum3);
+            P3 mean = {sum3[0], sum3[1], sum3[2]};
             mean = mean * (1.0 / mI);
             // rows of At (3 x mI): lane k < mI holds column k
             const bool col = lane < mI;
@@ -305,13 +319,32 @@ __global__ __launch_bounds__(64) void line3d_kernel(Args a) {
             if (col) { r0 = s_ch[0][lane] - mean.x; r1 = s_ch[1][lane] - mean.y; r2 = s_ch[2][lane] - mean.z; }
             double R[3] = {r0, r1, r2};
             double Wv[3], Vt[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-            auto gram = [&](double v0, double v1, double v2, double& o0, double& o1, double& o2) {    // three ordered sums over the columns
+            // ordered sums over the columns: only the chains a call needs are written and walked (the reference's sums of exact zeros are not formed)
+            auto gram3 = [&](double v0, double v1, double v2, double& o0, double& o1, double& o2) {
                 __syncthreads();
                 s_ch[0][lane] = v0; s_ch[1][lane] = v1; s_ch[2][lane] = v2;
                 __syncthreads();
-                o0 = chain_sum(s_ch[0], mI); o1 = chain_sum(s_ch[1], mI); o2 = chain_sum(s_ch[2], mI);
+                double o[3];
+                chain_sums<3>(s_ch, mI, lane, o);
+                o0 = o[0]; o1 = o[1]; o2 = o[2];
             };
-            gram(R[0] * R[0], R[1] * R[1], R[2] * R[2], Wv[0], Wv[1], Wv[2]);
+            auto gram2 = [&](double v0, double v1, double& o0, double& o1) {
+                __syncthreads();
+                s_ch[0][lane] = v0; s_ch[1][lane] = v1;
+                __syncthreads();
+                double o[2];
+                chain_sums<2>(s_ch, mI, lane, o);
+                o0 = o[0]; o1 = o[1];
+            };
+            auto gram1 = [&](double v0) -> double {
+                __syncthreads();
+                s_ch[0][lane] = v0;
+                __syncthreads();
+                double o[1];
+                chain_sums<1>(s_ch, mI, lane, o);
+                return o[0];
+            };
+            gram3(R[0] * R[0], R[1] * R[1], R[2] * R[2], Wv[0], Wv[1], Wv[2]);
             const double eps = 2.220446049250313e-16 * 10;
             const int max_iter = max(mI, 30);
             for (int iter = 0; iter < max_iter; iter++) {
@@ -319,8 +352,8 @@ __global__ __launch_bounds__(64) void line3d_kernel(Args a) {
 #pragma unroll
                 for (int pr = 0; pr < 3; pr++) {
                     const int i = pr == 2 ? 1 : 0, j = pr == 0 ? 1 : 2;
-                    double aa = Wv[i], bb = Wv[j], pp, u1, u2;
-                    gram(R[i] * R[j], 0, 0, pp, u1, u2);
+                    double aa = Wv[i], bb = Wv[j], pp;
+                    pp = gram1(R[i] * R[j]);
                     if (fabs(pp) <= eps * sqrt(aa * bb)) continue;
                     pp *= 2;
                     const double beta = aa - bb, gamma = hypot(pp, beta);
@@ -329,7 +362,7 @@ __global__ __launch_bounds__(64) void line3d_kernel(Args a) {
                     else { c = sqrt((gamma + beta) / (gamma * 2)); s = (pp / (gamma * c * 2)); }
                     const double t0 = c * R[i] + s * R[j], t1 = -s * R[i] + c * R[j];
                     R[i] = t0; R[j] = t1;
-                    gram(t0 * t0, t1 * t1, 0, aa, bb, u1);
+                    gram2(t0 * t0, t1 * t1, aa, bb);
                     Wv[i] = aa; Wv[j] = bb;
                     changed = true;
 #pragma unroll
@@ -337,13 +370,16 @@ __global__ __launch_bounds__(64) void line3d_kernel(Args a) {
                 }
                 if (!changed) break;
             }
-            gram(R[0] * R[0], R[1] * R[1], R[2] * R[2], Wv[0], Wv[1], Wv[2]);
+            gram3(R[0] * R[0], R[1] * R[1], R[2] * R[2], Wv[0], Wv[1], Wv[2]);
 #pragma unroll
             for (int i = 0; i < 3; i++) Wv[i] = sqrt(Wv[i]);
-            int top = 0;                                   // vt.row(0) after the descending selection sort = the row of the first maximum
-            if (Wv[top] < Wv[1]) top = 1;
-            if (Wv[top] < Wv[2]) top = 2;
-            const P3 tmp_m = mean, tmp_d = {Vt[top][0], Vt[top][1], Vt[top][2]};
+            // vt.row(0) after the descending selection sort = the row of the first maximum; chosen by selects, so that Vt stays in registers
+            const bool t1 = Wv[0] < Wv[1];
+            const bool t2 = (t1 ? Wv[1] : Wv[0]) < Wv[2];
+            P3 tmp_d = {Vt[0][0], Vt[0][1], Vt[0][2]};
+            if (t1) tmp_d = {Vt[1][0], Vt[1][1], Vt[1][2]};
+            if (t2) tmp_d = {Vt[2][0], Vt[2][1], Vt[2][2]};
+            const P3 tmp_m = mean;
             const bool inl2 = act && mah_dist(DU, pos, tmp_m, tmp_m + tmp_d) < DIST_THRESH;
             const unsigned long long mask2 = __ballot(inl2);
             __syncthreads();

@@ -9,9 +9,11 @@
 //   A  depth-change map -> initial distance map               one thread per grid cell; the marks PCL's sequential loop sets are order-independent
 //   B  two chamfer passes (1.0 / 1.4 weights)                  rows in sequence, columns in parallel: new[c] = min(t[c], new[c-1] + 1.0f) is
 //      evaluated as min over k <= 11 of (t[c-k] +1 +1 ... k times), each sum formed in the reference's order, which is exact for every value
-//      <= 10 (a chain of k steps costs >= k) - and only min(distance, 10) is ever read.  PCL's row-wrapping reads are reproduced.
+//      <= 10 (a chain of k steps costs >= k) - and only min(distance, 10) is ever read.  PCL's row-wrapping reads are reproduced.  The row a step
+//      writes stays in LDS as the next step's neighbour row; two barriers per row, no global access between them.
 //   C  first-order integral images of the two gradient fields  FP64, PCL's recurrence cur[c+1] = prev[c+1] + cur[c] - prev[c] + e[c], whose rounding
-//      depends on the order: six lanes (2 images x 3 components) walk each row in sequence in LDS (in place), all threads stage the row in and out
+//      depends on the order.  A cell needs (r, c), (r-1, c) and (r-1, c+1) only, so row r runs one column behind row r-1: bands of 10 rows, 60 lanes
+//      (10 rows x 2 images x 3 components) of one wavefront walk a band as a skewed front, gw + 9 steps per band instead of 10 gw
 //   D  box sums, cross product, normalisation, flip towards the viewpoint    one thread per output normal
 // Everything is FP32 / FP64 in the reference's operation order (-ffp-contract=off); outputs are bit-identical to the oracle.
 #include <algorithm>
@@ -23,6 +25,11 @@ namespace normals {
 
 constexpr int NT = 256;
 constexpr int KCHAIN = 11;
+constexpr int RB = 10;             // rows of an integral-image band: 6 components x RB rows are the chain lanes of one wavefront
+static_assert(6 * RB <= 64, "a band's chain lanes are one wavefront");
+
+// the value the lane below holds (lane 0 and lanes whose neighbour is idle get a value nobody uses)
+__device__ __forceinline__ double lane_up1(double v) { return __shfl_up(v, 1); }
 
 struct Geo {
     int W, H, gw, gh, iw;          // image, grid (gw = ceil(W/3), gh = ceil(H/3)), integral-image row length gw + 1
@@ -49,15 +56,72 @@ __device__ __forceinline__ bool jump(float d0, float d1) {
     return fabsf(d0 - d1) > th || !isfinite(d0) || !isfinite(d1);
 }
 
-__global__ __launch_bounds__(NT) void normals_kernel(Geo G, const uint16_t* __restrict__ depth_all, int pitch_px, int64_t frame_stride_px, uint8_t* __restrict__ ws_all,
+// The two chamfer passes of one frame.  The neighbouring row stays in LDS from step to step: the row a step writes is the next step's s_prev.  Its wrapped end
+// element is a value of the CURRENT row the pass does not update (forward: s_prev[gw + 1] = cur[0]; backward: s_prev[0] = cur[gw - 1]); the other end is never
+// read by an active column.  ONE: the grid is no wider than the workgroup, a thread owns one column and loads cur's old value one step ahead, so that no global
+// load lies between the two barriers of a row; wider grids loop over their columns and load it in place.
+template <bool ONE>
+__device__ __forceinline__ void chamfer_passes(float* __restrict__ dist, float* s_row0, int gw, int gh, int tid) {
+    float* s_row1 = s_row0 + (gw + 2);         // [gw + 2] x 2: the neighbouring row with the wrapped element at either end, and the row being written
+    float* s_t = s_row1 + (gw + 2);            // [gw]
+    for (int pass = 0; pass < 2; pass++) {
+        const int dir = pass == 0 ? 1 : -1;                 // forward: rows 1 .. gh-1, columns ascending; backward: rows gh-2 .. 0, columns descending
+        const int rfirst = pass == 0 ? 0 : gh - 1;          // the row the pass starts from and leaves as it is
+        const int cwrap = pass == 0 ? 0 : gw - 1, wslot = pass == 0 ? gw + 1 : 0;
+        float told = 0.f;
+        for (int c = tid; c < gw; c += NT) {
+            s_row0[1 + c] = dist[(size_t)rfirst * gw + c];
+            if (ONE) told = dist[(size_t)(rfirst + dir) * gw + c];
+            if (c == cwrap) { s_row0[wslot] = dist[(size_t)(rfirst + dir) * gw + c]; s_row0[gw + 1 - wslot] = 0.f; s_row1[gw + 1 - wslot] = 0.f; }
+        }
+        __syncthreads();
+        float *s_prev = s_row0, *s_next = s_row1;
+        for (int step = 1; step < gh; step++) {
+            const int r = rfirst + dir * step;
+            float* cur = dist + (size_t)r * gw;
+            const bool more = step + 1 < gh;
+            for (int c = tid; c < gw; c += NT) {
+                float t = ONE ? told : cur[c];
+                const bool active = pass == 0 ? c >= 1 : c <= gw - 2;
+                if (active) {
+                    const float a = s_prev[1 + c - 1] + 1.4f, u = s_prev[1 + c] + 1.0f, d = s_prev[1 + c + 1] + 1.4f;
+                    t = fminf(t, fminf(fminf(a, u), d));
+                }
+                s_t[c] = t;
+                if (ONE && more) told = cur[(ptrdiff_t)dir * gw + c];      // the next row's old value, needed after the next barrier
+            }
+            __syncthreads();
+            for (int c = tid; c < gw; c += NT) {
+                const bool active = pass == 0 ? c >= 1 : c <= gw - 2;
+                float best = s_t[c];
+                if (active) {
+                    for (int k = 1; k <= KCHAIN; k++) {
+                        const int cs = c - dir * k;         // the chain starts k cells "behind" in scan direction
+                        if (cs < 0 || cs > gw - 1) break;
+                        float v = s_t[cs];
+                        for (int q = 0; q < k; q++) v = v + 1.0f;
+                        best = fminf(best, v);
+                    }
+                }
+                cur[c] = best;
+                s_next[1 + c] = best;
+                if (c == cwrap && more) s_next[wslot] = ONE ? told : cur[(ptrdiff_t)dir * gw + c];
+            }
+            __syncthreads();
+            float* sw = s_prev; s_prev = s_next; s_next = sw;
+        }
+    }
+}
+
+// eight frames per compute unit (one wavefront of each per SIMD): 2048 frames are one round on 256 CUs; the kernel fits 64 registers without scratch
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void normals_kernel(Geo G, const uint16_t* __restrict__ depth_all, int pitch_px, int64_t frame_stride_px, uint8_t* __restrict__ ws_all,
                                                     float* __restrict__ normals, float* __restrict__ points, int out_stride) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const uint16_t* depth = depth_all + (size_t)b * frame_stride_px;
     float* dist = (float*)(ws_all + (size_t)b * G.ws_stride);
-    double* I = (double*)(ws_all + (size_t)b * G.ws_stride + G.off_I);        // [2][(gh + 1) * iw][3]
+    double* I = (double*)(ws_all + (size_t)b * G.ws_stride + G.off_I);        // [(gh + 1) * iw][6]: both images' three components side by side
     const int gw = G.gw, gh = G.gh, iw = G.iw;
-    const size_t img_stride = (size_t)(gh + 1) * iw * 3;
 
     // ---- A: depth-change map -> initial distance map ----
     for (int i = tid; i < gw * gh; i += NT) {
@@ -72,98 +136,73 @@ __global__ __launch_bounds__(NT) void normals_kernel(Geo G, const uint16_t* __re
     __syncthreads();
 
     // ---- B: chamfer passes ----
-    float* s_prev = (float*)smem;              // [gw + 2]: the neighbouring row, with the wrapped element at either end
-    float* s_t = s_prev + (gw + 2);            // [gw]
-    for (int pass = 0; pass < 2; pass++) {
-        const int dir = pass == 0 ? 1 : -1;                 // forward: rows 1 .. gh-1, columns ascending; backward: rows gh-2 .. 0, columns descending
-        for (int step = 1; step < gh; step++) {
-            const int r = pass == 0 ? step : gh - 1 - step;
-            const float* nb = dist + (size_t)(r - dir) * gw;    // previous_row / next_row (final values)
-            float* cur = dist + (size_t)r * gw;
-            // s_prev[1 + c] = nb[c]; s_prev[0] = nb[-1], s_prev[gw + 1] = nb[gw]: the flat-array neighbours PCL reads at the row ends
-            for (int c = tid; c < gw + 2; c += NT) {
-                const long idx = (long)(r - dir) * gw + (c - 1);
-                s_prev[c] = (idx >= 0 && idx < (long)gw * gh) ? dist[idx] : 0.f;
-            }
-            __syncthreads();
-            (void)nb;
-            for (int c = tid; c < gw; c += NT) {
-                float t = cur[c];
-                const bool active = pass == 0 ? c >= 1 : c <= gw - 2;
-                if (active) {
-                    const float a = s_prev[1 + c - 1] + 1.4f, u = s_prev[1 + c] + 1.0f, d = s_prev[1 + c + 1] + 1.4f;
-                    t = fminf(t, fminf(fminf(a, u), d));
-                }
-                s_t[c] = t;
-            }
-            __syncthreads();
-            for (int c = tid; c < gw; c += NT) {
-                const bool active = pass == 0 ? c >= 1 : c <= gw - 2;
-                float best = s_t[c];
-                if (active) {
-                    for (int k = 1; k <= KCHAIN; k++) {
-                        const int cs = c - dir * k;         // the chain starts k cells "behind" in scan direction
-                        if (cs < 0 || cs > gw - 1) break;
-                        float v = s_t[cs];
-                        for (int j = 0; j < k; j++) v = v + 1.0f;
-                        best = fminf(best, v);
-                    }
-                }
-                cur[c] = best;
-            }
-            __syncthreads();
-        }
-    }
+    if (gw <= NT) chamfer_passes<true>(dist, (float*)smem, gw, gh, tid); else chamfer_passes<false>(dist, (float*)smem, gw, gh, tid);
 
     // ---- C: integral images ----
-    double* s_I = (double*)smem;                            // [iw][6]: the previous row, overwritten in place by the current one
-    float* s_e = (float*)(s_I + (size_t)iw * 6);            // [gw][6]
-    for (int i = tid; i < iw * 6; i += NT) s_I[i] = 0.0;
-    for (int i = tid; i < iw; i += NT) for (int k = 0; k < 3; k++) { I[(size_t)i * 3 + k] = 0.0; I[img_stride + (size_t)i * 3 + k] = 0.0; }
-    __syncthreads();
-    for (int r = 0; r < gh; r++) {
-        for (int c = tid; c < gw; c += NT) {
-            float e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (r >= 1 && r < gh - 1 && c >= 1 && c < gw - 1) {
-                const Pt pl = cloud_pt(G, depth, pitch_px, r, c - 1), pr = cloud_pt(G, depth, pitch_px, r, c + 1);
-                const Pt pu = cloud_pt(G, depth, pitch_px, r - 1, c), pd = cloud_pt(G, depth, pitch_px, r + 1, c);
-                e[0] = pr.x - pl.x; e[1] = pr.y - pl.y; e[2] = pr.z - pl.z;
-                e[3] = pd.x - pu.x; e[4] = pd.y - pu.y; e[5] = pd.z - pu.z;
-            }
-            for (int k = 0; k < 6; k++) s_e[c * 6 + k] = e[k];
+    // Bands of RB rows.  Wavefront 0 runs the chains: lane k * RB + i owns (row i of the band, component k) and handles column s - i at step s, so that the row
+    // above (the lane below, one step earlier) has just produced prev[c + 1]; prev[c] is last step's prev[c + 1] and cur[c] stays in a register.  Row 0 of a band
+    // reads the last row of the band before from s_I, which the band's last row overwrites behind it.  Every cell is (prev[c+1] + cur[c] - prev[c]) + e[c] as before.
+    double* s_I = (double*)smem;                            // [iw][6]: the last row of the previous band
+    uint16_t* s_d = (uint16_t*)(s_I + (size_t)iw * 6);      // [RB + 2][gw]: the depth of the band's grid rows and of the one above and below
+    for (int i = tid; i < iw * 6; i += NT) { s_I[i] = 0.0; I[i] = 0.0; }
+    for (int i = tid; i < gh * 6; i += NT) I[((size_t)(i / 6 + 1) * iw) * 6 + i % 6] = 0.0;      // column 0 of every row
+    const int ci = tid % RB, ck = tid / RB;                 // chain lanes: tid < 6 * RB
+    const bool chain = tid < 6 * RB;
+    const bool horiz = ck < 3;                              // components 0..2: right - left; 3..5: down - up
+    const int kc = ck % 3;                                  // x, y, z
+    const float dvs = kc == 0 ? G.fx : kc == 1 ? G.fy : 1.0f;       // x / 1.0f and 1.0f * x are x: one instruction stream for the three components
+    for (int r0 = 0; r0 < gh; r0 += RB) {
+        const int nb = min(RB, gh - r0);
+        __syncthreads();                                    // the chains of the band before have read s_d
+        const int rlo = max(r0 - 1, 0), rhi = min(r0 + nb, gh - 1);
+        for (int i = tid; i < (rhi - rlo + 1) * gw; i += NT) {
+            const int rr = i / gw, c = i - rr * gw;
+            s_d[(rr + rlo - (r0 - 1)) * gw + c] = depth[(size_t)(3 * (rr + rlo)) * pitch_px + 3 * c];
         }
         __syncthreads();
-        if (tid < 6) {
-            double run = 0.0;                               // current_row[0] = 0
-            double pl = s_I[tid];                           // previous_row[0]
-            s_I[tid] = 0.0;
-            int c = 0;
-            for (; c + 4 <= gw; c += 4) {                   // the loads do not depend on the chain: four columns are fetched ahead of it
-                double pr[4]; float ee[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) { pr[u] = s_I[(c + u + 1) * 6 + tid]; ee[u] = s_e[(c + u) * 6 + tid]; }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    double v = pr[u] + run - pl;
-                    v += (double)ee[u];
-                    s_I[(c + u + 1) * 6 + tid] = v;
-                    run = v; pl = pr[u];
+        if (chain && ci < nb) {                             // wavefront 0 only (6 * RB <= 64)
+            const int r = r0 + ci;
+            const bool rin = r >= 1 && r < gh - 1;
+            const int rowP = (horiz ? ci + 1 : ci + 2) * gw, rowM = (horiz ? ci + 1 : ci) * gw;     // rows of s_d: grid row r is row ci + 1
+            const int dcP = horiz ? 1 : 0, dcM = horiz ? -1 : 0;
+            const float mP = kc == 1 ? (float)(3 * (horiz ? r : r + 1)) - G.cy : 1.0f, mM = kc == 1 ? (float)(3 * (horiz ? r : r - 1)) - G.cy : 1.0f;
+            // e[c] of this lane's row and component from the two depth samples it needs; the samples are read (clamped, so without a branch) a step before
+            // they are used and the gradient is formed a step before the chain takes it: neither the LDS latency nor the divisions lie on the chain
+            auto sampleP = [&](int c) -> uint16_t { return s_d[rowP + min(max(c + dcP, 0), gw - 1)]; };
+            auto sampleM = [&](int c) -> uint16_t { return s_d[rowM + min(max(c + dcM, 0), gw - 1)]; };
+            auto grad = [&](uint16_t sP, uint16_t sM, int c) -> float {
+                const float dP = (float)sP * G.factor, dM = (float)sM * G.factor;
+                const float fP = kc == 0 ? (float)(3 * (c + dcP)) - G.cx : mP, fM = kc == 0 ? (float)(3 * (c + dcM)) - G.cx : mM;
+                const float e = fP * dP / dvs - fM * dM / dvs;
+                return (rin && c >= 1 && c < gw - 1) ? e : 0.f;
+            };
+            auto prev_at = [&](int col) -> double { return s_I[(size_t)min(max(col, 0), gw) * 6 + ck]; };      // used by the band's first row only
+            double* out = I + ((size_t)(r + 1) * iw + 1) * 6 + ck;
+            const bool first = ci == 0, last = ci == nb - 1;
+            double run = 0.0, pl = 0.0, v = 0.0;            // cur[0] = 0, prev[0] = 0
+            double pr1 = prev_at(1 - ci), pr2 = prev_at(2 - ci);
+            float e_next = grad(sampleP(-ci), sampleM(-ci), -ci);
+            uint16_t sP1 = sampleP(1 - ci), sM1 = sampleM(1 - ci);
+            const int nsteps = gw + nb - 1;
+            for (int s = 0; s < nsteps; s++) {
+                const int c = s - ci;
+                const double up = lane_up1(v);              // what the row above produced one step ago: prev[c + 1]
+                const double pr_here = pr1;
+                const float e = e_next;
+                const uint16_t sP2 = sampleP(c + 2), sM2 = sampleM(c + 2);
+                pr1 = pr2; pr2 = prev_at(c + 3);            // ahead of the band's last row, which overwrites s_I[<= c + 1] behind it
+                e_next = grad(sP1, sM1, c + 1);
+                sP1 = sP2; sM1 = sM2;
+                if (c >= 0 && c < gw) {
+                    const double pr = first ? pr_here : up;
+                    double w = pr + run - pl;
+                    w += (double)e;
+                    out[(size_t)c * 6] = w;
+                    if (last) s_I[(size_t)(c + 1) * 6 + ck] = w;
+                    run = w; pl = pr; v = w;
                 }
             }
-            for (; c < gw; c++) {
-                const double pr = s_I[(c + 1) * 6 + tid];
-                double v = pr + run - pl;
-                v += (double)s_e[c * 6 + tid];
-                s_I[(c + 1) * 6 + tid] = v;
-                run = v; pl = pr;
-            }
         }
-        __syncthreads();
-        for (int i = tid; i < iw * 6; i += NT) {
-            const int c = i / 6, k = i - c * 6;
-            I[(size_t)(k / 3) * img_stride + ((size_t)(r + 1) * iw + c) * 3 + (k % 3)] = s_I[i];
-        }
-        // the next row's s_e writes and this row's s_I reads touch different arrays; the barrier after the s_e fill orders the chain behind both
     }
     __syncthreads();
 
@@ -183,8 +222,8 @@ __global__ __launch_bounds__(NT) void normals_kernel(Geo G, const uint16_t* __re
                 double gx[3], gy[3];
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    gx[k] = I[lr * 3 + k] + I[ul * 3 + k] - I[ur * 3 + k] - I[ll * 3 + k];
-                    gy[k] = I[img_stride + lr * 3 + k] + I[img_stride + ul * 3 + k] - I[img_stride + ur * 3 + k] - I[img_stride + ll * 3 + k];
+                    gx[k] = I[lr * 6 + k] + I[ul * 6 + k] - I[ur * 6 + k] - I[ll * 6 + k];
+                    gy[k] = I[lr * 6 + 3 + k] + I[ul * 6 + 3 + k] - I[ur * 6 + 3 + k] - I[ll * 6 + 3 + k];
                 }
                 const double v0 = gy[1] * gx[2] - gy[2] * gx[1], v1 = gy[2] * gx[0] - gy[0] * gx[2], v2 = gy[0] * gx[1] - gy[1] * gx[0];
                 const double len2 = v0 * v0 + v1 * v1 + v2 * v2;
@@ -229,7 +268,8 @@ int planar_normals_create(planar_ctx* ctx, int width, int height, int max_batch,
     const size_t dist_bytes = align_up((size_t)G.gw * G.gh * 4, (size_t)256);
     G.off_I = dist_bytes;
     G.ws_stride = dist_bytes + align_up((size_t)2 * (G.gh + 1) * G.iw * 3 * 8, (size_t)256);
-    p->smem = std::max((size_t)(2 * G.gw + 2) * 4, (size_t)G.iw * 6 * 8 + (size_t)G.gw * 6 * 4);      // 15.4 KB at 640x480: fits beside four peac_ahc frames on a CU
+    // chamfer rows (two neighbour rows + t) | the previous band's last integral row + the band's depth rows: 15.4 KB at 640x480, beside four peac_ahc frames on a CU
+    p->smem = std::max((size_t)(3 * G.gw + 4) * 4, (size_t)G.iw * 6 * 8 + (size_t)(normals::RB + 2) * G.gw * 2);
     int rc = p->ws.alloc(G.ws_stride * (size_t)max_batch);
     if (rc) { delete p; return rc; }
     if (p->smem > 48 * 1024) {
