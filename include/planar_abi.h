@@ -999,6 +999,38 @@ typedef struct planar_ba_result {
 int planar_local_ba(planar_ctx* ctx, const planar_ba_problem* problem, const planar_pose_params* params, int its1, int its2,
                     planar_ba_result* result, const volatile unsigned char* stop_flag, planar_comm* comm);
 
+/* ---- Global bundle adjustment (replaces the numerical core of Optimizer::BundleAdjustment, src/Optimizer.cc:44-548, as Optimizer::GlobalBundleAdjustemnt calls it
+ *      from LoopClosing::RunGlobalBundleAdjustment: ONE optimize(iterations) over every key frame and landmark of the map, no outlier levels, no erase lists) ----
+ * The same planar_ba_problem as the local BA: key frames in ascending mnId, kf_fixed = (mnId == 0) in the reference (any pattern is accepted, none fixed and all
+ * fixed included), line edges in consecutive (start, end) pairs with e_kf the OBSERVING key frame (:225-236 read that key frame's own line function; the local
+ * BA's quirk of hanging them on the central key frame does not exist here), identity information on both line edges, angleInfo on both the vertical and the
+ * parallel edges.  Huber kernels by edge kind: mono sqrt(5.99) (5.99 here, 5.991 in the local BA), stereo and line sqrt(7.815), each rounded through float, and
+ * only when `robust` is set; plane, vertical and parallel edges always carry theirs (sqrt(Plane.Chi), sqrt(Plane.VPChi)).
+ * A landmark without an edge is not optimised (the reference's vbNotIncluded*): lm_included is 0 and lm is lm_init, bit for bit.  A landmark whose edges all sit
+ * on fixed key frames is optimised.  stop_flag (or NULL) is sampled as planar_local_ba samples it; with the flag up on entry nothing is optimised (status
+ * PLANAR_GBA_STOPPED, poses through a quaternion, planes normalised).  No edges at all: nothing to optimise, status PLANAR_GBA_CONVERGED, the same pass-through.
+ * Up to PLANAR_GBA_MAX_KF key frames, fixed ones included: one more is PLANAR_ECAPACITY and writes nothing.  PLANAR_EINVAL (nothing launched, nothing written) on
+ * the conditions planar_local_ba checks: a null argument or array, negative sizes, an edge that names a key frame, landmark or kind out of range, a line edge
+ * without its partner.  There is no communicator argument: single GPU only.  Synchronous.  Two calls on the same input return the same bits (no floating-point
+ * atomics anywhere; every sum has one owner and a fixed order). */
+#define PLANAR_GBA_MAX_KF 256          /* = PLANAR_ESSGRAPH_MAX_KF: the call that follows the essential graph takes what the essential graph takes */
+#define PLANAR_GBA_CONVERGED 1         /* g2o's own stop rules: ten failed trials in an iteration, rho == 0, or three iterations without gain */
+#define PLANAR_GBA_MAX_ITERATIONS 2
+#define PLANAR_GBA_STOPPED 3           /* the stop flag */
+typedef struct planar_gba_result {
+    float* kf_Tcw;                /* [n_kf][16]  optimised poses                                                     */
+    double* lm;                   /* [n_lm][4]   optimised landmarks                                                 */
+    uint8_t* lm_included;         /* [n_lm]      0 where the reference would skip the landmark (no edge)             */
+    int32_t lm_iterations;        /* LM iterations run                                                               */
+    int32_t trials;               /* LM trials run (an iteration has one, plus one per rejected step)                */
+    int32_t stopped;              /* 1 if *stop_flag was seen                                                        */
+    int32_t status;               /* PLANAR_GBA_*                                                                    */
+    double chi2;                  /* robust chi2 of the returned estimate                                            */
+    double lambda;                /* the damping the solve ended with                                                */
+} planar_gba_result;
+int planar_global_ba(planar_ctx* ctx, const planar_ba_problem* problem, const planar_pose_params* params, int iterations, int robust,
+                     planar_gba_result* result, const volatile unsigned char* stop_flag);
+
 /* ---- DBoW2 vocabulary transform (replaces ORBVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) as Frame::ComputeBoW and
  *      KeyFrame::ComputeBoW call it with levelsup = 4; Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1124-1180, :1203-1250; include/ORBVocabulary.h:31) ----
  * The vocabulary arrives as the rows of the text format TemplatedVocabulary::loadFromTextFile reads (ORBvoc.txt): for node 1..n in file order its

@@ -13,6 +13,7 @@
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
 //   Planar_SLAM::PnPsolver  <- include/PnPsolver.h, src/PnPsolver.cc                                    (PLANAR_ADAPTERS_WITH_PNP_SOLVER)
 //   Optimizer::OptimizeEssentialGraph                                                                 (PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH)
+//   Optimizer::BundleAdjustment / GlobalBundleAdjustemnt                                              (PLANAR_ADAPTERS_WITH_GLOBAL_BA)
 //   ORBmatcher / LSDmatcher / PlaneMatcher / Optimizer member functions                                (PLANAR_ADAPTERS_WITH_TRACKING:
 //       include this header AFTER the reference's Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, ORBmatcher.h, LSDmatcher.h,
 //       PlaneMatcher.h and Optimizer.h; it then DEFINES the member functions those headers declare - gather the Frame fields into flat
@@ -1886,3 +1887,149 @@ inline void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyF
 }
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_ESSENTIAL_GRAPH
+
+
+// ---- Optimizer::BundleAdjustment / Optimizer::GlobalBundleAdjustemnt (src/Optimizer.cc:35-548, called from LoopClosing::RunGlobalBundleAdjustment,
+//      src/LoopClosing.cc:650): DEFINITIONS with the reference's signatures.  The map becomes a planar_ba_problem, planar_global_ba solves it, the values go back as
+//      :451-547 put them back.  Enabled with PLANAR_ADAPTERS_WITH_GLOBAL_BA, after the reference's Optimizer.h, Map.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h and
+//      Config.h; leave those two bodies of src/Optimizer.cc out.
+//      What is gathered: the key frames that are not bad, by ascending mnId (mnId 0 fixed); maxKFid over them; every map point, line and plane that is not bad; of
+//      their observations (for a plane its three maps: plane, vertical, parallel) those whose key frame is not bad and has mnId <= maxKFid.  (An observing key frame
+//      that passes both tests but is not in vpKFs has no vertex in the reference, which then dereferences a null pointer; here the observation is skipped.)  A line
+//      observation reads the OBSERVING key frame's mvKeyLineFunctions (:232).  A landmark left without an observation is the reference's vbNotIncluded*: untouched.
+//      Write-back: nLoopKF == 0: SetPose / SetWorldPos with UpdateNormalAndDepth / UpdateAverageDir / UpdateCoefficientsAndPoints, in the reference's order (key frames,
+//      points, lines, planes); otherwise mTcwGBA / mPosGBA (float, as Converter::toCvMat leaves them) and mnBAGlobalForKF = nLoopKF.  Intrinsics are the first key
+//      frame's (the reference copies each key frame's own into its edges; one camera per map is what the library takes).  A failing call, or a map of more than
+//      PLANAR_GBA_MAX_KF key frames, writes a message to stderr and changes nothing.
+#ifdef PLANAR_ADAPTERS_WITH_GLOBAL_BA
+#include <algorithm>
+namespace Planar_SLAM {
+inline void Optimizer::BundleAdjustment(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, const std::vector<MapLine*>& vpML,
+                                        const std::vector<MapPlane*>& vpMPL, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+    std::vector<KeyFrame*> kfs;
+    for (KeyFrame* k : vpKFs) if (k && !k->isBad()) kfs.push_back(k);
+    std::sort(kfs.begin(), kfs.end(), [](KeyFrame* a, KeyFrame* b) { return a->mnId < b->mnId; });
+    const int K = (int)kfs.size();
+    if (K < 1) return;
+    if (K > PLANAR_GBA_MAX_KF) { std::fprintf(stderr, "planar (BundleAdjustment): %d key frames, 1 .. %d supported - nothing optimised\n", K, PLANAR_GBA_MAX_KF); return; }
+    std::map<KeyFrame*, int> kf_index;
+    std::vector<float> kf_Tcw((size_t)K * 16);
+    std::vector<uint8_t> kf_fixed(K);
+    unsigned long maxKFid = 0;
+    for (int k = 0; k < K; k++) {
+        kf_index[kfs[k]] = k;
+        planar_adapter::mat_to_array(kfs[k]->GetPose(), &kf_Tcw[(size_t)k * 16]);
+        kf_fixed[k] = kfs[k]->mnId == 0;
+        if (kfs[k]->mnId > maxKFid) maxKFid = kfs[k]->mnId;
+    }
+    std::vector<uint8_t> lm_type, e_type;
+    std::vector<double> lm_init, e_meas;
+    std::vector<int32_t> e_kf, e_lm;
+    std::vector<float> e_is2;
+    auto add_lm = [&](int type, double a, double b, double c, double d) { lm_type.push_back((uint8_t)type); lm_init.insert(lm_init.end(), {a, b, c, d}); return (int32_t)lm_type.size() - 1; };
+    auto add_edge = [&](int kf, int lm, int type, double m0, double m1, double m2, double m3, float is2) {
+        e_kf.push_back(kf); e_lm.push_back(lm); e_type.push_back((uint8_t)type); e_meas.insert(e_meas.end(), {m0, m1, m2, m3}); e_is2.push_back(is2);
+    };
+    // the vertex of an observing key frame, or -1 where the observation is filtered (:116, :227, :317, :346, :372)
+    auto observer = [&](KeyFrame* k) { if (k->isBad() || k->mnId > maxKFid) return -1; auto it = kf_index.find(k); return it == kf_index.end() ? -1 : it->second; };
+    std::vector<int32_t> pt_lm(vpMP.size(), -1), ln_lm(vpML.size(), -1), pl_lm(vpMPL.size(), -1);
+    for (size_t i = 0; i < vpMP.size(); i++) {
+        MapPoint* p = vpMP[i];
+        if (!p || p->isBad()) continue;
+        cv::Mat X = p->GetWorldPos();
+        pt_lm[i] = add_lm(0, X.at<float>(0), X.at<float>(1), X.at<float>(2), 0);
+        const std::map<KeyFrame*, size_t> obs = p->GetObservations();
+        for (const auto& o : obs) {
+            const int v = observer(o.first);
+            if (v < 0) continue;
+            KeyFrame* k = o.first;
+            const cv::KeyPoint& kp = k->mvKeysUn[o.second];
+            const float ur = k->mvuRight[o.second], is2 = k->mvInvLevelSigma2[kp.octave];
+            if (ur < 0) add_edge(v, pt_lm[i], PLANAR_BA_MONO, kp.pt.x, kp.pt.y, 0, 0, is2);
+            else add_edge(v, pt_lm[i], PLANAR_BA_STEREO, kp.pt.x, kp.pt.y, ur, 0, is2);
+        }
+    }
+    for (size_t i = 0; i < vpML.size(); i++) {
+        MapLine* p = vpML[i];
+        if (!p || p->isBad()) continue;
+        const auto W = p->GetWorldPos();                       // Vector6d: start xyz, end xyz
+        ln_lm[i] = add_lm(0, W[0], W[1], W[2], 0);
+        add_lm(0, W[3], W[4], W[5], 0);
+        const std::map<KeyFrame*, size_t> obs = p->GetObservations();
+        for (const auto& o : obs) {
+            const int v = observer(o.first);
+            if (v < 0) continue;
+            const auto f = o.first->mvKeyLineFunctions[o.second];     // the observer's own line function, both end points on the observer's vertex
+            add_edge(v, ln_lm[i], PLANAR_BA_LINE, f[0], f[1], f[2], 0, 1.f);
+            add_edge(v, ln_lm[i] + 1, PLANAR_BA_LINE, f[0], f[1], f[2], 0, 1.f);
+        }
+    }
+    for (size_t i = 0; i < vpMPL.size(); i++) {
+        MapPlane* p = vpMPL[i];
+        if (!p || p->isBad()) continue;
+        cv::Mat C = p->GetWorldPos();
+        pl_lm[i] = add_lm(1, C.at<float>(0), C.at<float>(1), C.at<float>(2), C.at<float>(3));
+        auto plane_edges = [&](const std::map<KeyFrame*, size_t>& obs, int type) {
+            for (const auto& o : obs) {
+                const int v = observer(o.first);
+                if (v < 0) continue;
+                const cv::Mat& m = o.first->mvPlaneCoefficients[o.second];
+                add_edge(v, pl_lm[i], type, m.at<float>(0), m.at<float>(1), m.at<float>(2), m.at<float>(3), 1.f);
+            }
+        };
+        plane_edges(p->GetObservations(), PLANAR_BA_PLANE);
+        plane_edges(p->GetVerObservations(), PLANAR_BA_VERTICAL);
+        plane_edges(p->GetParObservations(), PLANAR_BA_PARALLEL);
+    }
+    const int NL = (int)lm_type.size(), NE = (int)e_type.size();
+    std::vector<float> out_T((size_t)K * 16);
+    std::vector<double> out_lm((size_t)std::max(NL, 1) * 4);
+    std::vector<uint8_t> out_inc(std::max(NL, 1));
+    planar_ba_problem P{K, kf_Tcw.data(), kf_fixed.data(), NL, lm_type.data(), lm_init.data(), NE, e_kf.data(), e_lm.data(), e_type.data(), e_meas.data(), e_is2.data()};
+    planar_gba_result R{out_T.data(), out_lm.data(), out_inc.data(), 0, 0, 0, 0, 0.0, 0.0};
+    const planar_pose_params prm = planar_adapter::plane_pose_params<Config>(kfs[0]->fx, kfs[0]->fy, kfs[0]->cx, kfs[0]->cy, kfs[0]->mbf);
+    static_assert(sizeof(bool) == 1, "bool* pbStopFlag is passed as a byte flag");
+    if (!planar_adapter::on_lane(planar_adapter::TRACKING, "planar_global_ba", [&](planar_ctx* ctx) {
+            return planar_global_ba(ctx, &P, &prm, nIterations, bRobust ? 1 : 0, &R, reinterpret_cast<const volatile unsigned char*>(pbStopFlag));
+        })) return;
+    // Recover optimized data (:451-547)
+    for (int k = 0; k < K; k++) {
+        const cv::Mat T = planar_adapter::array_to_mat(&out_T[(size_t)k * 16]);
+        if (nLoopKF == 0) kfs[k]->SetPose(T);
+        else { kfs[k]->mTcwGBA.create(4, 4, CV_32F); T.copyTo(kfs[k]->mTcwGBA); kfs[k]->mnBAGlobalForKF = nLoopKF; }
+    }
+    for (size_t i = 0; i < vpMP.size(); i++) {
+        if (pt_lm[i] < 0 || !out_inc[pt_lm[i]]) continue;
+        float x[3];
+        for (int j = 0; j < 3; j++) x[j] = (float)out_lm[(size_t)pt_lm[i] * 4 + j];
+        const cv::Mat X = planar_adapter::array_to_mat(x, 3, 1);
+        if (nLoopKF == 0) { vpMP[i]->SetWorldPos(X); vpMP[i]->UpdateNormalAndDepth(); }
+        else { vpMP[i]->mPosGBA.create(3, 1, CV_32F); X.copyTo(vpMP[i]->mPosGBA); vpMP[i]->mnBAGlobalForKF = nLoopKF; }
+    }
+    for (size_t i = 0; i < vpML.size(); i++) {
+        if (ln_lm[i] < 0 || !out_inc[ln_lm[i]]) continue;
+        const double* s = &out_lm[(size_t)ln_lm[i] * 4];
+        const double* e = &out_lm[(size_t)(ln_lm[i] + 1) * 4];
+        if (nLoopKF == 0) {
+            auto W = vpML[i]->GetWorldPos();
+            for (int j = 0; j < 3; j++) { W[j] = s[j]; W[3 + j] = e[j]; }                 // linePos << vStartPoint->estimate(), vEndPoint->estimate(): doubles
+            vpML[i]->SetWorldPos(W); vpML[i]->UpdateAverageDir();
+        } else {
+            const float x[6] = {(float)s[0], (float)s[1], (float)s[2], (float)e[0], (float)e[1], (float)e[2]};
+            vpML[i]->mPosGBA.create(6, 1, CV_32F); planar_adapter::array_to_mat(x, 6, 1).copyTo(vpML[i]->mPosGBA); vpML[i]->mnBAGlobalForKF = nLoopKF;
+        }
+    }
+    for (size_t i = 0; i < vpMPL.size(); i++) {
+        if (pl_lm[i] < 0 || !out_inc[pl_lm[i]]) continue;
+        float c[4];
+        for (int j = 0; j < 4; j++) c[j] = (float)out_lm[(size_t)pl_lm[i] * 4 + j];
+        const cv::Mat C = planar_adapter::array_to_mat(c, 4, 1);
+        if (nLoopKF == 0) { vpMPL[i]->SetWorldPos(C); vpMPL[i]->UpdateCoefficientsAndPoints(); }
+        else { vpMPL[i]->mPosGBA.create(4, 1, CV_32F); C.copyTo(vpMPL[i]->mPosGBA); vpMPL[i]->mnBAGlobalForKF = nLoopKF; }
+    }
+}
+inline void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, const unsigned long nLoopKF, const bool bRobust) {
+    BundleAdjustment(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), pMap->GetAllMapLines(), pMap->GetAllMapPlanes(), nIterations, pbStopFlag, nLoopKF, bRobust);
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_GLOBAL_BA

@@ -127,6 +127,15 @@ class BAResult(C.Structure):
     _fields_ = [("kf_Tcw", C.c_void_p), ("lm", C.c_void_p), ("e_outlier", C.c_void_p), ("lm_iterations", C.c_int32), ("stopped", C.c_int32)]
 
 
+class GBAResult(C.Structure):
+    """planar_gba_result"""
+    _fields_ = [("kf_Tcw", C.c_void_p), ("lm", C.c_void_p), ("lm_included", C.c_void_p), ("lm_iterations", C.c_int32), ("trials", C.c_int32),
+                ("stopped", C.c_int32), ("status", C.c_int32), ("chi2", C.c_double), ("lambda_", C.c_double)]
+
+
+GBA_MAX_KF = 256             # PLANAR_GBA_MAX_KF
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "planar_last_error": (C.c_char_p, []),
@@ -299,6 +308,7 @@ _SIGS = {
     "planar_comm_create_hosted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "planar_comm_destroy": (None, [C.c_void_p]),
     "planar_local_ba": (C.c_int, [C.c_void_p, C.POINTER(BAProblem), C.POINTER(PoseParams), C.c_int, C.c_int, C.POINTER(BAResult), C.c_void_p, C.c_void_p]),
+    "planar_global_ba": (C.c_int, [C.c_void_p, C.POINTER(BAProblem), C.POINTER(PoseParams), C.c_int, C.c_int, C.POINTER(GBAResult), C.c_void_p]),
     "planar_stereo_from_rgbd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64] + [C.c_float] * 6 + [C.c_void_p] * 5),
     "planar_stereo_from_rgbd_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64] + [C.c_float] * 6 + [C.c_void_p] * 5),
     "planar_pose_assemble": (C.c_int, [C.c_void_p, C.POINTER(TrackMatches), C.POINTER(PoseBatch)]),

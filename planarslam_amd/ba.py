@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import BAProblem, BAResult, Context, check, lib
+from ._lib import BAProblem, BAResult, Context, GBAResult, check, lib
 from .optimizer import make_params
 
 _KEYS = ("kf_Tcw", "kf_fixed", "lm_type", "lm_init", "e_kf", "e_lm", "e_type", "e_meas", "e_inv_sigma2")
@@ -108,4 +108,25 @@ def local_bundle_adjustment(prob: dict, params: dict, its1: int = 5, its2: int =
     prm = make_params(params)
     check(L.planar_local_ba(ctx.h, C.byref(P), C.byref(prm), its1, its2, C.byref(R), C.byref(stop_flag) if stop_flag is not None else None, comm.h if comm else None))
     out["lm_iters"], out["stopped"] = R.lm_iterations, R.stopped
+    return out
+
+
+GBA_STATUS = {1: "converged", 2: "iteration limit", 3: "stopped"}
+
+
+def global_bundle_adjustment(prob: dict, params: dict, iterations: int = 10, robust: bool = False, ctx: Context | None = None, stop_flag=None):
+    """Runs planar_global_ba (Optimizer::BundleAdjustment as GlobalBundleAdjustemnt calls it, reference src/Optimizer.cc:35-548) on a synth.ba_problem()-style dict
+    whose line edges name their observing key frame.  Returns kf_Tcw, lm, lm_included, lm_iters, trials, stopped, status, chi2, lambda.  Single GPU."""
+    L = lib()
+    ctx = ctx or Context(0)
+    a = {k: np.ascontiguousarray(prob[k]) for k in _KEYS}
+    K, NL = len(a["kf_fixed"]), len(a["lm_type"])
+    out = dict(kf_Tcw=np.zeros((K, 16), np.float32), lm=np.zeros((NL, 4), np.float64), lm_included=np.zeros(NL, np.uint8))
+    P = BAProblem(K, a["kf_Tcw"].ctypes.data, a["kf_fixed"].ctypes.data, NL, a["lm_type"].ctypes.data, a["lm_init"].ctypes.data, len(a["e_kf"]),
+                  a["e_kf"].ctypes.data, a["e_lm"].ctypes.data, a["e_type"].ctypes.data, a["e_meas"].ctypes.data, a["e_inv_sigma2"].ctypes.data)
+    R = GBAResult(out["kf_Tcw"].ctypes.data, out["lm"].ctypes.data, out["lm_included"].ctypes.data, 0, 0, 0, 0, 0.0, 0.0)
+    prm = make_params(params)
+    check(L.planar_global_ba(ctx.h, C.byref(P), C.byref(prm), int(iterations), 1 if robust else 0, C.byref(R), C.byref(stop_flag) if stop_flag is not None else None))
+    out.update(lm_iters=R.lm_iterations, trials=R.trials, stopped=R.stopped, status=R.status, chi2=R.chi2)
+    out["lambda"] = R.lambda_
     return out
