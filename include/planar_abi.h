@@ -1095,6 +1095,97 @@ int planar_bow_score(planar_ctx* ctx, int P, const int32_t* a_bow_n, const int32
 int planar_bow_score_dev(planar_ctx* ctx, int P, const int32_t* d_a_bow_n, const int32_t* d_a_bow_word, const double* d_a_bow_value, int a_stride,
                          const int32_t* d_b_bow_n, const int32_t* d_b_bow_word, const double* d_b_bow_value, int b_stride, double* d_out);
 
+/* ---- the local map of a tracked frame (replaces Tracking::UpdateLocalMap, src/Tracking.cc:2394-2405, the first statement of TrackLocalMap, :1954: UpdateLocalKeyFrames
+ *      :2458-2552, UpdateLocalPoints :2434-2455, UpdateLocalLines :2407-2432, and the head loops of SearchLocalPoints :2289-2312 / SearchLocalLines :2334-2358) ----
+ * A map is what the tracking thread reads of Map / KeyFrame / MapPoint / MapLine, as indices: key frames, map points and map lines are named by their position in
+ * the map's arrays, -1 = NULL / none.  G maps, padded like every other view; frame b of a call reads map map_of[b] (several frames may share one).  Limit: */
+#define PLANAR_LOCALMAP_MAX_KEYFRAMES 1024 /* kf_stride: key frames of one map (= PLANAR_KFDB_MAX_KEYFRAMES) */
+typedef struct planar_local_map {
+    int32_t n_maps;              /* G */
+    int32_t kf_stride, slot_stride, line_slot_stride, pt_stride, ml_stride, obs_cap, child_cap;
+    const int32_t* n_kf;         /* [G]                              key frames in use                                                             */
+    const uint8_t* kf_bad;       /* [G][kf_stride]                   KeyFrame::isBad()                                                             */
+    const int32_t* kf_rank;      /* [G][kf_stride]                   position of the key frame in std::less<KeyFrame*> order: a permutation of [0, n_kf) */
+    const int32_t* covis;        /* [G][kf_stride][10]               GetBestCovisibilityKeyFrames(10), -1 = none                                   */
+    const int32_t* parent;       /* [G][kf_stride]                   GetParent(), -1 = none                                                        */
+    const int32_t* child_off;    /* [G][kf_stride + 1]               GetChilds() of key frame k = child[g][child_off[k] .. child_off[k + 1])       */
+    const int32_t* child;        /* [G][child_cap]                   in the std::set's own (pointer) order                                         */
+    const int32_t* n_slots;      /* [G][kf_stride]                   GetMapPointMatches().size()                                                   */
+    const int32_t* kf_pts;       /* [G][kf_stride][slot_stride]      GetMapPointMatches(): map-point ids, -1 = NULL                                */
+    const int32_t* n_line_slots; /* [G][kf_stride]                   GetMapLineMatches().size()                                                    */
+    const int32_t* kf_lines;     /* [G][kf_stride][line_slot_stride] map-line ids, -1 = NULL                                                       */
+    const int32_t* n_pts;        /* [G]                              map points in use                                                             */
+    const uint8_t* pt_bad;       /* [G][pt_stride]                   MapPoint::isBad()                                                             */
+    const int32_t* obs_off;      /* [G][pt_stride + 1]               GetObservations() of point p = obs_kf[g][obs_off[p] .. obs_off[p + 1])        */
+    const int32_t* obs_kf;       /* [G][obs_cap]                     the observing key frames                                                      */
+    const float* pt_xw;          /* [G][pt_stride][3]                GetWorldPos()                                                                 */
+    const float* pt_normal;      /* [G][pt_stride][3]                GetNormal()                                                                   */
+    const float* pt_min_dist;    /* [G][pt_stride]                   mfMinDistance                                                                 */
+    const float* pt_max_dist;    /* [G][pt_stride]                   mfMaxDistance                                                                 */
+    const uint8_t* pt_desc;      /* [G][pt_stride][32]               GetDescriptor(); must start on a 4-byte boundary                              */
+    const int32_t* n_ml;         /* [G]                              map lines in use                                                              */
+    const uint8_t* ml_bad;       /* [G][ml_stride]                   MapLine::isBad()                                                              */
+    const uint8_t* ml_observed;  /* [G][ml_stride]                   Observations() > 0                                                            */
+    const double* ml_xw6;        /* [G][ml_stride][6]                GetWorldPos(); the doubles must start on an 8-byte boundary                   */
+    const double* ml_normal;     /* [G][ml_stride][3]                GetNormal()                                                                   */
+    const float* ml_min_dist;    /* [G][ml_stride]                                                                                                 */
+    const float* ml_max_dist;    /* [G][ml_stride]                                                                                                 */
+    const uint8_t* ml_desc;      /* [G][ml_stride][32]               GetDescriptor(); must start on a 4-byte boundary                              */
+} planar_local_map;
+/* The per-batch workspace: per frame the local key-frame list and two per-key-frame prefix counts (12 * kf_stride bytes), a position mark and an "already in the
+ * frame" byte per map point and per map line (5 * pt_stride + 5 * ml_stride bytes) and 32 bytes of state, i.e. 12 * kf_stride + 5 * (pt_stride + ml_stride) + 32
+ * bytes per frame of max_batch, allocated by the first call on the handle (creating it touches no device).  A call on maps with larger strides than the
+ * workspace was made for is PLANAR_EINVAL. */
+typedef struct planar_local_map_ws planar_local_map_ws;
+int planar_local_map_ws_create(planar_ctx* ctx, int max_batch, int kf_stride, int pt_stride, int ml_stride, planar_local_map_ws** out);
+void planar_local_map_ws_destroy(planar_local_map_ws* ws);
+/* HIP-event timing of the launches of planar_update_local_map_dev, as planar_plane_clouds_set_profiling: total_ms [5] = the two memsets, localmap_keyframes,
+ * localmap_mark, localmap_count, localmap_gather (points and lines) over `calls` recorded calls (tools/local_map_bench.py reads them) */
+int planar_local_map_ws_set_profiling(planar_local_map_ws* ws, int enable);
+int planar_local_map_ws_get_profile(planar_local_map_ws* ws, double* total_ms, int64_t* calls);
+/* Tracking::UpdateLocalMap for B frames.  `map` is a HOST pointer in both flavours (its arrays are device arrays in the _dev one); every other array follows the
+ * flavour.  The arrays of frame b:
+ *   n_frame [B], frame_match [B][frame_stride]   in/out: mCurrentFrame.N and mvpMapPoints as map-point ids; a bad point's entry becomes -1 (:2470, :2294)
+ *   n_frame_lines [B], frame_line_match [B][frame_line_stride]   in/out: NL and mvpMapLines likewise (:2339)
+ *   local_kf [B][local_kf_stride], n_local_kf [B]   in/out: mvpLocalKeyFrames; rewritten unless the vote is empty
+ *   ref_kf [B]   mpReferenceKF = pKFmax, or -1: keep the one you have (empty vote, or every voted key frame bad)
+ *   lp_id [B][lp_stride], n_lp [B]   mvpLocalMapPoints as ids, in the reference's order, and per listed point j the inputs of the next two calls in their layouts:
+ *       lp_valid, lp_xw [..][3], lp_normal [..][3], lp_min_dist, lp_max_dist  ->  planar_is_in_frustum_points_dev (n = n_lp, stride = lp_stride)
+ *       lp_desc [..][32], lp_observed (GetObservations() non-empty)           ->  planar_map_probes
+ *       lp_valid[j] = 0 where the frame holds the point already (frame_match names it once the bad ones are nulled): mnLastFrameSeen == mCurrentFrame.mnId (:2309)
+ *   ll_id [B][ll_stride], n_ll [B], ll_valid, ll_xw6 [..][6], ll_normal [..][3] (double), ll_min_dist, ll_max_dist, ll_desc [..][32], ll_observed: mvpLocalMapLines
+ *       likewise, for planar_is_in_frustum_lines_dev and planar_lsd_search_by_projection_dev; ll_valid honours frame_line_match (:2356)
+ *   status [B]   0 ok; 1 empty vote, the list that came in was kept; 3 an output list was longer than its stride: its count reports the full length and nothing is
+ *       written at or beyond the stride; 2 an index read from the map or the frame was out of range: the frame's lists are empty (n_lp = n_ll = 0), local_kf /
+ *       n_local_kf are left as they came in, ref_kf = -1 (matches nulled before the index was met stay nulled).  Nothing is ever read or written out of bounds.
+ * Kept as the reference has it:
+ *   vote       every key point with a match >= 0 whose point is not bad gives +1 to each key frame of the point's observation list (:2460-2473)
+ *   empty vote no key frame got a vote (bad ones count here, it is keyframeCounter.empty()): return, the previous mvpLocalKeyFrames stays (:2475) and the points
+ *              and lines are still rebuilt from it
+ *   voted list std::map<KeyFrame*, int> iterates in pointer order = ascending kf_rank; a bad key frame is neither listed, nor marked, nor a candidate for the
+ *              maximum; pKFmax on `>` from 0: the first of equal counts wins (:2485-2499)
+ *   expansion  over the VOTED entries only (the end iterator is taken once, :2503): `size > 80` at the top of an iteration ends the loop, on the live size, so the
+ *              list can end at 83; per key frame the first covis entry that is neither bad nor marked, then the first such child, then the parent if it is not
+ *              marked - isBad() is not asked of the parent, and appending the parent ends the WHOLE loop (the break of :2542 sits in the outer for)
+ *   lists      local key frames in list order, slots in slot order; a point / line is kept at its first occurrence if it is neither NULL nor bad
+ * A mark (mnTrackReferenceForFrame == mCurrentFrame.mnId) is per frame of the call: frames of one batch that share a map do not see each other's marks, nor does
+ * the next call.  IncreaseVisible and the other counters of SearchLocalPoints / SearchLocalLines stay the caller's.
+ * PLANAR_EINVAL before any HIP call: a null argument or map array, B < 1 or above the workspace's max_batch, kf_stride outside [1, PLANAR_LOCALMAP_MAX_KEYFRAMES],
+ * any other stride or capacity < 1 (slot strides above 2^20), strides above the workspace's, misaligned descriptor / double arrays.  The host-pointer flavour also
+ * walks the maps 0 .. n_maps - 1 and the frames on the host and returns PLANAR_EINVAL, before it touches a device, for every index the kernels could meet out of
+ * range (observation key frames, slot contents, covis, children, parent, kf_rank, map_of, frame_match, frame_line_match, the incoming local_kf, the counts). */
+int planar_update_local_map(planar_local_map_ws* ws, const planar_local_map* map, int B, const int32_t* map_of, const int32_t* n_frame, int32_t* frame_match,
+                            int frame_stride, const int32_t* n_frame_lines, int32_t* frame_line_match, int frame_line_stride, int32_t* local_kf, int32_t* n_local_kf,
+                            int local_kf_stride, int32_t* ref_kf, int32_t* lp_id, int32_t* n_lp, uint8_t* lp_valid, float* lp_xw, float* lp_normal, float* lp_min_dist,
+                            float* lp_max_dist, uint8_t* lp_desc, uint8_t* lp_observed, int lp_stride, int32_t* ll_id, int32_t* n_ll, uint8_t* ll_valid, double* ll_xw6,
+                            double* ll_normal, float* ll_min_dist, float* ll_max_dist, uint8_t* ll_desc, uint8_t* ll_observed, int ll_stride, int32_t* status);
+int planar_update_local_map_dev(planar_local_map_ws* ws, const planar_local_map* map, int B, const int32_t* d_map_of, const int32_t* d_n_frame, int32_t* d_frame_match,
+                                int frame_stride, const int32_t* d_n_frame_lines, int32_t* d_frame_line_match, int frame_line_stride, int32_t* d_local_kf,
+                                int32_t* d_n_local_kf, int local_kf_stride, int32_t* d_ref_kf, int32_t* d_lp_id, int32_t* d_n_lp, uint8_t* d_lp_valid, float* d_lp_xw,
+                                float* d_lp_normal, float* d_lp_min_dist, float* d_lp_max_dist, uint8_t* d_lp_desc, uint8_t* d_lp_observed, int lp_stride,
+                                int32_t* d_ll_id, int32_t* d_n_ll, uint8_t* d_ll_valid, double* d_ll_xw6, double* d_ll_normal, float* d_ll_min_dist,
+                                float* d_ll_max_dist, uint8_t* d_ll_desc, uint8_t* d_ll_observed, int ll_stride, int32_t* d_status);
+
 /* ---- 3-D line back-projection (replaces Frame::isLineGood, src/Frame.cc:189-267, with compPt3dCov / extract3dline_mahdist / verify3dLine /
  *      mah_dist3d_pt_line / computeLine3d_svd of src/LineExtractor.cpp:1157-1470) ----
  * keylines [B][ln_stride] = Frame::mvKeylinesUn, depth = the u16 depth image (imDepth = value * depth_factor), fx.. = Frame::fx.. (K(0,0) of compPt3dCov is fx).

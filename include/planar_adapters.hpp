@@ -8,6 +8,7 @@
 //   ORBmatcher::Fuse / LSDmatcher::Fuse (search on the device, map edits as in the reference)         (PLANAR_ADAPTERS_WITH_FUSE, needs one accessor, see there)
 //   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
+//   Tracking::UpdateLocalMap                                                                          (PLANAR_ADAPTERS_WITH_LOCAL_MAP)
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
@@ -1207,6 +1208,167 @@ namespace Planar_SLAM {
 typedef planar_adapter::KeyFrameDatabaseT<KeyFrame, Frame, ORBVocabulary> KeyFrameDatabase;
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_KFDB
+
+// ---- Tracking::UpdateLocalMap (src/Tracking.cc:2394-2552).  Enabled with PLANAR_ADAPTERS_WITH_LOCAL_MAP, after the reference's Tracking.h, Map.h, KeyFrame.h,
+//      MapPoint.h and MapLine.h; leave that body of src/Tracking.cc (with UpdateLocalKeyFrames / UpdateLocalPoints / UpdateLocalLines, which it alone calls) out.
+//      This form RE-PACKS THE MAP ON EVERY CALL: mpMap->GetAllKeyFrames() / GetAllMapPoints() / GetAllMapLines() name the objects (ids are positions in those
+//      vectors; an object they do not hold but a key frame, an observation or the frame refers to - a bad parent, for one - is appended behind them), kf_rank is
+//      std::less<KeyFrame*> over the pointers, children come in the std::set's own order, covis from GetBestCovisibilityKeyFrames(10), observations from
+//      GetObservations().  It is the correctness path; the throughput path is planar_update_local_map_dev on a resident map.  The gathered rows
+//      (positions, normals, descriptors) are not needed here and are passed as zeros.  The call runs with B = 1 on the tracking lane; a failing call, or a map of
+//      more than PLANAR_LOCALMAP_MAX_KEYFRAMES key frames, changes nothing and reports on stderr.  As in the reference, the frame's bad map points become NULL
+//      (:2470); its bad map lines are left to SearchLocalLines.
+#ifdef PLANAR_ADAPTERS_WITH_LOCAL_MAP
+#include <set>
+namespace Planar_SLAM {
+inline void Tracking::UpdateLocalMap() {
+    mpMap->SetReferenceMapPoints(mvpLocalMapPoints);      // This is for visualization (:2396-2397)
+    mpMap->SetReferenceMapLines(mvpLocalMapLines);
+    std::vector<KeyFrame*> K = mpMap->GetAllKeyFrames();
+    std::vector<MapPoint*> P = mpMap->GetAllMapPoints();
+    std::vector<MapLine*> ML = mpMap->GetAllMapLines();
+    std::map<KeyFrame*, int32_t> kf_id;
+    std::map<MapPoint*, int32_t> pt_id;
+    std::map<MapLine*, int32_t> ml_id;
+    for (size_t i = 0; i < K.size(); i++) kf_id[K[i]] = (int32_t)i;
+    for (size_t i = 0; i < P.size(); i++) pt_id[P[i]] = (int32_t)i;
+    for (size_t i = 0; i < ML.size(); i++) ml_id[ML[i]] = (int32_t)i;
+    auto kf_of = [&](KeyFrame* p) -> int32_t {
+        if (!p) return -1;
+        auto it = kf_id.find(p);
+        if (it != kf_id.end()) return it->second;
+        K.push_back(p);
+        return kf_id[p] = (int32_t)K.size() - 1;
+    };
+    auto pt_of = [&](MapPoint* p) -> int32_t {
+        if (!p) return -1;
+        auto it = pt_id.find(p);
+        if (it != pt_id.end()) return it->second;
+        P.push_back(p);
+        return pt_id[p] = (int32_t)P.size() - 1;
+    };
+    auto ml_of = [&](MapLine* p) -> int32_t {
+        if (!p) return -1;
+        auto it = ml_id.find(p);
+        if (it != ml_id.end()) return it->second;
+        ML.push_back(p);
+        return ml_id[p] = (int32_t)ML.size() - 1;
+    };
+    // the frame and the incoming list first, then every key frame and point reached, until nothing new turns up
+    const int N = mCurrentFrame.N, NL = (int)mCurrentFrame.mvpMapLines.size();
+    std::vector<int32_t> frame_match(N > 0 ? N : 1, -1), frame_line_match(NL > 0 ? NL : 1, -1), local_in;
+    for (int i = 0; i < N; i++) frame_match[i] = pt_of(mCurrentFrame.mvpMapPoints[i]);
+    for (int i = 0; i < NL; i++) frame_line_match[i] = ml_of(mCurrentFrame.mvpMapLines[i]);
+    for (KeyFrame* pKF : mvpLocalKeyFrames) local_in.push_back(kf_of(pKF));
+    std::vector<std::vector<int32_t>> covis_of, child_of, slots_of, lslots_of, obs_of;
+    std::vector<int32_t> parent_of;
+    size_t kdone = 0, pdone = 0;
+    while (kdone < K.size() || pdone < P.size()) {
+        for (; kdone < K.size() && K.size() <= PLANAR_LOCALMAP_MAX_KEYFRAMES; kdone++) {
+            KeyFrame* pKF = K[kdone];
+            std::vector<int32_t> c, ch, sl, ls;
+            const std::vector<KeyFrame*> vNeighs = pKF->GetBestCovisibilityKeyFrames(10);
+            for (size_t t = 0; t < vNeighs.size() && t < 10; t++) c.push_back(kf_of(vNeighs[t]));
+            const std::set<KeyFrame*> spChilds = pKF->GetChilds();
+            for (KeyFrame* pChild : spChilds) ch.push_back(kf_of(pChild));
+            const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();
+            for (MapPoint* pMP : vpMPs) sl.push_back(pt_of(pMP));
+            const std::vector<MapLine*> vpMLs = pKF->GetMapLineMatches();
+            for (MapLine* pML : vpMLs) ls.push_back(ml_of(pML));
+            parent_of.push_back(kf_of(pKF->GetParent()));
+            covis_of.push_back(c); child_of.push_back(ch); slots_of.push_back(sl); lslots_of.push_back(ls);
+        }
+        if (K.size() > PLANAR_LOCALMAP_MAX_KEYFRAMES) {
+            std::fprintf(stderr, "planar (UpdateLocalMap): more than %d key frames - the local map is left as it is\n", PLANAR_LOCALMAP_MAX_KEYFRAMES);
+            return;
+        }
+        for (; pdone < P.size(); pdone++) {
+            std::vector<int32_t> o;
+            const std::map<KeyFrame*, size_t> observations = P[pdone]->GetObservations();
+            for (const auto& kv : observations) o.push_back(kf_of(kv.first));
+            obs_of.push_back(o);
+        }
+    }
+    const size_t nk = K.size(), np = P.size(), nl = ML.size();
+    if (nk == 0) return;
+    const size_t S = nk, PS = np ? np : 1, LS = nl ? nl : 1;
+    size_t SS = 1, LSS = 1, OC = 1, CC = 1;
+    for (size_t k = 0; k < nk; k++) { SS = std::max(SS, slots_of[k].size()); LSS = std::max(LSS, lslots_of[k].size()); }
+    std::vector<uint8_t> kf_bad(S), pt_bad(PS, 0), ml_bad(LS, 0), ml_observed(LS, 1);
+    std::vector<int32_t> kf_rank(S), covis(S * 10, -1), parent(parent_of), child_off(S + 1, 0), child, n_slots(S), kf_pts(S * SS, -1), n_lslots(S), kf_lines(S * LSS, -1),
+        obs_off(PS + 1, 0), obs_kf;
+    {
+        int32_t r = 0;
+        for (const auto& kv : kf_id) kf_rank[kv.second] = r++;      // std::map<KeyFrame*, ...>: std::less<KeyFrame*>, the order of the reference's keyframeCounter
+    }
+    for (size_t k = 0; k < nk; k++) {
+        kf_bad[k] = K[k]->isBad();
+        std::copy(covis_of[k].begin(), covis_of[k].end(), covis.begin() + k * 10);
+        child.insert(child.end(), child_of[k].begin(), child_of[k].end());
+        child_off[k + 1] = (int32_t)child.size();
+        n_slots[k] = (int32_t)slots_of[k].size(); std::copy(slots_of[k].begin(), slots_of[k].end(), kf_pts.begin() + k * SS);
+        n_lslots[k] = (int32_t)lslots_of[k].size(); std::copy(lslots_of[k].begin(), lslots_of[k].end(), kf_lines.begin() + k * LSS);
+    }
+    for (size_t p = 0; p < np; p++) {
+        pt_bad[p] = P[p]->isBad();
+        obs_kf.insert(obs_kf.end(), obs_of[p].begin(), obs_of[p].end());
+        obs_off[p + 1] = (int32_t)obs_kf.size();
+    }
+    for (size_t p = np; p < PS; p++) obs_off[p + 1] = obs_off[np];
+    for (size_t l = 0; l < nl; l++) ml_bad[l] = ML[l]->isBad();
+    OC = std::max(OC, obs_kf.size()); CC = std::max(CC, child.size());
+    obs_kf.resize(OC, 0); child.resize(CC, 0);
+    // the rows the next calls would read are not needed here: zeros
+    std::vector<float> zf(std::max(PS * 3, LS), 0.f);
+    std::vector<double> zd(LS * 6, 0.0);
+    std::vector<uint8_t> zb(std::max(PS, LS) * 32, 0);
+    planar_local_map m;
+    m.n_maps = 1; m.kf_stride = (int32_t)S; m.slot_stride = (int32_t)SS; m.line_slot_stride = (int32_t)LSS; m.pt_stride = (int32_t)PS; m.ml_stride = (int32_t)LS;
+    m.obs_cap = (int32_t)OC; m.child_cap = (int32_t)CC;
+    const int32_t n_kf = (int32_t)nk, n_pts = (int32_t)np, n_ml = (int32_t)nl, map_of = 0, n_frame = N > 0 ? N : 0, n_frame_lines = NL;
+    m.n_kf = &n_kf; m.kf_bad = kf_bad.data(); m.kf_rank = kf_rank.data(); m.covis = covis.data(); m.parent = parent.data(); m.child_off = child_off.data();
+    m.child = child.data(); m.n_slots = n_slots.data(); m.kf_pts = kf_pts.data(); m.n_line_slots = n_lslots.data(); m.kf_lines = kf_lines.data(); m.n_pts = &n_pts;
+    m.pt_bad = pt_bad.data(); m.obs_off = obs_off.data(); m.obs_kf = obs_kf.data(); m.pt_xw = zf.data(); m.pt_normal = zf.data(); m.pt_min_dist = zf.data();
+    m.pt_max_dist = zf.data(); m.pt_desc = zb.data(); m.n_ml = &n_ml; m.ml_bad = ml_bad.data(); m.ml_observed = ml_observed.data(); m.ml_xw6 = zd.data();
+    m.ml_normal = zd.data(); m.ml_min_dist = zf.data(); m.ml_max_dist = zf.data(); m.ml_desc = zb.data();
+    // every point / line can be listed at most once, every key frame too
+    std::vector<int32_t> local_kf(S, -1), lp_id(PS, -1), ll_id(LS, -1);
+    std::copy(local_in.begin(), local_in.begin() + std::min(local_in.size(), S), local_kf.begin());
+    int32_t n_local_kf = (int32_t)std::min(local_in.size(), S), ref_kf = -1, n_lp = 0, n_ll = 0, status = 0;
+    std::vector<uint8_t> lp_u8(PS * 2), ll_u8(LS * 2), lp_desc(PS * 32), ll_desc(LS * 32);
+    std::vector<float> lp_f(PS * 8), ll_f(LS * 2);
+    std::vector<double> ll_d(LS * 9);
+    std::vector<int32_t> line_match_copy(frame_line_match);       // the lines' nulling is SearchLocalLines' (:2339); the frame's own vector is not touched here
+    const bool done = planar_adapter::on_lane(planar_adapter::TRACKING, "planar_update_local_map", [&](planar_ctx* ctx) -> int {
+        planar_local_map_ws* ws = nullptr;
+        int rc = planar_local_map_ws_create(ctx, 1, (int)S, (int)PS, (int)LS, &ws);
+        if (rc != PLANAR_OK) return rc;
+        rc = planar_update_local_map(ws, &m, 1, &map_of, &n_frame, frame_match.data(), (int)frame_match.size(), &n_frame_lines, line_match_copy.data(),
+                                     (int)line_match_copy.size(), local_kf.data(), &n_local_kf, (int)S, &ref_kf, lp_id.data(), &n_lp, lp_u8.data(), lp_f.data(),
+                                     lp_f.data() + PS * 3, lp_f.data() + PS * 6, lp_f.data() + PS * 7, lp_desc.data(), lp_u8.data() + PS, (int)PS, ll_id.data(), &n_ll,
+                                     ll_u8.data(), ll_d.data(), ll_d.data() + LS * 6, ll_f.data(), ll_f.data() + LS, ll_desc.data(), ll_u8.data() + LS, (int)LS, &status);
+        planar_local_map_ws_destroy(ws);
+        return rc;
+    });
+    if (!done) return;
+    if (status != 0 && status != 1) {
+        std::fprintf(stderr, "planar (UpdateLocalMap): frame status %d - the local map is left as it is\n", (int)status);
+        return;
+    }
+    for (int i = 0; i < N; i++)
+        if (frame_match[i] < 0 && mCurrentFrame.mvpMapPoints[i]) mCurrentFrame.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);     // :2470
+    if (status == 0) {                                                                                                             // :2481-2499, :2548-2551
+        mvpLocalKeyFrames.clear();
+        for (int i = 0; i < n_local_kf; i++) mvpLocalKeyFrames.push_back(K[local_kf[i]]);
+        if (ref_kf >= 0) { mpReferenceKF = K[ref_kf]; mCurrentFrame.mpReferenceKF = mpReferenceKF; }
+    }
+    mvpLocalMapPoints.clear();
+    for (int i = 0; i < n_lp; i++) mvpLocalMapPoints.push_back(P[lp_id[i]]);
+    mvpLocalMapLines.clear();
+    for (int i = 0; i < n_ll; i++) mvpLocalMapLines.push_back(ML[ll_id[i]]);
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_LOCAL_MAP
 
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.

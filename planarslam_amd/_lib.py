@@ -119,6 +119,17 @@ class KfDatabase(C.Structure):
     _fields_ = [("kf_stride", C.c_int32), ("word_stride", C.c_int32)] + [(n, C.c_void_p) for n in ("n_kf", "present", "add_seq", "bow_n", "bow_word", "bow_value", "covis")]
 
 
+class LocalMapView(C.Structure):
+    """planar_local_map"""
+    _fields_ = [(n, C.c_int32) for n in ("n_maps", "kf_stride", "slot_stride", "line_slot_stride", "pt_stride", "ml_stride", "obs_cap", "child_cap")] + \
+               [(n, C.c_void_p) for n in ("n_kf", "kf_bad", "kf_rank", "covis", "parent", "child_off", "child", "n_slots", "kf_pts", "n_line_slots", "kf_lines", "n_pts",
+                                          "pt_bad", "obs_off", "obs_kf", "pt_xw", "pt_normal", "pt_min_dist", "pt_max_dist", "pt_desc", "n_ml", "ml_bad", "ml_observed",
+                                          "ml_xw6", "ml_normal", "ml_min_dist", "ml_max_dist", "ml_desc")]
+
+
+LOCALMAP_MAX_KEYFRAMES = 1024   # PLANAR_LOCALMAP_MAX_KEYFRAMES
+_UPDATE_LOCAL_MAP = [C.c_void_p, C.POINTER(LocalMapView), C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + \
+                    [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
 KFDB_MAX_WORDS = 4096        # PLANAR_KFDB_MAX_WORDS
 KFDB_MAX_KEYFRAMES = 1024    # PLANAR_KFDB_MAX_KEYFRAMES
 
@@ -260,6 +271,12 @@ _SIGS = {
     "planar_kfdb_detect_dev": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(KfDatabase), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7),
     "planar_bow_score": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     "planar_bow_score_dev": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
+    "planar_local_map_ws_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "planar_local_map_ws_destroy": (None, [C.c_void_p]),
+    "planar_local_map_ws_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
+    "planar_local_map_ws_get_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "planar_update_local_map": (C.c_int, _UPDATE_LOCAL_MAP),
+    "planar_update_local_map_dev": (C.c_int, _UPDATE_LOCAL_MAP),
     "planar_search_by_bow_kf": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_bow_kf_dev": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_projection_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
