@@ -1186,6 +1186,55 @@ int planar_update_local_map_dev(planar_local_map_ws* ws, const planar_local_map*
                                 int32_t* d_ll_id, int32_t* d_n_ll, uint8_t* d_ll_valid, double* d_ll_xw6, double* d_ll_normal, float* d_ll_min_dist,
                                 float* d_ll_max_dist, uint8_t* d_ll_desc, uint8_t* d_ll_observed, int ll_stride, int32_t* d_status);
 
+/* ---- the covisibility graph of the maps of a planar_local_map (replaces KeyFrame::UpdateConnections, src/KeyFrame.cc:298-432, with AddConnection :132-145 and
+ *      UpdateBestCovisibles :147-166; the one author of the covis and parent rows planar_update_local_map reads) ----
+ * The connection state of every key frame of the G maps, in the map's kf_stride (S below).  Every array but kf_mnid is in/out. */
+typedef struct planar_covis_graph {
+    int32_t* conn_w;           /* [G][S][S]   row x = mConnectedKeyFrameWeights of key frame x; 0 = absent (the reference stores no weight below 1)      */
+    int32_t* ord_n;            /* [G][S]      mvpOrderedConnectedKeyFrames.size()                                                                        */
+    int32_t* ord_kf;           /* [G][S][S]   mvpOrderedConnectedKeyFrames                                                                               */
+    int32_t* ord_w;            /* [G][S][S]   mvOrderedWeights                                                                                           */
+    uint8_t* first_connection; /* [G][S]      mbFirstConnection                                                                                          */
+    const int32_t* kf_mnid;    /* [G][S]      mnId (only `!= 0` is asked); input                                                                         */
+    int32_t* parent;           /* [G][S]      mpParent, -1 = none; may be the array planar_local_map.parent points at                                    */
+    int32_t* covis;            /* [G][S][10]  the first ten of the ordered list, -1 = none; may be the array planar_local_map.covis points at            */
+} planar_covis_graph;
+/* The per-call workspace: a counter row of kf_stride ints and 16 bytes of state per entry of max_entries, and the place in the list of every key frame of
+ * max_maps maps (4 * (max_entries * (kf_stride + 4) + max_maps * kf_stride) bytes), allocated by the first call on the handle (creating it touches no device).  A
+ * call with more entries, more maps or a larger kf_stride than the workspace was made for is PLANAR_EINVAL. */
+typedef struct planar_connections_ws planar_connections_ws;
+int planar_connections_ws_create(planar_ctx* ctx, int max_entries, int max_maps, int kf_stride, planar_connections_ws** out);
+void planar_connections_ws_destroy(planar_connections_ws* ws);
+/* HIP-event timing of the launches of planar_update_connections_dev, as planar_local_map_ws_set_profiling: total_ms [3] = the memset with connections_register,
+ * connections_count, connections_apply over `calls` recorded calls (tools/connections_bench.py reads them) */
+int planar_connections_ws_set_profiling(planar_connections_ws* ws, int enable);
+int planar_connections_ws_get_profile(planar_connections_ws* ws, double* total_ms, int64_t* calls);
+/* The state the reference reaches by calling UpdateConnections() on the L key frames (entry_map[l], entry_kf[l]) IN LIST ORDER.  `map` and `graph` are HOST
+ * structs in both flavours (their arrays are device arrays in the _dev one); the four arrays [L] follow the flavour.  Of the map the call reads only n_kf, kf_rank,
+ * n_slots, kf_pts, n_pts, pt_bad, obs_off and obs_kf (and n_maps, kf_stride, slot_stride, pt_stride, obs_cap); the other arrays may be null.
+ *   new_parent [L]  the parent key frame l was given in this call (the caller inserts l among its children), else -1
+ *   status [L]      0 ok; 1 the counter was empty: nothing changed; 2 (_dev only) an index the entry met was out of range (entry_map, entry_kf, n_kf, n_pts,
+ *                   n_slots, slot contents, obs_off, obs_kf, kf_rank), or the list names its key frame twice: the entry has no effect
+ * Kept as the reference has it:
+ *   count      every slot of the key frame whose point is neither NULL nor bad gives +1 to each key frame of the point's observation list but the key frame
+ *              itself (:315-333): a point in two slots counts twice, a point whose list lacks the key frame counts; lines and planes do not vote
+ *   targets    the key frames with count >= 15; if none, the maximum on `>` from 0 in pointer order (ascending kf_rank: the first of equals)
+ *   AddConnection(j, w) on target x: nothing if conn_w[x][j] == w already; else the weight is set and x's ordered list becomes ALL of its row
+ *   own state  row j = the whole counter (stale entries vanish), j's ordered list = the targets only
+ *   order      sort on (weight, KeyFrame*) ascending, reversed: descending weight, ties in DESCENDING pointer order
+ *   parent     if first_connection[j] and kf_mnid[j] != 0: parent[j] = the front of j's list, the flag clears
+ *   covis      rewritten (first ten, padded with -1) for every key frame whose ordered list was written
+ * Entries of different maps are independent.  The list may not name a (map, key frame) twice: the host flavour answers PLANAR_EINVAL, in the _dev flavour every
+ * entry naming it gets status 2.  Entries with status 2 count as not listed.
+ * PLANAR_EINVAL before any HIP call: a null argument, a null array of the graph or of the eight the map must hold, L < 1 or above the workspace's max_entries,
+ * kf_stride outside [1, PLANAR_LOCALMAP_MAX_KEYFRAMES], n_maps / slot_stride / pt_stride / obs_cap < 1 (slot_stride above 2^20), kf_stride or n_maps above the
+ * workspace's.  The host-pointer flavour also walks the maps and the list on the host and returns PLANAR_EINVAL, before it touches a device, for every index the
+ * kernels could meet out of range.  Nothing is ever read or written out of bounds. */
+int planar_update_connections(planar_connections_ws* ws, const planar_local_map* map, const planar_covis_graph* graph, int L, const int32_t* entry_map,
+                              const int32_t* entry_kf, int32_t* new_parent, int32_t* status);
+int planar_update_connections_dev(planar_connections_ws* ws, const planar_local_map* map, const planar_covis_graph* graph, int L, const int32_t* d_entry_map,
+                                  const int32_t* d_entry_kf, int32_t* d_new_parent, int32_t* d_status);
+
 /* ---- 3-D line back-projection (replaces Frame::isLineGood, src/Frame.cc:189-267, with compPt3dCov / extract3dline_mahdist / verify3dLine /
  *      mah_dist3d_pt_line / computeLine3d_svd of src/LineExtractor.cpp:1157-1470) ----
  * keylines [B][ln_stride] = Frame::mvKeylinesUn, depth = the u16 depth image (imDepth = value * depth_factor), fx.. = Frame::fx.. (K(0,0) of compPt3dCov is fx).

@@ -9,6 +9,7 @@
 //   LocalMapping::CreateNewMapPoints up to the candidate list (planar_adapter::CreateNewMapPoints)   (PLANAR_ADAPTERS_WITH_NEW_POINTS)
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
 //   Tracking::UpdateLocalMap                                                                          (PLANAR_ADAPTERS_WITH_LOCAL_MAP)
+//   KeyFrame::UpdateConnections                                                                       (PLANAR_ADAPTERS_WITH_CONNECTIONS)
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
@@ -1369,6 +1370,121 @@ inline void Tracking::UpdateLocalMap() {
 }
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_LOCAL_MAP
+
+// ---- KeyFrame::UpdateConnections (src/KeyFrame.cc:298-432).  Enabled with PLANAR_ADAPTERS_WITH_CONNECTIONS, after the reference's KeyFrame.h and MapPoint.h; leave
+//      that body of src/KeyFrame.cc out (AddConnection, UpdateBestCovisibles and AddChild stay the reference's).  The key frame's map points are copied under
+//      mMutexFeatures and their isBad() / GetObservations() gathered into a ONE-ENTRY problem: key frame ids are places in std::less<KeyFrame*> order of the key
+//      frames met (so kf_rank is the identity), only this key frame has slots, and the graph comes in empty apart from this key frame's mbFirstConnection and
+//      whether its mnId is 0.  planar_update_connections runs with L = 1 on the tracking lane; from its result come the counter (row j), the key frame's ordered
+//      list (exactly the targets, sorted) and the parent.  The targets' own state is the reference's: AddConnection(this, w) is called on each, as :397 / :404 do.
+//      It is the correctness path; the throughput path is planar_update_connections_dev on a resident map.  A failing call, or more than
+//      PLANAR_LOCALMAP_MAX_KEYFRAMES key frames met, changes nothing and reports on stderr.
+#ifdef PLANAR_ADAPTERS_WITH_CONNECTIONS
+#include <map>
+#include <mutex>
+namespace Planar_SLAM {
+inline void KeyFrame::UpdateConnections() {
+    std::vector<MapPoint*> vpMP;
+    {
+        std::unique_lock<std::mutex> lockMPs(mMutexFeatures);
+        vpMP = mvpMapPoints;
+    }
+    std::map<MapPoint*, int32_t> pt_id;
+    std::vector<std::map<KeyFrame*, size_t>> obs_of;
+    std::vector<uint8_t> pt_bad;
+    std::map<KeyFrame*, int32_t> kf_id;                  // std::less<KeyFrame*>: the order of the reference's KFcounter
+    kf_id[this] = 0;
+    std::vector<int32_t> kf_pts(vpMP.size() ? vpMP.size() : 1, -1);
+    for (size_t i = 0; i < vpMP.size(); i++) {
+        MapPoint* pMP = vpMP[i];
+        if (!pMP) continue;
+        auto it = pt_id.find(pMP);
+        if (it == pt_id.end()) {
+            it = pt_id.emplace(pMP, (int32_t)pt_bad.size()).first;
+            const bool bad = pMP->isBad();
+            pt_bad.push_back(bad);
+            obs_of.push_back(bad ? std::map<KeyFrame*, size_t>() : pMP->GetObservations());
+            for (const auto& kv : obs_of.back()) kf_id[kv.first] = 0;
+        }
+        kf_pts[i] = it->second;
+    }
+    if (kf_id.size() > PLANAR_LOCALMAP_MAX_KEYFRAMES) {
+        std::fprintf(stderr, "planar (UpdateConnections): more than %d key frames - the connections are left as they are\n", PLANAR_LOCALMAP_MAX_KEYFRAMES);
+        return;
+    }
+    std::vector<KeyFrame*> K;
+    for (auto& kv : kf_id) { kv.second = (int32_t)K.size(); K.push_back(kv.first); }
+    const size_t S = K.size(), PS = pt_bad.size() ? pt_bad.size() : 1;
+    const int32_t j = kf_id[this];
+    // a self observation is skipped on mnId, not on the pointer (:329): a key frame that shares this one's mnId must not count either
+    std::vector<int32_t> obs_off(PS + 1, 0), obs_kf;
+    for (size_t p = 0; p < obs_of.size(); p++) {
+        for (const auto& kv : obs_of[p])
+            if (kv.first->mnId != mnId) obs_kf.push_back(kf_id[kv.first]);
+        obs_off[p + 1] = (int32_t)obs_kf.size();
+    }
+    for (size_t p = obs_of.size(); p < PS; p++) obs_off[p + 1] = obs_off[obs_of.size()];
+    if (obs_kf.empty()) obs_kf.push_back(0);
+    pt_bad.resize(PS, 0);
+    const size_t SS = kf_pts.size();
+    std::vector<int32_t> kf_rank(S), n_slots(S, 0), slots(S * SS, -1);
+    for (size_t k = 0; k < S; k++) kf_rank[k] = (int32_t)k;
+    n_slots[j] = (int32_t)vpMP.size();
+    std::copy(kf_pts.begin(), kf_pts.end(), slots.begin() + (size_t)j * SS);
+    planar_local_map m{};
+    m.n_maps = 1; m.kf_stride = (int32_t)S; m.slot_stride = (int32_t)SS; m.line_slot_stride = 1; m.pt_stride = (int32_t)PS; m.ml_stride = 1;
+    m.obs_cap = (int32_t)obs_kf.size(); m.child_cap = 1;
+    const int32_t n_kf = (int32_t)S, n_pts = (int32_t)obs_of.size();
+    m.n_kf = &n_kf; m.kf_rank = kf_rank.data(); m.n_slots = n_slots.data(); m.kf_pts = slots.data(); m.n_pts = &n_pts; m.pt_bad = pt_bad.data();
+    m.obs_off = obs_off.data(); m.obs_kf = obs_kf.data();
+    std::vector<int32_t> conn_w(S * S, 0), ord_n(S, 0), ord_kf(S * S, -1), ord_w(S * S, 0), kf_mnid(S, 1), parent(S, -1), covis(S * 10, -1);
+    std::vector<uint8_t> first(S, 0);
+    {
+        std::unique_lock<std::mutex> lockCon(mMutexConnections);
+        first[j] = mbFirstConnection;
+    }
+    kf_mnid[j] = mnId != 0;
+    planar_covis_graph gr;
+    gr.conn_w = conn_w.data(); gr.ord_n = ord_n.data(); gr.ord_kf = ord_kf.data(); gr.ord_w = ord_w.data(); gr.first_connection = first.data();
+    gr.kf_mnid = kf_mnid.data(); gr.parent = parent.data(); gr.covis = covis.data();
+    const int32_t entry_map = 0, entry_kf = j;
+    int32_t new_parent = -1, status = -1;
+    const bool done = planar_adapter::on_lane(planar_adapter::TRACKING, "planar_update_connections", [&](planar_ctx* ctx) -> int {
+        planar_connections_ws* ws = nullptr;
+        int rc = planar_connections_ws_create(ctx, 1, 1, (int)S, &ws);
+        if (rc != PLANAR_OK) return rc;
+        rc = planar_update_connections(ws, &m, &gr, 1, &entry_map, &entry_kf, &new_parent, &status);
+        planar_connections_ws_destroy(ws);
+        return rc;
+    });
+    if (!done) return;
+    if (status == 1) return;                             // This should not happen (:376)
+    if (status != 0) {
+        std::fprintf(stderr, "planar (UpdateConnections): entry status %d - the connections are left as they are\n", (int)status);
+        return;
+    }
+    const int n = ord_n[j];
+    std::map<KeyFrame*, int> KFcounter;
+    for (size_t k = 0; k < S; k++)
+        if (conn_w[(size_t)j * S + k] > 0) KFcounter[K[k]] = conn_w[(size_t)j * S + k];
+    std::vector<KeyFrame*> vpOrdered;
+    std::vector<int> vOrderedWeights;
+    for (int i = 0; i < n; i++) { vpOrdered.push_back(K[ord_kf[(size_t)j * S + i]]); vOrderedWeights.push_back(ord_w[(size_t)j * S + i]); }
+    for (int i = 0; i < n; i++) vpOrdered[i]->AddConnection(this, vOrderedWeights[i]);      // the key frame's ordered list is exactly the targets (:394-405)
+    {
+        std::unique_lock<std::mutex> lockCon(mMutexConnections);
+        mConnectedKeyFrameWeights = KFcounter;
+        mvpOrderedConnectedKeyFrames = vpOrdered;
+        mvOrderedWeights = vOrderedWeights;
+        if (mbFirstConnection && mnId != 0 && new_parent >= 0) {
+            mpParent = K[new_parent];
+            mpParent->AddChild(this);
+            mbFirstConnection = false;
+        }
+    }
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_CONNECTIONS
 
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.

@@ -130,6 +130,14 @@ class LocalMapView(C.Structure):
 LOCALMAP_MAX_KEYFRAMES = 1024   # PLANAR_LOCALMAP_MAX_KEYFRAMES
 _UPDATE_LOCAL_MAP = [C.c_void_p, C.POINTER(LocalMapView), C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + \
                     [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
+
+
+class CovisGraph(C.Structure):
+    """planar_covis_graph"""
+    _fields_ = [(n, C.c_void_p) for n in ("conn_w", "ord_n", "ord_kf", "ord_w", "first_connection", "kf_mnid", "parent", "covis")]
+
+
+_UPDATE_CONNECTIONS = [C.c_void_p, C.POINTER(LocalMapView), C.POINTER(CovisGraph), C.c_int] + [C.c_void_p] * 4
 KFDB_MAX_WORDS = 4096        # PLANAR_KFDB_MAX_WORDS
 KFDB_MAX_KEYFRAMES = 1024    # PLANAR_KFDB_MAX_KEYFRAMES
 
@@ -277,6 +285,12 @@ _SIGS = {
     "planar_local_map_ws_get_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "planar_update_local_map": (C.c_int, _UPDATE_LOCAL_MAP),
     "planar_update_local_map_dev": (C.c_int, _UPDATE_LOCAL_MAP),
+    "planar_connections_ws_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "planar_connections_ws_destroy": (None, [C.c_void_p]),
+    "planar_connections_ws_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
+    "planar_connections_ws_get_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "planar_update_connections": (C.c_int, _UPDATE_CONNECTIONS),
+    "planar_update_connections_dev": (C.c_int, _UPDATE_CONNECTIONS),
     "planar_search_by_bow_kf": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_bow_kf_dev": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_projection_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
