@@ -1235,6 +1235,157 @@ int planar_update_connections(planar_connections_ws* ws, const planar_local_map*
 int planar_update_connections_dev(planar_connections_ws* ws, const planar_local_map* map, const planar_covis_graph* graph, int L, const int32_t* d_entry_map,
                                   const int32_t* d_entry_kf, int32_t* d_new_parent, int32_t* d_status);
 
+/* ---- key-frame insertion into the maps of a planar_local_map (replaces the end of Tracking::Track, src/Tracking.cc:1973-2003 and :321-336, NeedNewKeyFrame
+ *      :2049-2137, CreateNewKeyFrame :2139-2285 without its plane loop, and the head of LocalMapping::ProcessNewKeyFrame, src/LocalMapping.cc:123-157) ----
+ * The arrays of the G maps that these calls write, in the layout of planar_local_map and, like parent / covis of planar_covis_graph, possibly the very arrays a
+ * planar_local_map points at.  Three arrays are new: the observation counters and the observation lists of the lines. */
+typedef struct planar_map_edit {
+    int32_t n_maps;              /* G */
+    int32_t kf_stride, slot_stride, line_slot_stride, pt_stride, ml_stride, obs_cap, ml_obs_cap;
+    int32_t* n_kf;               /* [G]                                                                                                            */
+    uint8_t* kf_bad;             /* [G][kf_stride]                                                                                                 */
+    int32_t* kf_rank;            /* [G][kf_stride]                   a permutation of [0, n_kf)                                                    */
+    int32_t* parent;             /* [G][kf_stride]                                                                                                 */
+    int32_t* covis;              /* [G][kf_stride][10]                                                                                             */
+    int32_t* child_off;          /* [G][kf_stride + 1]                                                                                             */
+    int32_t* n_slots;            /* [G][kf_stride]                                                                                                 */
+    int32_t* kf_pts;             /* [G][kf_stride][slot_stride]                                                                                    */
+    int32_t* n_line_slots;       /* [G][kf_stride]                                                                                                 */
+    int32_t* kf_lines;           /* [G][kf_stride][line_slot_stride]                                                                               */
+    int32_t* n_pts;              /* [G]                                                                                                            */
+    uint8_t* pt_bad;             /* [G][pt_stride]                                                                                                 */
+    int32_t* obs_off;            /* [G][pt_stride + 1]               obs_off[0] = 0, ascending; obs_off[n_pts] entries of obs_kf are in use        */
+    int32_t* obs_kf;             /* [G][obs_cap]                     each list in ascending kf_rank (std::map<KeyFrame*, size_t>)                  */
+    int32_t* pt_nobs;            /* [G][pt_stride]                   MapPoint::nObs = Observations(): +2 per observation with mvuRight >= 0, else +1 */
+    float* pt_xw;                /* [G][pt_stride][3]                                                                                              */
+    float* pt_normal;            /* [G][pt_stride][3]                                                                                              */
+    float* pt_min_dist;          /* [G][pt_stride]                                                                                                 */
+    float* pt_max_dist;          /* [G][pt_stride]                                                                                                 */
+    uint8_t* pt_desc;            /* [G][pt_stride][32]               4-byte aligned                                                                */
+    int32_t* n_ml;               /* [G]                                                                                                            */
+    uint8_t* ml_bad;             /* [G][ml_stride]                                                                                                 */
+    uint8_t* ml_observed;        /* [G][ml_stride]                   Observations() > 0                                                            */
+    int32_t* ml_obs_off;         /* [G][ml_stride + 1]               the observation lists of the lines, as obs_off / obs_kf                       */
+    int32_t* ml_obs_kf;          /* [G][ml_obs_cap]                                                                                                */
+    int32_t* ml_nobs;            /* [G][ml_stride]                   MapLine::nObs: +1 per observation                                             */
+    double* ml_xw6;              /* [G][ml_stride][6]                8-byte aligned                                                                */
+    double* ml_normal;           /* [G][ml_stride][3]                                                                                              */
+    float* ml_min_dist;          /* [G][ml_stride]                                                                                                 */
+    float* ml_max_dist;          /* [G][ml_stride]                                                                                                 */
+    uint8_t* ml_desc;            /* [G][ml_stride][32]               4-byte aligned                                                                */
+    const planar_covis_graph* graph; /* optional (a HOST pointer in both flavours); its arrays MUST be laid out in this view's n_maps and kf_stride, as
+                                  * planar_update_connections asks of its graph: the struct carries no sizes of its own, so nothing can check it, and a graph
+                                  * packed with another stride is written out of bounds.  planar_create_new_key_frame initialises the row of the key frame k it
+                                  * appends: conn_w[k][x] = conn_w[x][k] = 0 for x <= k, ord_n[k] = 0, first_connection[k] = 1, kf_mnid[k] = mnid, parent[k] =
+                                  * -1, covis[k][*] = -1 */
+} planar_map_edit;
+/* The tracked frames of a call, B of them, padded like every other view.  planar_need_new_key_frame reads map_of, the counts, the matches, the outlier flags and
+ * the depths (the others may be null); planar_create_new_key_frame reads all but the outlier flags. */
+typedef struct planar_kf_frames {
+    int32_t B, frame_stride, frame_line_stride;
+    const int32_t* map_of;       /* [B]                          the frame's map                                                                     */
+    const int32_t* n_frame;      /* [B]                          mCurrentFrame.N                                                                     */
+    int32_t* frame_match;        /* [B][frame_stride]            in/out: mvpMapPoints as map-point ids, -1 = NULL                                    */
+    uint8_t* outlier;            /* [B][frame_stride]            in/out: mvbOutlier                                                                  */
+    const float* depth;          /* [B][frame_stride]            mvDepth                                                                             */
+    const float* u_right;        /* [B][frame_stride]            mvuRight (planar_stereo_from_rgbd_dev)                                              */
+    const float* xw;             /* [B][frame_stride][3]         UnprojectStereo(i) (planar_stereo_from_rgbd_dev)                                    */
+    const float* normal;         /* [B][frame_stride][3]         planar_update_normal_and_depth_dev on the frame's single observation                */
+    const float* min_dist;       /* [B][frame_stride]                                                                                                */
+    const float* max_dist;       /* [B][frame_stride]                                                                                                */
+    const uint8_t* desc;         /* [B][frame_stride][32]        mDescriptors, 4-byte aligned                                                        */
+    const int32_t* n_frame_lines; /* [B]                         NL                                                                                  */
+    int32_t* frame_line_match;   /* [B][frame_line_stride]       in/out: mvpMapLines                                                                 */
+    uint8_t* line_outlier;       /* [B][frame_line_stride]       in/out: mvbLineOutlier                                                              */
+    const float* depth_line;     /* [B][frame_line_stride]       mvDepthLine                                                                         */
+    const double* xw6;           /* [B][frame_line_stride][6]    obtain3DLine(i), 8-byte aligned                                                     */
+    const double* line_normal;   /* [B][frame_line_stride][3]                                                                                        */
+    const float* line_min_dist;  /* [B][frame_line_stride]                                                                                           */
+    const float* line_max_dist;  /* [B][frame_line_stride]                                                                                           */
+    const uint8_t* line_desc;    /* [B][frame_line_stride][32]   4-byte aligned                                                                      */
+} planar_kf_frames;
+/* What NeedNewKeyFrame reads from outside the frame and the map, per frame (48 bytes) */
+typedef struct planar_need_kf_params {
+    uint64_t frame_id;                              /* mCurrentFrame.mnId (long unsigned)                                       */
+    uint32_t last_reloc_frame_id, last_kf_frame_id; /* mnLastRelocFrameId, mnLastKeyFrameId (unsigned int: their sums with the int below wrap as the reference's) */
+    int32_t max_frames, min_frames;                 /* mMaxFrames, mMinFrames                                                   */
+    float th_depth;                                 /* mThDepth                                                                 */
+    int32_t n_kfs_in_map;                           /* Map::KeyFramesInMap()                                                    */
+    int32_t n_plane_inliers;                        /* what the plane loops (:2005 ff.) add to mnMatchesInliers                 */
+    int32_t flags;                                  /* PLANAR_NEEDKF_*                                                          */
+    int32_t keyframes_in_queue;                     /* LocalMapping::KeyframesInQueue()                                         */
+    int32_t reserved;
+} planar_need_kf_params;
+#define PLANAR_NEEDKF_ONLY_TRACKING 1    /* mbOnlyTracking */
+#define PLANAR_NEEDKF_MAPPER_STOPPED 2   /* isStopped() || stopRequested() */
+#define PLANAR_NEEDKF_MAPPER_ACCEPTS 4   /* AcceptKeyFrames() */
+#define PLANAR_NEEDKF_NEW_PLANE 8        /* mCurrentFrame.mbNewPlane */
+/* the row of int32 planar_need_new_key_frame writes per frame */
+#define PLANAR_NEEDKF_NOUT 12
+enum { PLANAR_NEEDKF_NEED = 0, PLANAR_NEEDKF_INTERRUPT_BA, PLANAR_NEEDKF_MATCHES_INLIERS, PLANAR_NEEDKF_REF_MATCHES, PLANAR_NEEDKF_MAP, PLANAR_NEEDKF_TOTAL,
+       PLANAR_NEEDKF_NON_TRACKED_CLOSE, PLANAR_NEEDKF_C1A, PLANAR_NEEDKF_C1B, PLANAR_NEEDKF_C1C, PLANAR_NEEDKF_C2, PLANAR_NEEDKF_STATUS };
+#define PLANAR_KEYFRAME_MAX_KEYS 2048    /* frame_stride and frame_line_stride of planar_create_new_key_frame: a frame's sort keys stay within a sixth of a CU's LDS */
+/* The workspace: one int per map of max_maps (the frame or entry that names it), a mark per map point and per map line and a second observation buffer per map
+ * (4 * (1 + pt_stride + ml_stride + obs_cap + ml_obs_cap) bytes per map), allocated by the first call on the handle (creating it touches no device).  A call with
+ * more frames than max_batch, more maps than max_maps or larger strides / capacities than the workspace was made for is PLANAR_EINVAL. */
+typedef struct planar_keyframe_ws planar_keyframe_ws;
+int planar_keyframe_ws_create(planar_ctx* ctx, int max_batch, int max_maps, int pt_stride, int ml_stride, int obs_cap, int ml_obs_cap, planar_keyframe_ws** out);
+void planar_keyframe_ws_destroy(planar_keyframe_ws* ws);
+/* HIP-event timing, as planar_connections_ws_set_profiling: total_ms [3] = keyframe_need; keyframe_register with keyframe_create; keyframe_register
+ * with keyframe_add (the 4-byte-per-map memset ahead of the last two is enqueued before the first event), each over the `calls` recorded calls of ITS entry point (calls [3]) */
+int planar_keyframe_ws_set_profiling(planar_keyframe_ws* ws, int enable);
+int planar_keyframe_ws_get_profile(planar_keyframe_ws* ws, double* total_ms, int64_t* calls);
+/* The end of Tracking::Track for the B frames of `fr` (RGB-D sensor); frames may share a map, the map is only read.  `map` and `fr` are HOST structs in both
+ * flavours (their arrays are device arrays in the _dev one); ref_kf [B] (mpReferenceKF), params [B] and out [B][PLANAR_NEEDKF_NOUT] follow the flavour.  In order:
+ *   count   mnMatchesInliers (:1973-2003): the matched key points and lines that are not outliers and, unless only_tracking, whose Observations() > 0, plus
+ *           n_plane_inliers; outlier entries are not nulled (that is the STEREO sensor's)
+ *   clean   "Clean VO matches" (:321-336): a match whose point or line has Observations() < 1 becomes -1 and its outlier flag 0
+ *   decide  NeedNewKeyFrame line for line on the cleaned frame: nRefMatches = TrackedMapPoints(nKFs <= 2 ? 2 : 3) over the slots of ref_kf (not NULL, not bad,
+ *           pt_nobs >= nMinObs); nMap / nTotal / nNonTrackedClose over 0 < depth < th_depth; ratioMap = (float)((double)(float)nMap / fmax(1.0, nTotal));
+ *           mnMatchesInliers < nRefMatches * 0.25 in double, < nRefMatches * thRefRatio in float; the early returns (only_tracking, a stopped mapper, too close
+ *           to a relocalisation) give need = 0 with the counters and condition bits still reported
+ *   out     need, interrupt_ba (InterruptBA() was called), the five counters, c1a, c1b, c1c, c2, status: 0 ok; 2 (_dev only) an index was out of range (map_of,
+ *           ref_kf, the counts, a match, a slot of ref_kf): need = 0, the other entries 0, the frame's arrays untouched
+ * PLANAR_EINVAL before any HIP call: a null argument or required array, B < 1 or above max_batch, strides < 1 or above the workspace's; the host-pointer
+ * flavour also walks every index on the host first. */
+int planar_need_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const int32_t* ref_kf,
+                              const planar_need_kf_params* params, int32_t* out);
+int planar_need_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const int32_t* d_ref_kf,
+                                  const planar_need_kf_params* d_params, int32_t* d_out);
+/* Tracking::CreateNewKeyFrame (RGB-D, planes left to the caller) for the frames b of `fr` with create[b] != 0, at most one per map and call.  Per frame: th_depth,
+ * new_rank (the new key frame's place in pointer order, in [0, n_kf]; every kf_rank >= it moves up by one) and mnid.
+ *   selection  the pairs (z, i) with z > 0 sorted as std::pair<float, int>; the walk's break (`z > mThDepth && nPoints > 100`, nPoints counting both branches)
+ *              processes the first min(M, max(100, c) + 1) of the M candidates, c of which have z <= th_depth; lines: the first min(ML, 51)
+ *   creation   a processed key point creates a map point iff its match is -1 or its point has pt_nobs < 1; the new point's id is n_pts plus the number of
+ *              creators before it in sorted order; its rows are copies of the frame's (the descriptor too: ComputeDistinctiveDescriptors over one observation
+ *              returns it), pt_bad = 0, one observation (the new key frame), pt_nobs = u_right[i] >= 0 ? 2 : 1; lines likewise with ml_nobs = 1, ml_observed = 1
+ *   key frame  k = n_kf appended: kf_bad = 0, parent = -1, covis = -1, child_off[k + 1] = child_off[k], n_slots = N, slots = frame_match as it came in with the
+ *              created ids over it, lines likewise, kf_rank[k] = new_rank, the optional graph row
+ *   frame      frame_match / frame_line_match get the new ids
+ *   new_kf [B] k, or -1; created_pt [B][frame_stride], n_created_pt [B], created_ml [B][frame_line_stride], n_created_ml [B]: the key-point (line) index of each
+ *              creation in creation order
+ *   status [B] 0 ok (also a frame not chosen); 2 (_dev only) an index was out of range or the map is named twice (then for every frame naming it); 3 a capacity
+ *              (kf_stride, pt_stride, ml_stride, obs_cap, ml_obs_cap, a slot stride below N / NL) would be exceeded.  With 2 or 3 the frame changes nothing.
+ * PLANAR_EINVAL as above, and frame_stride or frame_line_stride above PLANAR_KEYFRAME_MAX_KEYS; the host-pointer flavour answers it for a map named twice. */
+int planar_create_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const uint8_t* create, const float* th_depth,
+                                const int32_t* new_rank, const int32_t* mnid, int32_t* new_kf, int32_t* created_pt, int32_t* n_created_pt, int32_t* created_ml,
+                                int32_t* n_created_ml, int32_t* status);
+int planar_create_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const uint8_t* d_create, const float* d_th_depth,
+                                    const int32_t* d_new_rank, const int32_t* d_mnid, int32_t* d_new_kf, int32_t* d_created_pt, int32_t* d_n_created_pt,
+                                    int32_t* d_created_ml, int32_t* d_n_created_ml, int32_t* d_status);
+/* The head of LocalMapping::ProcessNewKeyFrame for L entries (entry_map[l], entry_kf[l]), at most one per map and call.  Every slot of the key frame whose point is
+ * neither NULL nor bad and does not list the key frame gives the point one observation: the key frame is inserted into the point's list at its place in ascending
+ * kf_rank and pt_nobs grows by 2 if u_right[l][slot] >= 0, else by 1; a point in two slots gains one observation and its first slot decides.  Lines likewise with
+ * increment 1 and ml_observed = 1.
+ *   u_right [L][slot_stride]  mvuRight of the key frame
+ *   added_pt [L][slot_stride], added_ml [L][line_slot_stride]  bytes, written for the slots in use: 1 = the slot gave its point the observation
+ *   status [L]  0 ok; 2 (_dev only) an index out of range or the map named twice; 3 obs_cap or ml_obs_cap would be exceeded.  With 2 or 3 nothing changes.
+ * PLANAR_EINVAL as above. */
+int planar_add_observations(planar_keyframe_ws* ws, const planar_map_edit* map, int L, const int32_t* entry_map, const int32_t* entry_kf, const float* u_right,
+                            uint8_t* added_pt, uint8_t* added_ml, int32_t* status);
+int planar_add_observations_dev(planar_keyframe_ws* ws, const planar_map_edit* map, int L, const int32_t* d_entry_map, const int32_t* d_entry_kf,
+                                const float* d_u_right, uint8_t* d_added_pt, uint8_t* d_added_ml, int32_t* d_status);
+
 /* ---- 3-D line back-projection (replaces Frame::isLineGood, src/Frame.cc:189-267, with compPt3dCov / extract3dline_mahdist / verify3dLine /
  *      mah_dist3d_pt_line / computeLine3d_svd of src/LineExtractor.cpp:1157-1470) ----
  * keylines [B][ln_stride] = Frame::mvKeylinesUn, depth = the u16 depth image (imDepth = value * depth_factor), fx.. = Frame::fx.. (K(0,0) of compPt3dCov is fx).

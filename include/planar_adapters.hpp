@@ -10,6 +10,7 @@
 //   Planar_SLAM::KeyFrameDatabase <- include/KeyFrameDatabase.h:42-70, src/KeyFrameDatabase.cc         (PLANAR_ADAPTERS_WITH_KFDB)
 //   Tracking::UpdateLocalMap                                                                          (PLANAR_ADAPTERS_WITH_LOCAL_MAP)
 //   KeyFrame::UpdateConnections                                                                       (PLANAR_ADAPTERS_WITH_CONNECTIONS)
+//   Tracking::NeedNewKeyFrame / Tracking::CreateNewKeyFrame                                           (PLANAR_ADAPTERS_WITH_KEYFRAME)
 //   ORBmatcher::SearchByBoW(KF, KF) / SearchBySim3 / SearchByProjection(KF, Scw) / Fuse(KF, Scw)      (PLANAR_ADAPTERS_WITH_LOOP_MATCHERS)
 //   Optimizer::OptimizeSim3                                                                           (PLANAR_ADAPTERS_WITH_SIM3_OPT)
 //   Planar_SLAM::Sim3Solver <- include/Sim3Solver.h, src/Sim3Solver.cc                                  (PLANAR_ADAPTERS_WITH_SIM3_SOLVER)
@@ -1485,6 +1486,209 @@ inline void KeyFrame::UpdateConnections() {
 }
 }  // namespace Planar_SLAM
 #endif   // PLANAR_ADAPTERS_WITH_CONNECTIONS
+
+// ---- Tracking::NeedNewKeyFrame (src/Tracking.cc:2049-2137) and Tracking::CreateNewKeyFrame (:2139-2285).  Enabled with PLANAR_ADAPTERS_WITH_KEYFRAME, after the
+//      reference's Tracking.h, Frame.h, KeyFrame.h, MapPoint.h, MapLine.h, MapPlane.h, Map.h and LocalMapping.h; leave those two bodies of src/Tracking.cc out.
+//      Both pack the current frame into a ONE-FRAME problem on a one-map planar_map_edit and call the host form with B = 1 on the tracking lane: the correctness
+//      path; the throughput path is the _dev calls on a resident map.  Map points and lines are numbered as the frame (and, for the
+//      decision, the reference key frame) meets them; their Observations() are pt_nobs / ml_nobs.
+//      NeedNewKeyFrame: the only key frame of the packed map is mpReferenceKF; the call counts and cleans again what Track() counted and cleaned before it
+//      (:1973-2003, :321-336), which changes nothing on a frame that went through those, and the member mnMatchesInliers is handed through: n_plane_inliers is
+//      what the member holds beyond the point and line inliers the call counts.  InterruptBA() is called where the reference calls it.
+//      CreateNewKeyFrame: the packed map has no key frame yet (new_rank 0) and no rows worth copying; the call gives the key points and lines that create, in
+//      creation order, and new MapPoint / AddObservation / AddMapPoint / ... run on the objects in that order, as the reference's walk does.  The plane loop
+//      works on MapPlane objects and stays on the host.  A failing call creates no point and no line (the key frame is still inserted) and reports on stderr.
+#ifdef PLANAR_ADAPTERS_WITH_KEYFRAME
+#include <iostream>
+#include <map>
+namespace planar_adapter {
+// the frame's matches as ids, with the Observations() of every object met; ids are handed out in the order of meeting
+template <class T> struct ObjectIds {
+    std::map<T*, int32_t> id;
+    std::vector<T*> object;
+    std::vector<int32_t> nobs;
+    std::vector<uint8_t> bad;
+    int32_t of(T* p) {
+        if (!p) return -1;
+        auto it = id.find(p);
+        if (it != id.end()) return it->second;
+        id[p] = (int32_t)object.size();
+        object.push_back(p); nobs.push_back(p->Observations()); bad.push_back(p->isBad());
+        return (int32_t)object.size() - 1;
+    }
+};
+template <class V> inline V* data_or_one(std::vector<V>& v) { if (v.empty()) v.resize(1); return v.data(); }
+}  // namespace planar_adapter
+
+namespace Planar_SLAM {
+inline bool Tracking::NeedNewKeyFrame() {
+    Frame& F = mCurrentFrame;
+    const int N = F.N, NL = F.NL;
+    planar_adapter::ObjectIds<MapPoint> pts;
+    planar_adapter::ObjectIds<MapLine> mls;
+    std::vector<int32_t> match(N > 0 ? N : 1, -1), lmatch(NL > 0 ? NL : 1, -1);
+    std::vector<uint8_t> outl(match.size(), 0), loutl(lmatch.size(), 0);
+    std::vector<float> depth(match.size(), -1.f);
+    int counted = 0;                                     // what the call will count itself of mnMatchesInliers
+    for (int i = 0; i < N; i++) {
+        match[i] = pts.of(F.mvpMapPoints[i]); outl[i] = F.mvbOutlier[i]; depth[i] = F.mvDepth[i];
+        if (match[i] >= 0 && !outl[i] && (mbOnlyTracking || pts.nobs[match[i]] > 0)) counted++;
+    }
+    for (int i = 0; i < NL; i++) {
+        lmatch[i] = mls.of(F.mvpMapLines[i]); loutl[i] = F.mvbLineOutlier[i];
+        if (lmatch[i] >= 0 && !loutl[i] && (mbOnlyTracking || mls.nobs[lmatch[i]] > 0)) counted++;
+    }
+    const std::vector<MapPoint*> ref = mpReferenceKF->GetMapPointMatches();
+    std::vector<int32_t> slots(ref.size() ? ref.size() : 1, -1);
+    for (size_t i = 0; i < ref.size(); i++) slots[i] = pts.of(ref[i]);
+    planar_map_edit m{};
+    m.n_maps = 1; m.kf_stride = 1; m.slot_stride = (int32_t)slots.size(); m.line_slot_stride = 1; m.pt_stride = (int32_t)(pts.object.size() ? pts.object.size() : 1);
+    m.ml_stride = (int32_t)(mls.object.size() ? mls.object.size() : 1); m.obs_cap = 1; m.ml_obs_cap = 1;
+    int32_t n_kf = 1, n_slots = (int32_t)ref.size(), n_pts = (int32_t)pts.object.size(), n_ml = (int32_t)mls.object.size();
+    m.n_kf = &n_kf; m.n_slots = &n_slots; m.kf_pts = slots.data(); m.n_pts = &n_pts; m.pt_bad = planar_adapter::data_or_one(pts.bad);
+    m.pt_nobs = planar_adapter::data_or_one(pts.nobs); m.n_ml = &n_ml; m.ml_nobs = planar_adapter::data_or_one(mls.nobs);
+    planar_kf_frames fr{};
+    const int32_t map_of = 0, ref_kf = 0;
+    fr.B = 1; fr.frame_stride = (int32_t)match.size(); fr.frame_line_stride = (int32_t)lmatch.size();
+    fr.map_of = &map_of; fr.n_frame = &N; fr.frame_match = match.data(); fr.outlier = outl.data(); fr.depth = depth.data();
+    fr.n_frame_lines = &NL; fr.frame_line_match = lmatch.data(); fr.line_outlier = loutl.data();
+    planar_need_kf_params prm{};
+    prm.frame_id = F.mnId; prm.last_reloc_frame_id = mnLastRelocFrameId; prm.last_kf_frame_id = mnLastKeyFrameId; prm.max_frames = mMaxFrames; prm.min_frames = mMinFrames;
+    prm.th_depth = mThDepth; prm.n_kfs_in_map = (int32_t)mpMap->KeyFramesInMap(); prm.n_plane_inliers = mnMatchesInliers - counted;
+    prm.flags = (mbOnlyTracking ? PLANAR_NEEDKF_ONLY_TRACKING : 0) | ((mpLocalMapper->isStopped() || mpLocalMapper->stopRequested()) ? PLANAR_NEEDKF_MAPPER_STOPPED : 0) |
+                (mpLocalMapper->AcceptKeyFrames() ? PLANAR_NEEDKF_MAPPER_ACCEPTS : 0) | (F.mbNewPlane ? PLANAR_NEEDKF_NEW_PLANE : 0);
+    prm.keyframes_in_queue = mpLocalMapper->KeyframesInQueue();
+    int32_t out[PLANAR_NEEDKF_NOUT] = {0};
+    const bool done = planar_adapter::on_lane(planar_adapter::TRACKING, "planar_need_new_key_frame", [&](planar_ctx* ctx) -> int {
+        planar_keyframe_ws* ws = nullptr;
+        int rc = planar_keyframe_ws_create(ctx, 1, 1, m.pt_stride, m.ml_stride, 1, 1, &ws);
+        if (rc != PLANAR_OK) return rc;
+        rc = planar_need_new_key_frame(ws, &m, &fr, &ref_kf, &prm, out);
+        planar_keyframe_ws_destroy(ws);
+        return rc;
+    });
+    if (!done || out[PLANAR_NEEDKF_STATUS] != 0) return false;
+    for (int i = 0; i < N; i++) {                        // the clean step's result; nothing changes on a frame Track() cleaned already
+        if (match[i] < 0) F.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);
+        F.mvbOutlier[i] = outl[i] != 0;
+    }
+    for (int i = 0; i < NL; i++) {
+        if (lmatch[i] < 0) F.mvpMapLines[i] = static_cast<MapLine*>(NULL);
+        F.mvbLineOutlier[i] = loutl[i] != 0;
+    }
+    if (out[PLANAR_NEEDKF_INTERRUPT_BA]) mpLocalMapper->InterruptBA();
+    return out[PLANAR_NEEDKF_NEED] != 0;
+}
+
+inline void Tracking::CreateNewKeyFrame() {
+    if (!mpLocalMapper->SetNotStop(true)) return;
+    KeyFrame* pKF = new KeyFrame(mCurrentFrame, mpMap, mpKeyFrameDB);
+    mpReferenceKF = pKF;
+    mCurrentFrame.mpReferenceKF = pKF;
+    if (mSensor != System::MONOCULAR) {
+        Frame& F = mCurrentFrame;
+        F.UpdatePoseMatrices();
+        const int N = F.N, NL = F.NL;
+        planar_adapter::ObjectIds<MapPoint> pts;
+        planar_adapter::ObjectIds<MapLine> mls;
+        const size_t FS = N > 0 ? N : 1, FLS = NL > 0 ? NL : 1;
+        std::vector<int32_t> match(FS, -1), lmatch(FLS, -1);
+        std::vector<float> depth(FS, -1.f), u_right(FS, -1.f), depth_line(FLS, -1.f);
+        for (int i = 0; i < N; i++) { match[i] = pts.of(F.mvpMapPoints[i]); depth[i] = F.mvDepth[i]; u_right[i] = F.mvuRight[i]; }
+        for (int i = 0; i < NL; i++) { lmatch[i] = mls.of(F.mvpMapLines[i]); depth_line[i] = F.mvDepthLine[i]; }
+        // a one-map problem without a key frame: room for one, and for every key point and line to create
+        const int32_t np0 = (int32_t)pts.object.size(), nl0 = (int32_t)mls.object.size();
+        const size_t PS = np0 + FS, LS = nl0 + FLS;
+        int32_t n_kf = 0, n_pts = np0, n_ml = nl0, kf_rank = 0, parent = -1, n_slots = 0, n_line_slots = 0, child_off[2] = {0, 0}, covis[10];
+        uint8_t kf_bad = 0;
+        std::vector<int32_t> kf_pts(FS, -1), kf_lines(FLS, -1), obs_off(PS + 1, 0), obs_kf(FS, 0), pt_nobs(PS, 0), ml_obs_off(LS + 1, 0), ml_obs_kf(FLS, 0), ml_nobs(LS, 0);
+        std::vector<uint8_t> pt_bad(PS, 0), ml_bad(LS, 0), ml_observed(LS, 0), pt_desc(PS * 32, 0), ml_desc(LS * 32, 0), desc(FS * 32, 0), line_desc(FLS * 32, 0);
+        std::vector<float> pt_xw(PS * 3, 0.f), pt_normal(PS * 3, 0.f), pt_min(PS, 0.f), pt_max(PS, 0.f), ml_min(LS, 0.f), ml_max(LS, 0.f), xw(FS * 3, 0.f), normal(FS * 3, 0.f),
+            fmin_(FS, 0.f), fmax_(FS, 0.f), lmin(FLS, 0.f), lmax(FLS, 0.f);
+        std::vector<double> ml_xw6(LS * 6, 0.0), ml_normal(LS * 3, 0.0), xw6(FLS * 6, 0.0), line_normal(FLS * 3, 0.0);
+        for (int32_t p = 0; p < np0; p++) { pt_nobs[p] = pts.nobs[p]; pt_bad[p] = pts.bad[p]; }
+        for (int32_t p = 0; p < nl0; p++) { ml_nobs[p] = mls.nobs[p]; ml_bad[p] = mls.bad[p]; ml_observed[p] = mls.nobs[p] > 0; }
+        planar_map_edit m{};
+        m.n_maps = 1; m.kf_stride = 1; m.slot_stride = (int32_t)FS; m.line_slot_stride = (int32_t)FLS; m.pt_stride = (int32_t)PS; m.ml_stride = (int32_t)LS;
+        m.obs_cap = (int32_t)FS; m.ml_obs_cap = (int32_t)FLS;
+        m.n_kf = &n_kf; m.kf_bad = &kf_bad; m.kf_rank = &kf_rank; m.parent = &parent; m.covis = covis; m.child_off = child_off; m.n_slots = &n_slots; m.kf_pts = kf_pts.data();
+        m.n_line_slots = &n_line_slots; m.kf_lines = kf_lines.data(); m.n_pts = &n_pts; m.pt_bad = pt_bad.data(); m.obs_off = obs_off.data(); m.obs_kf = obs_kf.data();
+        m.pt_nobs = pt_nobs.data(); m.pt_xw = pt_xw.data(); m.pt_normal = pt_normal.data(); m.pt_min_dist = pt_min.data(); m.pt_max_dist = pt_max.data();
+        m.pt_desc = pt_desc.data(); m.n_ml = &n_ml; m.ml_bad = ml_bad.data(); m.ml_observed = ml_observed.data(); m.ml_obs_off = ml_obs_off.data();
+        m.ml_obs_kf = ml_obs_kf.data(); m.ml_nobs = ml_nobs.data(); m.ml_xw6 = ml_xw6.data(); m.ml_normal = ml_normal.data(); m.ml_min_dist = ml_min.data();
+        m.ml_max_dist = ml_max.data(); m.ml_desc = ml_desc.data();
+        planar_kf_frames fr{};
+        const int32_t map_of = 0, new_rank = 0, mnid = 0;
+        const uint8_t create = 1;
+        const float th = mThDepth;
+        fr.B = 1; fr.frame_stride = (int32_t)FS; fr.frame_line_stride = (int32_t)FLS;
+        fr.map_of = &map_of; fr.n_frame = &N; fr.frame_match = match.data(); fr.depth = depth.data(); fr.u_right = u_right.data(); fr.xw = xw.data();
+        fr.normal = normal.data(); fr.min_dist = fmin_.data(); fr.max_dist = fmax_.data(); fr.desc = desc.data(); fr.n_frame_lines = &NL;
+        fr.frame_line_match = lmatch.data(); fr.depth_line = depth_line.data(); fr.xw6 = xw6.data(); fr.line_normal = line_normal.data(); fr.line_min_dist = lmin.data();
+        fr.line_max_dist = lmax.data(); fr.line_desc = line_desc.data();
+        std::vector<int32_t> created_pt(FS, -1), created_ml(FLS, -1);
+        int32_t new_kf = -1, n_created_pt = 0, n_created_ml = 0, status = -1;
+        const bool done = planar_adapter::on_lane(planar_adapter::TRACKING, "planar_create_new_key_frame", [&](planar_ctx* ctx) -> int {
+            planar_keyframe_ws* ws = nullptr;
+            int rc = planar_keyframe_ws_create(ctx, 1, 1, m.pt_stride, m.ml_stride, m.obs_cap, m.ml_obs_cap, &ws);
+            if (rc != PLANAR_OK) return rc;
+            rc = planar_create_new_key_frame(ws, &m, &fr, &create, &th, &new_rank, &mnid, &new_kf, created_pt.data(), &n_created_pt, created_ml.data(), &n_created_ml, &status);
+            planar_keyframe_ws_destroy(ws);
+            return rc;
+        });
+        if (done && status != 0) std::fprintf(stderr, "planar (CreateNewKeyFrame): frame status %d - no map point and no map line is created\n", (int)status);
+        if (done && status == 0) {
+            for (int c = 0; c < n_created_pt; c++) {     // in creation order: the order of the reference's sorted walk
+                const int i = created_pt[c];
+                cv::Mat x3D = F.UnprojectStereo(i);
+                MapPoint* pNewMP = new MapPoint(x3D, pKF, mpMap);
+                pNewMP->AddObservation(pKF, i);
+                pKF->AddMapPoint(pNewMP, i);
+                pNewMP->ComputeDistinctiveDescriptors();
+                pNewMP->UpdateNormalAndDepth();
+                mpMap->AddMapPoint(pNewMP);
+                F.mvpMapPoints[i] = pNewMP;
+            }
+            for (int c = 0; c < n_created_ml; c++) {
+                const int i = created_ml[c];
+                Vector6d line3D = F.obtain3DLine(i);
+                MapLine* pNewML = new MapLine(line3D, pKF, mpMap);
+                pNewML->AddObservation(pKF, i);
+                pKF->AddMapLine(pNewML, i);
+                pNewML->ComputeDistinctiveDescriptors();
+                pNewML->UpdateAverageDir();
+                mpMap->AddMapLine(pNewML);
+                F.mvpMapLines[i] = pNewML;
+            }
+        }
+        // the planes: observations of the matched ones, a new MapPlane for an unmatched inlier, an unmatched outlier forgiven (:2248-2272)
+        for (int i = 0; i < F.mnPlaneNum; ++i) {
+            const bool inlier = !F.mvbPlaneOutlier[i];
+            if (inlier && F.mvpParallelPlanes[i]) F.mvpParallelPlanes[i]->AddParObservation(pKF, i);
+            if (inlier && F.mvpVerticalPlanes[i]) F.mvpVerticalPlanes[i]->AddVerObservation(pKF, i);
+            if (F.mvpMapPlanes[i]) {
+                F.mvpMapPlanes[i]->AddObservation(pKF, i);
+            } else if (!inlier) {
+                F.mvbPlaneOutlier[i] = false;
+            } else {
+                cv::Mat p3D = F.ComputePlaneWorldCoeff(i);
+                MapPlane* pNewPlane = new MapPlane(p3D, pKF, mpMap);
+                pNewPlane->AddObservation(pKF, i);
+                pKF->AddMapPlane(pNewPlane, i);
+                pNewPlane->UpdateCoefficientsAndPoints();
+                mpMap->AddMapPlane(pNewPlane);
+            }
+        }
+        mpPointCloudMapping->print();
+        std::cout << "New map created with " << mpMap->MapPlanesInMap() << " planes" << std::endl;
+    }
+    mpLocalMapper->InsertKeyFrame(pKF);
+    mpLocalMapper->SetNotStop(false);
+    mnLastKeyFrameId = mCurrentFrame.mnId;
+    mpLastKeyFrame = pKF;
+}
+}  // namespace Planar_SLAM
+#endif   // PLANAR_ADAPTERS_WITH_KEYFRAME
 
 // ---- Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*)  (src/Optimizer.cc:1853-2680): the graph the reference assembles from the covisibility
 //      list and the observation maps becomes a planar_ba_problem, planar_local_ba solves it, the erase lists and the optimised values go back.

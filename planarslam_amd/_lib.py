@@ -138,6 +138,29 @@ class CovisGraph(C.Structure):
 
 
 _UPDATE_CONNECTIONS = [C.c_void_p, C.POINTER(LocalMapView), C.POINTER(CovisGraph), C.c_int] + [C.c_void_p] * 4
+
+
+class MapEditView(C.Structure):
+    """planar_map_edit"""
+    _fields_ = [(n, C.c_int32) for n in ("n_maps", "kf_stride", "slot_stride", "line_slot_stride", "pt_stride", "ml_stride", "obs_cap", "ml_obs_cap")] + \
+               [(n, C.c_void_p) for n in ("n_kf", "kf_bad", "kf_rank", "parent", "covis", "child_off", "n_slots", "kf_pts", "n_line_slots", "kf_lines", "n_pts", "pt_bad",
+                                          "obs_off", "obs_kf", "pt_nobs", "pt_xw", "pt_normal", "pt_min_dist", "pt_max_dist", "pt_desc", "n_ml", "ml_bad", "ml_observed",
+                                          "ml_obs_off", "ml_obs_kf", "ml_nobs", "ml_xw6", "ml_normal", "ml_min_dist", "ml_max_dist", "ml_desc")] + \
+               [("graph", C.POINTER(CovisGraph))]
+
+
+class KfFrames(C.Structure):
+    """planar_kf_frames"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "frame_stride", "frame_line_stride")] + \
+               [(n, C.c_void_p) for n in ("map_of", "n_frame", "frame_match", "outlier", "depth", "u_right", "xw", "normal", "min_dist", "max_dist", "desc", "n_frame_lines",
+                                          "frame_line_match", "line_outlier", "depth_line", "xw6", "line_normal", "line_min_dist", "line_max_dist", "line_desc")]
+
+
+KEYFRAME_MAX_KEYS = 2048     # PLANAR_KEYFRAME_MAX_KEYS
+NEEDKF_NOUT = 12             # PLANAR_NEEDKF_NOUT
+_NEED_NEW_KEY_FRAME = [C.c_void_p, C.POINTER(MapEditView), C.POINTER(KfFrames)] + [C.c_void_p] * 3
+_CREATE_NEW_KEY_FRAME = [C.c_void_p, C.POINTER(MapEditView), C.POINTER(KfFrames)] + [C.c_void_p] * 10
+_ADD_OBSERVATIONS = [C.c_void_p, C.POINTER(MapEditView), C.c_int] + [C.c_void_p] * 6
 KFDB_MAX_WORDS = 4096        # PLANAR_KFDB_MAX_WORDS
 KFDB_MAX_KEYFRAMES = 1024    # PLANAR_KFDB_MAX_KEYFRAMES
 
@@ -291,6 +314,16 @@ _SIGS = {
     "planar_connections_ws_get_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "planar_update_connections": (C.c_int, _UPDATE_CONNECTIONS),
     "planar_update_connections_dev": (C.c_int, _UPDATE_CONNECTIONS),
+    "planar_keyframe_ws_create": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
+    "planar_keyframe_ws_destroy": (None, [C.c_void_p]),
+    "planar_keyframe_ws_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
+    "planar_keyframe_ws_get_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "planar_need_new_key_frame": (C.c_int, _NEED_NEW_KEY_FRAME),
+    "planar_need_new_key_frame_dev": (C.c_int, _NEED_NEW_KEY_FRAME),
+    "planar_create_new_key_frame": (C.c_int, _CREATE_NEW_KEY_FRAME),
+    "planar_create_new_key_frame_dev": (C.c_int, _CREATE_NEW_KEY_FRAME),
+    "planar_add_observations": (C.c_int, _ADD_OBSERVATIONS),
+    "planar_add_observations_dev": (C.c_int, _ADD_OBSERVATIONS),
     "planar_search_by_bow_kf": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_bow_kf_dev": (C.c_int, [C.c_void_p, C.c_int] + ([C.c_void_p, C.c_int] + [C.c_void_p] * 4) * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "planar_search_by_projection_sim3": (C.c_int, [C.c_void_p, C.POINTER(FrameView), C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
