@@ -10,22 +10,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import Context, CovisGraph, LocalMapView, check, lib
+from ._mapview import NCOVIS, _addr, _place, _Workspace
 
-NCOVIS = 10
 _MAP_FIELDS = (("n_kf", np.int32), ("kf_rank", np.int32), ("n_slots", np.int32), ("kf_pts", np.int32), ("n_pts", np.int32), ("pt_bad", np.uint8), ("obs_off", np.int32),
                ("obs_kf", np.int32))
 _GRAPH_FIELDS = (("conn_w", np.int32), ("ord_n", np.int32), ("ord_kf", np.int32), ("ord_w", np.int32), ("first_connection", np.uint8), ("kf_mnid", np.int32),
                  ("parent", np.int32), ("covis", np.int32))
-
-
-def _place(a, dt, device):
-    """-> (the array kept alive, its address): a C-contiguous numpy array, or a torch tensor on `device`"""
-    a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dt)
-    if device is None:
-        return a, a.ctypes.data
-    import torch
-    t = torch.from_numpy(a).to(device)
-    return t, t.data_ptr()
 
 
 class ConnMap:
@@ -39,8 +29,8 @@ class ConnMap:
         v.line_slot_stride = v.ml_stride = v.child_cap = 1
         self.arrays = {}
         for name, dt in _MAP_FIELDS:
-            self.arrays[name], p = _place(d[name], dt, device)
-            setattr(v, name, p)
+            self.arrays[name] = _place(d[name], dt, device)
+            setattr(v, name, _addr(self.arrays[name]))
         self.view, self.device = v, device
 
 
@@ -55,11 +45,10 @@ class Graph:
             if localmap is not None and name in ("parent", "covis"):
                 if localmap.device != device:
                     raise ValueError("the local map and the graph must live in the same place")
-                a = localmap.arrays[name]
-                self.arrays[name], p = a, (a.ctypes.data if device is None else a.data_ptr())
+                self.arrays[name] = localmap.arrays[name]
             else:
-                self.arrays[name], p = _place(d[name], dt, device)
-            setattr(v, name, p)
+                self.arrays[name] = _place(d[name], dt, device)
+            setattr(v, name, _addr(self.arrays[name]))
         self.view, self.device = v, device
 
     def numpy(self):
@@ -67,25 +56,12 @@ class Graph:
         return {k: (a.cpu().numpy() if hasattr(a, "cpu") else a.copy()) for k, a in self.arrays.items()}
 
 
-class Workspace:
+class Workspace(_Workspace):
     """planar_connections_ws: a counter row per entry and the place in the list of every key frame (4 * (max_entries * (kf_stride + 4) + max_maps * kf_stride) bytes)"""
+    _NAME = "planar_connections_ws"
 
     def __init__(self, ctx: Context, max_entries: int, max_maps: int, kf_stride: int):
-        self.ctx, self.L = ctx, lib()
-        h = C.c_void_p()
-        check(self.L.planar_connections_ws_create(ctx.h, int(max_entries), int(max_maps), int(kf_stride), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.planar_connections_ws_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, max_entries, max_maps, kf_stride)
 
 
 def update_connections(ws: Workspace, m, graph: Graph, entry_map, entry_kf):

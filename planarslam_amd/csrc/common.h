@@ -98,9 +98,11 @@ struct Stager {
     template <typename T> Dev<T> inout(T* h, size_t count) { return h ? add<T>(h, h, count) : Dev<T>{}; }
     template <typename T> Dev<T> temp(size_t count) { return add<T>(nullptr, nullptr, count); }   // an array of the block that is not copied either way
     // For the arrays of a view struct, on the caller's copy of the view: the host array `field` points to is staged, and upload() stores its device address in `field`.
-    // A null input stays null; an output without a host array (planar_pose_assemble's optional ones) still gets its device array.
+    // A null input stays null; an output without a host array (planar_pose_assemble's optional ones) still gets its device array.  inout_field: an array the call
+    // updates in place (back = false: of a view of writable arrays, for a call that only reads it).
     template <typename T> void in_field(const T*& field, size_t count) { if (field) add<const T>(field, nullptr, count, &field); }
     template <typename T> void out_field(const T*& field, size_t count) { add<T>(nullptr, const_cast<T*>(field), count, &field); }
+    template <typename T> void inout_field(T*& field, size_t count, bool back = true) { if (field) add<T>(field, back ? field : nullptr, count, &field); }
     template <typename T> Dev<T> add(const void* hin, void* hout, size_t count, void* field = nullptr) {
         const size_t bytes = count * sizeof(T);
         items.push_back({hin, hout, bytes, total, field});

@@ -11,18 +11,18 @@
 //                                come after its own; its ordered list is one bitonic sort in LDS on (weight, rank), descending; parent and covis follow
 // Integers only.  Every index read from device memory is checked against its range before it is used; an entry that meets one outside ends with status 2 and
 // changes nothing.
+#include "map_view.h"
 #include "ref_arith.h"
 #include "wave_ops.h"
 
 namespace planar {
 namespace connections {
 
-constexpr int NT = 256, NW = NT / 64, MAXK = PLANAR_LOCALMAP_MAX_KEYFRAMES, NCOVIS = 10, TH = 15, RANK_BITS = 10, MAX_SLOT_STRIDE = 1 << 20;
+constexpr int NT = 256, NW = NT / 64, TH = 15, RANK_BITS = 10;
 static_assert(MAXK == 1 << RANK_BITS, "a rank takes the low bits of a sort key");
 constexpr int NSTATE = 4;      // per entry: what became of it, whether a count reached the threshold, the first maximum in pointer order
 enum { ST_CODE = 0, ST_HAS_TH = 1, ST_MAX_KF = 2 };
 enum { E_OK = 0, E_EMPTY = 1, E_ERR = 2 };
-constexpr int NO_ENTRY = -1, TWICE = -2;
 
 struct Args {
     // of the map
@@ -39,7 +39,6 @@ struct Args {
     int32_t* pos;        // [n_maps][S]   the entry that names the key frame, NO_ENTRY, or TWICE
 };
 
-__device__ inline bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
 __device__ inline bool is_target(int c, int kf, const int32_t* st) { return c >= TH || (!st[ST_HAS_TH] && st[ST_MAX_KF] == kf && c > 0); }
 
 __global__ __launch_bounds__(NT) void connections_register_kernel(Args a) {
@@ -225,55 +224,23 @@ static size_t ws_bytes(size_t L, size_t G, size_t S) { return 4 * (L * S + L * N
 
 static int check_args(const planar_connections_ws* ws, const planar_local_map* m, const planar_covis_graph* gr, int L, bool arrays) {
     PLANAR_REQUIRE(ws && m && gr && arrays, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(m->n_kf && m->kf_rank && m->n_slots && m->kf_pts && m->n_pts && m->pt_bad && m->obs_off && m->obs_kf, PLANAR_EINVAL, "null array in the map view");
-    PLANAR_REQUIRE(gr->conn_w && gr->ord_n && gr->ord_kf && gr->ord_w && gr->first_connection && gr->kf_mnid && gr->parent && gr->covis, PLANAR_EINVAL,
-                   "null array in the graph");
+    if (int rc = check_map_arrays(*m, NEEDS_CONNECTIONS)) return rc;
+    if (int rc = check_graph_arrays(gr)) return rc;
     PLANAR_REQUIRE(L >= 1, PLANAR_EINVAL, "L >= 1 required");
     PLANAR_REQUIRE(L <= ws->max_entries, PLANAR_EINVAL, "L exceeds the workspace's max_entries");
-    PLANAR_REQUIRE(m->kf_stride >= 1 && m->kf_stride <= MAXK, PLANAR_EINVAL, "1 <= kf_stride <= PLANAR_LOCALMAP_MAX_KEYFRAMES required");
-    PLANAR_REQUIRE(m->n_maps >= 1 && m->slot_stride >= 1 && m->pt_stride >= 1 && m->obs_cap >= 1, PLANAR_EINVAL,
-                   "n_maps, slot_stride, pt_stride and obs_cap of the map view must be >= 1");
-    PLANAR_REQUIRE(m->slot_stride <= MAX_SLOT_STRIDE, PLANAR_EINVAL, "slot stride above 2^20");
+    if (int rc = check_map_sizes(*m, NEEDS_CONNECTIONS)) return rc;
     PLANAR_REQUIRE(m->kf_stride <= ws->kf_stride && m->n_maps <= ws->max_maps, PLANAR_EINVAL, "the map's kf_stride / n_maps exceed the workspace's");
     return PLANAR_OK;
 }
 
-static inline bool in_range_h(int v, int n) { return (unsigned)v < (unsigned)n; }
-
-// the host-pointer flavour's walk: every index a kernel could meet, on host arrays
-static int check_indices(const planar_local_map* m, int L, const int32_t* entry_map, const int32_t* entry_kf) {
-    const int S = m->kf_stride, PS = m->pt_stride;
-    std::vector<uint8_t> seen;
-    for (int g = 0; g < m->n_maps; g++) {
-        const int nk = m->n_kf[g], np = m->n_pts[g];
-        PLANAR_REQUIRE(nk >= 0 && nk <= S, PLANAR_EINVAL, "n_kf outside [0, kf_stride]");
-        PLANAR_REQUIRE(np >= 0 && np <= PS, PLANAR_EINVAL, "n_pts outside [0, pt_stride]");
-        const size_t gk = (size_t)g * S;
-        seen.assign((size_t)nk, 0);
-        for (int k = 0; k < nk; k++) {
-            const int r = m->kf_rank[gk + k];
-            PLANAR_REQUIRE(in_range_h(r, nk) && !seen[r], PLANAR_EINVAL, "kf_rank is not a permutation of [0, n_kf)");
-            seen[r] = 1;
-            const int ns = m->n_slots[gk + k];
-            PLANAR_REQUIRE(ns >= 0 && ns <= m->slot_stride, PLANAR_EINVAL, "slot count outside its stride");
-            for (int s = 0; s < ns; s++) {
-                const int id = m->kf_pts[(gk + k) * m->slot_stride + s];
-                PLANAR_REQUIRE(id >= -1 && id < np, PLANAR_EINVAL, "map-point slot out of range");
-            }
-        }
-        const int32_t* oo = m->obs_off + (size_t)g * (PS + 1);
-        for (int p = 0; p < np; p++) {
-            PLANAR_REQUIRE(oo[p] >= 0 && oo[p + 1] >= oo[p] && oo[p + 1] <= m->obs_cap, PLANAR_EINVAL, "obs_off out of range");
-            for (int o = oo[p]; o < oo[p + 1]; o++)
-                PLANAR_REQUIRE(in_range_h(m->obs_kf[(size_t)g * m->obs_cap + o], nk), PLANAR_EINVAL, "observation key frame out of range");
-        }
-    }
-    seen.assign((size_t)m->n_maps * S, 0);
+// the host-pointer flavour's walk of the list (check_map_indices walked the maps)
+static int check_entries(const planar_local_map* m, int L, const int32_t* entry_map, const int32_t* entry_kf) {
+    std::vector<uint8_t> seen((size_t)m->n_maps * m->kf_stride, 0);
     for (int l = 0; l < L; l++) {
         const int g = entry_map[l];
         PLANAR_REQUIRE(in_range_h(g, m->n_maps), PLANAR_EINVAL, "entry_map out of range");
         PLANAR_REQUIRE(in_range_h(entry_kf[l], m->n_kf[g]), PLANAR_EINVAL, "entry_kf out of range");
-        uint8_t& s = seen[(size_t)g * S + entry_kf[l]];
+        uint8_t& s = seen[(size_t)g * m->kf_stride + entry_kf[l]];
         PLANAR_REQUIRE(!s, PLANAR_EINVAL, "the list names the same key frame twice");
         s = 1;
     }
@@ -289,7 +256,7 @@ extern "C" {
 
 int planar_connections_ws_create(planar_ctx* ctx, int max_entries, int max_maps, int kf_stride, planar_connections_ws** out) {
     PLANAR_REQUIRE(ctx && out, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(max_entries >= 1 && max_maps >= 1 && kf_stride >= 1 && kf_stride <= connections::MAXK, PLANAR_EINVAL,
+    PLANAR_REQUIRE(max_entries >= 1 && max_maps >= 1 && kf_stride >= 1 && kf_stride <= MAXK, PLANAR_EINVAL,
                    "max_entries, max_maps >= 1 and 1 <= kf_stride <= PLANAR_LOCALMAP_MAX_KEYFRAMES required");
     planar_connections_ws* p = new planar_connections_ws;  // the device block is allocated by the first call: creating the handle touches no device
     p->ctx = ctx; p->max_entries = max_entries; p->max_maps = max_maps; p->kf_stride = kf_stride;
@@ -301,24 +268,18 @@ void planar_connections_ws_destroy(planar_connections_ws* ws) { delete ws; }
 
 int planar_connections_ws_set_profiling(planar_connections_ws* ws, int enable) {
     PLANAR_REQUIRE(ws != nullptr, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    ws->prof.on = enable != 0;
-    ws->prof.reset();
-    return PLANAR_OK;
+    return set_profiling(ws->ctx, {&ws->prof}, enable);
 }
 int planar_connections_ws_get_profile(planar_connections_ws* ws, double* total_ms /* [3] */, int64_t* calls) {
     PLANAR_REQUIRE(ws && total_ms && calls, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    return ws->prof.sum(total_ms, calls);
+    return get_profile(ws->ctx, {&ws->prof}, total_ms, calls);
 }
 
 int planar_update_connections_dev(planar_connections_ws* ws, const planar_local_map* map, const planar_covis_graph* graph, int L, const int32_t* d_entry_map,
                                   const int32_t* d_entry_kf, int32_t* d_new_parent, int32_t* d_status) {
     if (int rc = connections::check_args(ws, map, graph, L, d_entry_map && d_entry_kf && d_new_parent && d_status)) return rc;
     planar_ctx* ctx = ws->ctx;
-    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ws->buf.p)
-        if (int rc = ws->buf.alloc(connections::ws_bytes((size_t)ws->max_entries, (size_t)ws->max_maps, (size_t)ws->kf_stride))) return rc;
+    if (int rc = ensure_block(ctx, ws->buf, connections::ws_bytes((size_t)ws->max_entries, (size_t)ws->max_maps, (size_t)ws->kf_stride))) return rc;
     const size_t S = map->kf_stride, G = map->n_maps, nl = (size_t)L;
     connections::Args a{};
     a.n_maps = map->n_maps; a.S = map->kf_stride; a.SS = map->slot_stride; a.PS = map->pt_stride; a.obs_cap = map->obs_cap;
@@ -344,26 +305,18 @@ int planar_update_connections_dev(planar_connections_ws* ws, const planar_local_
 int planar_update_connections(planar_connections_ws* ws, const planar_local_map* map, const planar_covis_graph* graph, int L, const int32_t* entry_map,
                               const int32_t* entry_kf, int32_t* new_parent, int32_t* status) {
     if (int rc = connections::check_args(ws, map, graph, L, entry_map && entry_kf && new_parent && status)) return rc;
-    if (int rc = connections::check_indices(map, L, entry_map, entry_kf)) return rc;
+    if (int rc = check_map_indices(*map, NEEDS_CONNECTIONS)) return rc;
+    if (int rc = connections::check_entries(map, L, entry_map, entry_kf)) return rc;
     planar_ctx* ctx = ws->ctx;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
     planar_local_map d = *map;                                       // the arrays the call does not read stay as they are and are not touched
-    const size_t G = map->n_maps, k = G * map->kf_stride, nl = (size_t)L;
-    s.in_field(d.n_kf, G); s.in_field(d.kf_rank, k); s.in_field(d.n_slots, k); s.in_field(d.kf_pts, k * map->slot_stride); s.in_field(d.n_pts, G);
-    s.in_field(d.pt_bad, G * map->pt_stride); s.in_field(d.obs_off, G * (map->pt_stride + 1)); s.in_field(d.obs_kf, G * map->obs_cap);
-    const auto d_conn = s.inout(graph->conn_w, k * map->kf_stride), d_ord_kf = s.inout(graph->ord_kf, k * map->kf_stride), d_ord_w = s.inout(graph->ord_w, k * map->kf_stride);
-    const auto d_ord_n = s.inout(graph->ord_n, k), d_parent = s.inout(graph->parent, k), d_covis = s.inout(graph->covis, k * connections::NCOVIS);
-    const auto d_first = s.inout(graph->first_connection, k);
-    const auto d_mnid = s.in(graph->kf_mnid, k);
+    planar_covis_graph dg = *graph;
+    stage_map(s, d, NEEDS_CONNECTIONS); stage_graph(s, dg, d, true, false);
+    const size_t nl = (size_t)L;
     const auto d_map = s.in(entry_map, nl), d_kf = s.in(entry_kf, nl);
     const auto d_np = s.out(new_parent, nl), d_status = s.out(status, nl);
-    return s.run(ctx->stream, [&] {
-        planar_covis_graph dg;
-        dg.conn_w = d_conn; dg.ord_n = d_ord_n; dg.ord_kf = d_ord_kf; dg.ord_w = d_ord_w; dg.first_connection = d_first; dg.kf_mnid = d_mnid; dg.parent = d_parent;
-        dg.covis = d_covis;
-        return planar_update_connections_dev(ws, &d, &dg, L, d_map, d_kf, d_np, d_status);
-    });
+    return s.run(ctx->stream, [&] { return planar_update_connections_dev(ws, &d, &dg, L, d_map, d_kf, d_np, d_status); });
 }
 
 }  // extern "C"

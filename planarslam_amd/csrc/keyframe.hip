@@ -13,15 +13,15 @@
 //                             scattered with the insertion into the workspace's buffer and copied back
 // Integers and copies only but for the comparisons and the ratio of NeedNewKeyFrame.  Every index read from device memory is checked against its range before it
 // is used; a frame or entry that meets one outside ends with status 2 and changes nothing.
+#include "map_view.h"
 #include "ref_arith.h"
 #include "wave_ops.h"
 
 namespace planar {
 namespace keyframe {
 
-constexpr int NT = 256, NW = NT / 64, MAXK = PLANAR_LOCALMAP_MAX_KEYFRAMES, MAXN = PLANAR_KEYFRAME_MAX_KEYS, NCOVIS = 10, MAX_SLOT_STRIDE = 1 << 20;
-constexpr int WALK_MIN = 100, LINE_CUT = 51, NOUT = PLANAR_NEEDKF_NOUT;
-constexpr int NO_ENTRY = -1, TWICE = -2, NO_MARK = 0x7fffffff;
+constexpr int NT = 256, NW = NT / 64, MAXN = PLANAR_KEYFRAME_MAX_KEYS;
+constexpr int WALK_MIN = 100, LINE_CUT = 51, NOUT = PLANAR_NEEDKF_NOUT, NO_MARK = 0x7fffffff;
 
 struct Args {
     planar_map_edit m;               // m.graph is a host pointer: the kernels read g
@@ -40,8 +40,6 @@ struct Args {
     int32_t* mark_pt; int32_t* mark_ml;   // [n_maps][PS] / [n_maps][LS]   the first slot that gives the point / line its observation
     int32_t* tmp_pt; int32_t* tmp_ml;     // [n_maps][obs_cap] / [n_maps][ml_obs_cap]
 };
-
-__device__ inline bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------- NeedNewKeyFrame
 __global__ __launch_bounds__(NT) void keyframe_need_kernel(Args a) {
@@ -204,12 +202,6 @@ __device__ int select_creators(const float* z, int n, bool points, float th, con
     }
     __syncthreads();
     return nc;
-}
-
-__device__ inline void copy_desc(uint8_t* dst, const uint8_t* src) {
-    const uint32_t* s = (const uint32_t*)src;
-    uint32_t* d = (uint32_t*)dst;
-    for (int w = 0; w < 8; w++) d[w] = s[w];
 }
 
 __global__ __launch_bounds__(NT) void keyframe_create_kernel(Args a) {
@@ -458,44 +450,28 @@ static size_t ws_bytes(const planar_keyframe_ws* ws) {
     return 4 * (size_t)ws->max_maps * (1 + (size_t)ws->pt_stride + ws->ml_stride + ws->obs_cap + ws->ml_obs_cap) + 64;
 }
 
-static inline bool in_range_h(int v, int n) { return (unsigned)v < (unsigned)n; }
-static inline bool aligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
-enum Need { FOR_NEED, FOR_CREATE, FOR_ADD };
-
-static int check_map(const planar_keyframe_ws* ws, const planar_map_edit* m, Need what) {
+// needs: NEEDS_NEED, NEEDS_CREATE or NEEDS_ADD, which also says which of the three calls it is
+static int check_map(const planar_keyframe_ws* ws, const planar_map_edit* m, uint64_t needs) {
     PLANAR_REQUIRE(ws && m, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(m->n_kf && m->n_slots && m->kf_pts && m->n_pts && m->pt_bad && m->pt_nobs && m->n_ml && m->ml_nobs, PLANAR_EINVAL, "null array in the map view");
-    if (what != FOR_NEED)
-        PLANAR_REQUIRE(m->kf_rank && m->n_line_slots && m->kf_lines && m->obs_off && m->obs_kf && m->ml_bad && m->ml_observed && m->ml_obs_off && m->ml_obs_kf,
-                       PLANAR_EINVAL, "null array in the map view");
-    if (what == FOR_CREATE) {
-        PLANAR_REQUIRE(m->kf_bad && m->parent && m->covis && m->child_off && m->pt_xw && m->pt_normal && m->pt_min_dist && m->pt_max_dist && m->pt_desc && m->ml_xw6 &&
-                           m->ml_normal && m->ml_min_dist && m->ml_max_dist && m->ml_desc,
-                       PLANAR_EINVAL, "null array in the map view");
+    if (int rc = check_map_arrays(*m, needs)) return rc;
+    if (needs == NEEDS_CREATE) {
         PLANAR_REQUIRE(aligned(m->pt_desc, 4) && aligned(m->ml_desc, 4) && aligned(m->ml_xw6, 8) && aligned(m->ml_normal, 8), PLANAR_EINVAL,
                        "misaligned descriptor / double array in the map view");
-        if (const planar_covis_graph* gr = m->graph)
-            PLANAR_REQUIRE(gr->conn_w && gr->ord_n && gr->ord_kf && gr->ord_w && gr->first_connection && gr->kf_mnid && gr->parent && gr->covis, PLANAR_EINVAL,
-                           "null array in the graph");
+        if (int rc = m->graph ? check_graph_arrays(m->graph) : PLANAR_OK) return rc;
     }
-    PLANAR_REQUIRE(m->kf_stride >= 1 && m->kf_stride <= MAXK, PLANAR_EINVAL, "1 <= kf_stride <= PLANAR_LOCALMAP_MAX_KEYFRAMES required");
-    PLANAR_REQUIRE(m->n_maps >= 1 && m->slot_stride >= 1 && m->line_slot_stride >= 1 && m->pt_stride >= 1 && m->ml_stride >= 1 && m->obs_cap >= 1 && m->ml_obs_cap >= 1,
-                   PLANAR_EINVAL, "n_maps, the strides and the capacities of the map view must be >= 1");
-    PLANAR_REQUIRE(m->slot_stride <= MAX_SLOT_STRIDE && m->line_slot_stride <= MAX_SLOT_STRIDE, PLANAR_EINVAL, "slot stride above 2^20");
-    PLANAR_REQUIRE(m->n_maps <= ws->max_maps && m->pt_stride <= ws->pt_stride && m->ml_stride <= ws->ml_stride && m->obs_cap <= ws->obs_cap &&
-                       m->ml_obs_cap <= ws->ml_obs_cap,
+    if (int rc = check_map_sizes(*m, needs)) return rc;
+    PLANAR_REQUIRE(m->n_maps <= ws->max_maps && m->pt_stride <= ws->pt_stride && m->ml_stride <= ws->ml_stride && m->obs_cap <= ws->obs_cap && m->ml_obs_cap <= ws->ml_obs_cap,
                    PLANAR_EINVAL, "the map's n_maps / strides / capacities exceed the workspace's");
     return PLANAR_OK;
 }
 
-static int check_frames(const planar_keyframe_ws* ws, const planar_kf_frames* f, Need what) {
+static int check_frames(const planar_keyframe_ws* ws, const planar_kf_frames* f, uint64_t needs) {
     PLANAR_REQUIRE(f != nullptr, PLANAR_EINVAL, "null argument");
     PLANAR_REQUIRE(f->B >= 1, PLANAR_EINVAL, "B >= 1 required");
     PLANAR_REQUIRE(f->B <= ws->max_batch, PLANAR_EINVAL, "B exceeds the workspace's max_batch");
     PLANAR_REQUIRE(f->frame_stride >= 1 && f->frame_line_stride >= 1, PLANAR_EINVAL, "frame_stride and frame_line_stride must be >= 1");
     PLANAR_REQUIRE(f->map_of && f->n_frame && f->frame_match && f->depth && f->n_frame_lines && f->frame_line_match, PLANAR_EINVAL, "null array in the frame view");
-    if (what == FOR_NEED) {
+    if (needs == NEEDS_NEED) {
         PLANAR_REQUIRE(f->outlier && f->line_outlier, PLANAR_EINVAL, "null array in the frame view");
         PLANAR_REQUIRE(f->frame_stride <= MAX_SLOT_STRIDE && f->frame_line_stride <= MAX_SLOT_STRIDE, PLANAR_EINVAL, "frame stride above 2^20");
     } else {
@@ -509,56 +485,7 @@ static int check_frames(const planar_keyframe_ws* ws, const planar_kf_frames* f,
     return PLANAR_OK;
 }
 
-// the host-pointer flavours' walk of the maps: every index a kernel could meet, on host arrays
-static int check_map_indices(const planar_map_edit* m, Need what) {
-    const int S = m->kf_stride, PS = m->pt_stride, LS = m->ml_stride;
-    std::vector<uint8_t> seen;
-    for (int g = 0; g < m->n_maps; g++) {
-        const int nk = m->n_kf[g], np = m->n_pts[g], nm = m->n_ml[g];
-        PLANAR_REQUIRE(nk >= 0 && nk <= S, PLANAR_EINVAL, "n_kf outside [0, kf_stride]");
-        PLANAR_REQUIRE(np >= 0 && np <= PS, PLANAR_EINVAL, "n_pts outside [0, pt_stride]");
-        PLANAR_REQUIRE(nm >= 0 && nm <= LS, PLANAR_EINVAL, "n_ml outside [0, ml_stride]");
-        const size_t gk = (size_t)g * S;
-        seen.assign((size_t)nk, 0);
-        for (int k = 0; k < nk; k++) {
-            if (what != FOR_NEED) {
-                const int r = m->kf_rank[gk + k];
-                PLANAR_REQUIRE(in_range_h(r, nk) && !seen[r], PLANAR_EINVAL, "kf_rank is not a permutation of [0, n_kf)");
-                seen[r] = 1;
-            }
-            const int ns = m->n_slots[gk + k];
-            PLANAR_REQUIRE(ns >= 0 && ns <= m->slot_stride, PLANAR_EINVAL, "slot count outside its stride");
-            for (int s = 0; s < ns; s++) {
-                const int id = m->kf_pts[(gk + k) * m->slot_stride + s];
-                PLANAR_REQUIRE(id >= -1 && id < np, PLANAR_EINVAL, "map-point slot out of range");
-            }
-            if (what == FOR_NEED) continue;
-            const int nls = m->n_line_slots[gk + k];
-            PLANAR_REQUIRE(nls >= 0 && nls <= m->line_slot_stride, PLANAR_EINVAL, "line slot count outside its stride");
-            for (int s = 0; s < nls; s++) {
-                const int id = m->kf_lines[(gk + k) * m->line_slot_stride + s];
-                PLANAR_REQUIRE(id >= -1 && id < nm, PLANAR_EINVAL, "map-line slot out of range");
-            }
-        }
-        if (what == FOR_NEED) continue;
-        const int32_t* oo = m->obs_off + (size_t)g * (PS + 1);
-        PLANAR_REQUIRE(oo[0] == 0, PLANAR_EINVAL, "obs_off out of range");
-        for (int p = 0; p < np; p++) {
-            PLANAR_REQUIRE(oo[p] >= 0 && oo[p + 1] >= oo[p] && oo[p + 1] <= m->obs_cap, PLANAR_EINVAL, "obs_off out of range");
-            for (int o = oo[p]; o < oo[p + 1]; o++)
-                PLANAR_REQUIRE(in_range_h(m->obs_kf[(size_t)g * m->obs_cap + o], nk), PLANAR_EINVAL, "observation key frame out of range");
-        }
-        const int32_t* lo = m->ml_obs_off + (size_t)g * (LS + 1);
-        PLANAR_REQUIRE(lo[0] == 0, PLANAR_EINVAL, "ml_obs_off out of range");
-        for (int p = 0; p < nm; p++) {
-            PLANAR_REQUIRE(lo[p] >= 0 && lo[p + 1] >= lo[p] && lo[p + 1] <= m->ml_obs_cap, PLANAR_EINVAL, "ml_obs_off out of range");
-            for (int o = lo[p]; o < lo[p + 1]; o++)
-                PLANAR_REQUIRE(in_range_h(m->ml_obs_kf[(size_t)g * m->ml_obs_cap + o], nk), PLANAR_EINVAL, "line observation key frame out of range");
-        }
-    }
-    return PLANAR_OK;
-}
-
+// the host-pointer flavours' walk of the frames (check_map_indices walked the maps)
 static int check_frame_indices(const planar_map_edit* m, const planar_kf_frames* f, const uint8_t* chosen) {
     for (int b = 0; b < f->B; b++) {
         if (chosen && !chosen[b]) continue;
@@ -576,36 +503,6 @@ static int check_frame_indices(const planar_map_edit* m, const planar_kf_frames*
             PLANAR_REQUIRE(id >= -1 && id < m->n_ml[g], PLANAR_EINVAL, "frame_line_match out of range");
         }
     }
-    return PLANAR_OK;
-}
-
-// the arrays of the map view staged on the caller's copy of it: all of them in and out, or only what planar_need_new_key_frame reads, in
-template <typename T> static void stage(Stager& s, T*& field, size_t count, bool back) { if (field) s.add<T>(field, back ? field : nullptr, count, &field); }
-
-static void stage_map(Stager& s, planar_map_edit& d, planar_covis_graph& dg, Need what) {
-    const size_t G = d.n_maps, k = G * d.kf_stride, P = G * d.pt_stride, Lm = G * d.ml_stride;
-    const bool w = what != FOR_NEED;
-    stage(s, d.n_kf, G, w); stage(s, d.n_slots, k, w); stage(s, d.kf_pts, k * d.slot_stride, w); stage(s, d.n_pts, G, w); stage(s, d.pt_bad, P, w);
-    stage(s, d.pt_nobs, P, w); stage(s, d.n_ml, G, w); stage(s, d.ml_nobs, Lm, w);
-    if (!w) return;
-    stage(s, d.kf_rank, k, w); stage(s, d.n_line_slots, k, w); stage(s, d.kf_lines, k * d.line_slot_stride, w); stage(s, d.obs_off, G * (d.pt_stride + 1), w);
-    stage(s, d.obs_kf, G * d.obs_cap, w); stage(s, d.ml_bad, Lm, w); stage(s, d.ml_observed, Lm, w); stage(s, d.ml_obs_off, G * (d.ml_stride + 1), w);
-    stage(s, d.ml_obs_kf, G * d.ml_obs_cap, w);
-    if (what != FOR_CREATE) return;
-    stage(s, d.kf_bad, k, w); stage(s, d.parent, k, w); stage(s, d.covis, k * NCOVIS, w); stage(s, d.child_off, G * (d.kf_stride + 1), w);
-    stage(s, d.pt_xw, P * 3, w); stage(s, d.pt_normal, P * 3, w); stage(s, d.pt_min_dist, P, w); stage(s, d.pt_max_dist, P, w); stage(s, d.pt_desc, P * 32, w);
-    stage(s, d.ml_xw6, Lm * 6, w); stage(s, d.ml_normal, Lm * 3, w); stage(s, d.ml_min_dist, Lm, w); stage(s, d.ml_max_dist, Lm, w); stage(s, d.ml_desc, Lm * 32, w);
-    if (!d.graph) return;
-    // where parent / covis of the graph are the map's own arrays the two staged copies get the same stores
-    dg = *d.graph; d.graph = &dg;
-    const size_t kk = k * d.kf_stride;
-    stage(s, dg.conn_w, kk, w); stage(s, dg.ord_n, k, w); stage(s, dg.first_connection, k, w); stage(s, dg.parent, k, w); stage(s, dg.covis, k * NCOVIS, w);
-    s.add<int32_t>(dg.kf_mnid, const_cast<int32_t*>(dg.kf_mnid), k, &dg.kf_mnid);
-}
-
-static int ensure_ws(planar_keyframe_ws* ws) {
-    PLANAR_HIP_CHECK(hipSetDevice(ws->ctx->device));
-    if (!ws->buf.p) return ws->buf.alloc(ws_bytes(ws));
     return PLANAR_OK;
 }
 
@@ -637,25 +534,17 @@ void planar_keyframe_ws_destroy(planar_keyframe_ws* ws) { delete ws; }
 
 int planar_keyframe_ws_set_profiling(planar_keyframe_ws* ws, int enable) {
     PLANAR_REQUIRE(ws != nullptr, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    for (LaunchProfile* p : {&ws->prof_need, &ws->prof_create, &ws->prof_add}) { p->on = enable != 0; p->reset(); }
-    return PLANAR_OK;
+    return set_profiling(ws->ctx, {&ws->prof_need, &ws->prof_create, &ws->prof_add}, enable);
 }
 int planar_keyframe_ws_get_profile(planar_keyframe_ws* ws, double* total_ms /* [3] */, int64_t* calls /* [3] */) {
     PLANAR_REQUIRE(ws && total_ms && calls, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    int i = 0;
-    for (LaunchProfile* p : {&ws->prof_need, &ws->prof_create, &ws->prof_add}) {
-        if (int rc = p->sum(total_ms + i, calls + i)) return rc;
-        i++;
-    }
-    return PLANAR_OK;
+    return get_profile(ws->ctx, {&ws->prof_need, &ws->prof_create, &ws->prof_add}, total_ms, calls);
 }
 
 int planar_need_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const int32_t* d_ref_kf,
                                   const planar_need_kf_params* d_params, int32_t* d_out) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_NEED)) return rc;
-    if (int rc = keyframe::check_frames(ws, fr, keyframe::FOR_NEED)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_NEED)) return rc;
+    if (int rc = keyframe::check_frames(ws, fr, NEEDS_NEED)) return rc;
     PLANAR_REQUIRE(d_ref_kf && d_params && d_out, PLANAR_EINVAL, "null argument");
     PLANAR_HIP_CHECK(hipSetDevice(ws->ctx->device));
     keyframe::Args a{};
@@ -671,22 +560,20 @@ int planar_need_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edit*
 
 int planar_need_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const int32_t* ref_kf,
                               const planar_need_kf_params* params, int32_t* out) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_NEED)) return rc;
-    if (int rc = keyframe::check_frames(ws, fr, keyframe::FOR_NEED)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_NEED)) return rc;
+    if (int rc = keyframe::check_frames(ws, fr, NEEDS_NEED)) return rc;
     PLANAR_REQUIRE(ref_kf && params && out, PLANAR_EINVAL, "null argument");
-    if (int rc = keyframe::check_map_indices(map, keyframe::FOR_NEED)) return rc;
+    if (int rc = check_map_indices(*map, NEEDS_NEED)) return rc;
     if (int rc = keyframe::check_frame_indices(map, fr, nullptr)) return rc;
-    for (int b = 0; b < fr->B; b++) PLANAR_REQUIRE(keyframe::in_range_h(ref_kf[b], map->n_kf[fr->map_of[b]]), PLANAR_EINVAL, "ref_kf out of range");
+    for (int b = 0; b < fr->B; b++) PLANAR_REQUIRE(in_range_h(ref_kf[b], map->n_kf[fr->map_of[b]]), PLANAR_EINVAL, "ref_kf out of range");
     PLANAR_HIP_CHECK(hipSetDevice(ws->ctx->device));
     Stager s;
     planar_map_edit d = *map;
-    planar_covis_graph dg{};
     planar_kf_frames f = *fr;
-    keyframe::stage_map(s, d, dg, keyframe::FOR_NEED);
+    stage_map(s, d, NEEDS_NEED, false);
     const size_t B = fr->B, nf = B * fr->frame_stride, nl = B * fr->frame_line_stride;
     s.in_field(f.map_of, B); s.in_field(f.n_frame, B); s.in_field(f.depth, nf); s.in_field(f.n_frame_lines, B);
-    keyframe::stage(s, f.frame_match, nf, true); keyframe::stage(s, f.outlier, nf, true); keyframe::stage(s, f.frame_line_match, nl, true);
-    keyframe::stage(s, f.line_outlier, nl, true);
+    s.inout_field(f.frame_match, nf); s.inout_field(f.outlier, nf); s.inout_field(f.frame_line_match, nl); s.inout_field(f.line_outlier, nl);
     const auto d_ref = s.in(ref_kf, B);
     const auto d_prm = s.in(params, B);
     const auto d_out = s.out(out, B * keyframe::NOUT);
@@ -696,11 +583,11 @@ int planar_need_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* map
 int planar_create_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const uint8_t* d_create, const float* d_th_depth,
                                     const int32_t* d_new_rank, const int32_t* d_mnid, int32_t* d_new_kf, int32_t* d_created_pt, int32_t* d_n_created_pt,
                                     int32_t* d_created_ml, int32_t* d_n_created_ml, int32_t* d_status) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_CREATE)) return rc;
-    if (int rc = keyframe::check_frames(ws, fr, keyframe::FOR_CREATE)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_CREATE)) return rc;
+    if (int rc = keyframe::check_frames(ws, fr, NEEDS_CREATE)) return rc;
     PLANAR_REQUIRE(d_create && d_th_depth && d_new_rank && d_mnid && d_new_kf && d_created_pt && d_n_created_pt && d_created_ml && d_n_created_ml && d_status,
                    PLANAR_EINVAL, "null argument");
-    if (int rc = keyframe::ensure_ws(ws)) return rc;
+    if (int rc = ensure_block(ws->ctx, ws->buf, keyframe::ws_bytes(ws))) return rc;
     keyframe::Args a{};
     a.m = *map; a.f = *fr; a.has_graph = map->graph != nullptr;
     if (map->graph) a.g = *map->graph;
@@ -722,11 +609,11 @@ int planar_create_new_key_frame_dev(planar_keyframe_ws* ws, const planar_map_edi
 int planar_create_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* map, const planar_kf_frames* fr, const uint8_t* create, const float* th_depth,
                                 const int32_t* new_rank, const int32_t* mnid, int32_t* new_kf, int32_t* created_pt, int32_t* n_created_pt, int32_t* created_ml,
                                 int32_t* n_created_ml, int32_t* status) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_CREATE)) return rc;
-    if (int rc = keyframe::check_frames(ws, fr, keyframe::FOR_CREATE)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_CREATE)) return rc;
+    if (int rc = keyframe::check_frames(ws, fr, NEEDS_CREATE)) return rc;
     PLANAR_REQUIRE(create && th_depth && new_rank && mnid && new_kf && created_pt && n_created_pt && created_ml && n_created_ml && status, PLANAR_EINVAL,
                    "null argument");
-    if (int rc = keyframe::check_map_indices(map, keyframe::FOR_CREATE)) return rc;
+    if (int rc = check_map_indices(*map, NEEDS_ADD)) return rc;      // of the rows the call needs beyond those it only stores: it follows no index into them
     if (int rc = keyframe::check_frame_indices(map, fr, create)) return rc;
     {
         std::vector<uint8_t> seen((size_t)map->n_maps, 0);
@@ -743,12 +630,14 @@ int planar_create_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* m
     planar_map_edit d = *map;
     planar_covis_graph dg{};
     planar_kf_frames f = *fr;
-    keyframe::stage_map(s, d, dg, keyframe::FOR_CREATE);
+    stage_map(s, d, NEEDS_CREATE, true);
+    // where parent / covis of the graph are the map's own arrays the two staged copies get the same stores
+    if (d.graph) { dg = *d.graph; d.graph = &dg; stage_graph(s, dg, d, false, true); }
     const size_t B = fr->B, nf = B * fr->frame_stride, nl = B * fr->frame_line_stride;
     s.in_field(f.map_of, B); s.in_field(f.n_frame, B); s.in_field(f.depth, nf); s.in_field(f.u_right, nf); s.in_field(f.xw, nf * 3); s.in_field(f.normal, nf * 3);
     s.in_field(f.min_dist, nf); s.in_field(f.max_dist, nf); s.in_field(f.desc, nf * 32); s.in_field(f.n_frame_lines, B); s.in_field(f.depth_line, nl);
     s.in_field(f.xw6, nl * 6); s.in_field(f.line_normal, nl * 3); s.in_field(f.line_min_dist, nl); s.in_field(f.line_max_dist, nl); s.in_field(f.line_desc, nl * 32);
-    keyframe::stage(s, f.frame_match, nf, true); keyframe::stage(s, f.frame_line_match, nl, true);
+    s.inout_field(f.frame_match, nf); s.inout_field(f.frame_line_match, nl);
     f.outlier = nullptr; f.line_outlier = nullptr;
     const auto d_create = s.in(create, B);
     const auto d_th = s.in(th_depth, B);
@@ -761,11 +650,11 @@ int planar_create_new_key_frame(planar_keyframe_ws* ws, const planar_map_edit* m
 
 int planar_add_observations_dev(planar_keyframe_ws* ws, const planar_map_edit* map, int L, const int32_t* d_entry_map, const int32_t* d_entry_kf,
                                 const float* d_u_right, uint8_t* d_added_pt, uint8_t* d_added_ml, int32_t* d_status) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_ADD)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_ADD)) return rc;
     PLANAR_REQUIRE(d_entry_map && d_entry_kf && d_u_right && d_added_pt && d_added_ml && d_status, PLANAR_EINVAL, "null argument");
     PLANAR_REQUIRE(L >= 1, PLANAR_EINVAL, "L >= 1 required");
     PLANAR_REQUIRE(L <= ws->max_batch, PLANAR_EINVAL, "L exceeds the workspace's max_batch");
-    if (int rc = keyframe::ensure_ws(ws)) return rc;
+    if (int rc = ensure_block(ws->ctx, ws->buf, keyframe::ws_bytes(ws))) return rc;
     keyframe::Args a{};
     a.m = *map; a.L = L; a.entry_map = d_entry_map; a.entry_kf = d_entry_kf; a.u_right = d_u_right; a.added_pt = d_added_pt; a.added_ml = d_added_ml;
     a.status = d_status;
@@ -784,17 +673,17 @@ int planar_add_observations_dev(planar_keyframe_ws* ws, const planar_map_edit* m
 
 int planar_add_observations(planar_keyframe_ws* ws, const planar_map_edit* map, int L, const int32_t* entry_map, const int32_t* entry_kf, const float* u_right,
                             uint8_t* added_pt, uint8_t* added_ml, int32_t* status) {
-    if (int rc = keyframe::check_map(ws, map, keyframe::FOR_ADD)) return rc;
+    if (int rc = keyframe::check_map(ws, map, NEEDS_ADD)) return rc;
     PLANAR_REQUIRE(entry_map && entry_kf && u_right && added_pt && added_ml && status, PLANAR_EINVAL, "null argument");
     PLANAR_REQUIRE(L >= 1, PLANAR_EINVAL, "L >= 1 required");
     PLANAR_REQUIRE(L <= ws->max_batch, PLANAR_EINVAL, "L exceeds the workspace's max_batch");
-    if (int rc = keyframe::check_map_indices(map, keyframe::FOR_ADD)) return rc;
+    if (int rc = check_map_indices(*map, NEEDS_ADD)) return rc;
     {
         std::vector<uint8_t> seen((size_t)map->n_maps, 0);
         for (int l = 0; l < L; l++) {
             const int g = entry_map[l];
-            PLANAR_REQUIRE(keyframe::in_range_h(g, map->n_maps), PLANAR_EINVAL, "entry_map out of range");
-            PLANAR_REQUIRE(keyframe::in_range_h(entry_kf[l], map->n_kf[g]), PLANAR_EINVAL, "entry_kf out of range");
+            PLANAR_REQUIRE(in_range_h(g, map->n_maps), PLANAR_EINVAL, "entry_map out of range");
+            PLANAR_REQUIRE(in_range_h(entry_kf[l], map->n_kf[g]), PLANAR_EINVAL, "entry_kf out of range");
             PLANAR_REQUIRE(!seen[g], PLANAR_EINVAL, "two entries name the same map");
             seen[g] = 1;
         }
@@ -802,8 +691,7 @@ int planar_add_observations(planar_keyframe_ws* ws, const planar_map_edit* map, 
     PLANAR_HIP_CHECK(hipSetDevice(ws->ctx->device));
     Stager s;
     planar_map_edit d = *map;
-    planar_covis_graph dg{};
-    keyframe::stage_map(s, d, dg, keyframe::FOR_ADD);
+    stage_map(s, d, NEEDS_ADD, true);
     const size_t nl = (size_t)L;
     const auto d_map = s.in(entry_map, nl), d_kf = s.in(entry_kf, nl);
     const auto d_ur = s.in(u_right, nl * map->slot_stride);

@@ -13,14 +13,14 @@
 //                              with the rows of the map that planar_is_in_frustum_points/_lines_dev and the projection matchers read next
 // Integers only; no floating-point arithmetic and no floating-point atomics: the gathered rows are copies.  Every index read from device memory is checked
 // against its range before it is used; a frame that meets one outside ends with status 2 and empty lists.
+#include "map_view.h"
 #include "ref_arith.h"
 #include "wave_ops.h"
 
 namespace planar {
 namespace localmap {
 
-static_assert(PLANAR_LOCALMAP_MAX_KEYFRAMES == PLANAR_KFDB_MAX_KEYFRAMES, "one key-frame limit for the map views");
-constexpr int NT = 256, NW = NT / 64, MAXK = PLANAR_LOCALMAP_MAX_KEYFRAMES, NCOVIS = 10, KF_CAP = 80, UNMARKED = 0x7f7f7f7f, MAX_SLOT_STRIDE = 1 << 20;
+constexpr int NT = 256, NW = NT / 64, KF_CAP = 80, UNMARKED = 0x7f7f7f7f;
 constexpr int NSTATE = 8;      // per frame: list length, error (key frames), reference key frame, status (0 new list, 1 kept list), error (slots)
 enum { ST_N = 0, ST_ERR = 1, ST_REF = 2, ST_STATUS = 3, ST_ERR2 = 4 };
 
@@ -47,8 +47,6 @@ struct Args {
     uint8_t* pt_held;    // [B][pt_stride]     the frame holds the point (frame_match names it and it is not bad)
     uint8_t* ml_held;    // [B][ml_stride]
 };
-
-__device__ inline bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
 
 __global__ __launch_bounds__(NT) void localmap_keyframes_kernel(Args a) {
     __shared__ int32_t s_cnt[MAXK], s_byrank[MAXK], s_list[MAXK];
@@ -252,13 +250,6 @@ __global__ __launch_bounds__(NT) void localmap_count_kernel(Args a) {
     }
 }
 
-__device__ inline void copy32(uint8_t* dst, const uint8_t* src) {      // one descriptor; both on 4-byte boundaries
-    const uint32_t* s = (const uint32_t*)src;
-    uint32_t* d = (uint32_t*)dst;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d[i] = s[i];
-}
-
 // Z = 0: points, 1: lines - two instances, so that each holds only its own half of the output pointers in SGPRs
 template <int Z> __global__ __launch_bounds__(NT) void localmap_gather_kernel(Args a) {
     __shared__ int s_w[NW];
@@ -309,7 +300,7 @@ template <int Z> __global__ __launch_bounds__(NT) void localmap_gather_kernel(Ar
                 a.lp_valid[o] = !a.pt_held[(size_t)b * a.m.pt_stride + id];
                 for (int c = 0; c < 3; c++) { a.lp_xw[o * 3 + c] = a.m.pt_xw[q * 3 + c]; a.lp_normal[o * 3 + c] = a.m.pt_normal[q * 3 + c]; }
                 a.lp_min_dist[o] = a.m.pt_min_dist[q]; a.lp_max_dist[o] = a.m.pt_max_dist[q];
-                copy32(a.lp_desc + o * 32, a.m.pt_desc + q * 32);
+                copy_desc(a.lp_desc + o * 32, a.m.pt_desc + q * 32);
                 a.lp_observed[o] = oo[1] > oo[0];
             } else {
                 const size_t o = (size_t)b * a.ll_stride + pos, q = (size_t)g * a.m.ml_stride + id;
@@ -318,7 +309,7 @@ template <int Z> __global__ __launch_bounds__(NT) void localmap_gather_kernel(Ar
                 for (int c = 0; c < 6; c++) a.ll_xw6[o * 6 + c] = a.m.ml_xw6[q * 6 + c];
                 for (int c = 0; c < 3; c++) a.ll_normal[o * 3 + c] = a.m.ml_normal[q * 3 + c];
                 a.ll_min_dist[o] = a.m.ml_min_dist[q]; a.ll_max_dist[o] = a.m.ml_max_dist[q];
-                copy32(a.ll_desc + o * 32, a.m.ml_desc + q * 32);
+                copy_desc(a.ll_desc + o * 32, a.m.ml_desc + q * 32);
                 a.ll_observed[o] = a.m.ml_observed[q] != 0;
             }
         }
@@ -346,73 +337,26 @@ static int check_args(const planar_local_map_ws* ws, const planar_local_map* m, 
                       bool points, const void* lp_desc, int lp_stride, bool lines, const void* ll_xw6, const void* ll_normal, const void* ll_desc, int ll_stride,
                       const void* status) {
     PLANAR_REQUIRE(ws && m && frame && kf && points && lines && status, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(m->n_kf && m->kf_bad && m->kf_rank && m->covis && m->parent && m->child_off && m->child && m->n_slots && m->kf_pts && m->n_line_slots && m->kf_lines &&
-                   m->n_pts && m->pt_bad && m->obs_off && m->obs_kf && m->pt_xw && m->pt_normal && m->pt_min_dist && m->pt_max_dist && m->pt_desc && m->n_ml &&
-                   m->ml_bad && m->ml_observed && m->ml_xw6 && m->ml_normal && m->ml_min_dist && m->ml_max_dist && m->ml_desc, PLANAR_EINVAL, "null array in the map view");
+    if (int rc = check_map_arrays(*m, NEEDS_LOCAL_MAP)) return rc;
     PLANAR_REQUIRE(B >= 1, PLANAR_EINVAL, "B >= 1 required");
     PLANAR_REQUIRE(B <= ws->max_batch, PLANAR_EINVAL, "B exceeds the workspace's max_batch");
-    PLANAR_REQUIRE(m->kf_stride >= 1 && m->kf_stride <= MAXK, PLANAR_EINVAL, "1 <= kf_stride <= PLANAR_LOCALMAP_MAX_KEYFRAMES required");
-    PLANAR_REQUIRE(m->n_maps >= 1 && m->slot_stride >= 1 && m->line_slot_stride >= 1 && m->pt_stride >= 1 && m->ml_stride >= 1 && m->obs_cap >= 1 && m->child_cap >= 1,
-                   PLANAR_EINVAL, "n_maps and every stride and capacity of the map view must be >= 1");
-    PLANAR_REQUIRE(m->slot_stride <= MAX_SLOT_STRIDE && m->line_slot_stride <= MAX_SLOT_STRIDE, PLANAR_EINVAL, "slot strides above 2^20");
+    if (int rc = check_map_sizes(*m, NEEDS_LOCAL_MAP)) return rc;
     PLANAR_REQUIRE(m->kf_stride <= ws->kf_stride && m->pt_stride <= ws->pt_stride && m->ml_stride <= ws->ml_stride, PLANAR_EINVAL,
                    "the map's kf_stride / pt_stride / ml_stride exceed the workspace's");
     PLANAR_REQUIRE(local_kf_stride >= 1, PLANAR_EINVAL, "local_kf_stride >= 1 required");
     PLANAR_REQUIRE(frame_stride >= 1 && frame_line_stride >= 1 && lp_stride >= 1 && ll_stride >= 1, PLANAR_EINVAL, "frame and output strides must be >= 1");
-    PLANAR_REQUIRE(((uintptr_t)m->ml_xw6 & 7) == 0 && ((uintptr_t)m->ml_normal & 7) == 0 && ((uintptr_t)ll_xw6 & 7) == 0 && ((uintptr_t)ll_normal & 7) == 0, PLANAR_EINVAL,
+    PLANAR_REQUIRE(aligned(m->ml_xw6, 8) && aligned(m->ml_normal, 8) && aligned(ll_xw6, 8) && aligned(ll_normal, 8), PLANAR_EINVAL,
                    "the line arrays of doubles must start on an 8-byte boundary");
-    PLANAR_REQUIRE(((uintptr_t)m->pt_desc & 3) == 0 && ((uintptr_t)m->ml_desc & 3) == 0 && ((uintptr_t)lp_desc & 3) == 0 && ((uintptr_t)ll_desc & 3) == 0, PLANAR_EINVAL,
+    PLANAR_REQUIRE(aligned(m->pt_desc, 4) && aligned(m->ml_desc, 4) && aligned(lp_desc, 4) && aligned(ll_desc, 4), PLANAR_EINVAL,
                    "descriptor arrays must start on a 4-byte boundary");
     return PLANAR_OK;
 }
 
-static inline bool in_range_h(int v, int n) { return (unsigned)v < (unsigned)n; }
-
-// the host-pointer flavour's walk: every index a kernel could meet, on host arrays
-static int check_indices(const planar_local_map* m, int B, const int32_t* map_of, const int32_t* n_frame, const int32_t* frame_match, int frame_stride,
-                         const int32_t* n_frame_lines, const int32_t* frame_line_match, int frame_line_stride, const int32_t* local_kf, const int32_t* n_local_kf,
-                         int local_kf_stride) {
-    const int S = m->kf_stride, PS = m->pt_stride, LS = m->ml_stride;
-    std::vector<uint8_t> seen;
-    for (int g = 0; g < m->n_maps; g++) {
-        const int nk = m->n_kf[g], np = m->n_pts[g], nl = m->n_ml[g];
-        PLANAR_REQUIRE(nk >= 0 && nk <= S, PLANAR_EINVAL, "n_kf outside [0, kf_stride]");
-        PLANAR_REQUIRE(np >= 0 && np <= PS, PLANAR_EINVAL, "n_pts outside [0, pt_stride]");
-        PLANAR_REQUIRE(nl >= 0 && nl <= LS, PLANAR_EINVAL, "n_ml outside [0, ml_stride]");
-        const size_t gk = (size_t)g * S;
-        seen.assign((size_t)nk, 0);
-        const int32_t* co = m->child_off + (size_t)g * (S + 1);
-        for (int k = 0; k < nk; k++) {
-            const int r = m->kf_rank[gk + k];
-            PLANAR_REQUIRE(in_range_h(r, nk) && !seen[r], PLANAR_EINVAL, "kf_rank is not a permutation of [0, n_kf)");
-            seen[r] = 1;
-            for (int t = 0; t < NCOVIS; t++) {
-                const int c = m->covis[(gk + k) * NCOVIS + t];
-                PLANAR_REQUIRE(c >= -1 && c < nk, PLANAR_EINVAL, "covis entry out of range");
-            }
-            const int pa = m->parent[gk + k];
-            PLANAR_REQUIRE(pa >= -1 && pa < nk, PLANAR_EINVAL, "parent out of range");
-            PLANAR_REQUIRE(co[k] >= 0 && co[k + 1] >= co[k] && co[k + 1] <= m->child_cap, PLANAR_EINVAL, "child_off out of range");
-            for (int c = co[k]; c < co[k + 1]; c++)
-                PLANAR_REQUIRE(in_range_h(m->child[(size_t)g * m->child_cap + c], nk), PLANAR_EINVAL, "child out of range");
-            const int ns = m->n_slots[gk + k], nls = m->n_line_slots[gk + k];
-            PLANAR_REQUIRE(ns >= 0 && ns <= m->slot_stride && nls >= 0 && nls <= m->line_slot_stride, PLANAR_EINVAL, "slot count outside its stride");
-            for (int s = 0; s < ns; s++) {
-                const int id = m->kf_pts[(gk + k) * m->slot_stride + s];
-                PLANAR_REQUIRE(id >= -1 && id < np, PLANAR_EINVAL, "map-point slot out of range");
-            }
-            for (int s = 0; s < nls; s++) {
-                const int id = m->kf_lines[(gk + k) * m->line_slot_stride + s];
-                PLANAR_REQUIRE(id >= -1 && id < nl, PLANAR_EINVAL, "map-line slot out of range");
-            }
-        }
-        const int32_t* oo = m->obs_off + (size_t)g * (PS + 1);
-        for (int p = 0; p < np; p++) {
-            PLANAR_REQUIRE(oo[p] >= 0 && oo[p + 1] >= oo[p] && oo[p + 1] <= m->obs_cap, PLANAR_EINVAL, "obs_off out of range");
-            for (int o = oo[p]; o < oo[p + 1]; o++)
-                PLANAR_REQUIRE(in_range_h(m->obs_kf[(size_t)g * m->obs_cap + o], nk), PLANAR_EINVAL, "observation key frame out of range");
-        }
-    }
+// the host-pointer flavour's walk of the frames (check_map_indices walked the maps); any negative match means "none" to the kernel
+static int check_frame_indices(const planar_local_map* m, int B, const int32_t* map_of, const int32_t* n_frame, const int32_t* frame_match, int frame_stride,
+                               const int32_t* n_frame_lines, const int32_t* frame_line_match, int frame_line_stride, const int32_t* local_kf, const int32_t* n_local_kf,
+                               int local_kf_stride) {
+    const int S = m->kf_stride;
     for (int b = 0; b < B; b++) {
         const int g = map_of[b];
         PLANAR_REQUIRE(in_range_h(g, m->n_maps), PLANAR_EINVAL, "map_of out of range");
@@ -438,7 +382,7 @@ extern "C" {
 
 int planar_local_map_ws_create(planar_ctx* ctx, int max_batch, int kf_stride, int pt_stride, int ml_stride, planar_local_map_ws** out) {
     PLANAR_REQUIRE(ctx && out, PLANAR_EINVAL, "null argument");
-    PLANAR_REQUIRE(max_batch >= 1 && kf_stride >= 1 && kf_stride <= localmap::MAXK && pt_stride >= 1 && ml_stride >= 1, PLANAR_EINVAL,
+    PLANAR_REQUIRE(max_batch >= 1 && kf_stride >= 1 && kf_stride <= MAXK && pt_stride >= 1 && ml_stride >= 1, PLANAR_EINVAL,
                    "max_batch, pt_stride, ml_stride >= 1 and 1 <= kf_stride <= PLANAR_LOCALMAP_MAX_KEYFRAMES required");
     planar_local_map_ws* p = new planar_local_map_ws;      // the device block is allocated by the first call: creating the handle touches no device
     p->ctx = ctx; p->max_batch = max_batch; p->kf_stride = kf_stride; p->pt_stride = pt_stride; p->ml_stride = ml_stride;
@@ -450,15 +394,11 @@ void planar_local_map_ws_destroy(planar_local_map_ws* ws) { delete ws; }
 
 int planar_local_map_ws_set_profiling(planar_local_map_ws* ws, int enable) {
     PLANAR_REQUIRE(ws != nullptr, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    ws->prof.on = enable != 0;
-    ws->prof.reset();
-    return PLANAR_OK;
+    return set_profiling(ws->ctx, {&ws->prof}, enable);
 }
 int planar_local_map_ws_get_profile(planar_local_map_ws* ws, double* total_ms /* [5] */, int64_t* calls) {
     PLANAR_REQUIRE(ws && total_ms && calls, PLANAR_EINVAL, "null argument");
-    PLANAR_HIP_CHECK(hipStreamSynchronize(ws->ctx->stream));
-    return ws->prof.sum(total_ms, calls);
+    return get_profile(ws->ctx, {&ws->prof}, total_ms, calls);
 }
 
 int planar_update_local_map_dev(planar_local_map_ws* ws, const planar_local_map* map, int B, const int32_t* d_map_of, const int32_t* d_n_frame, int32_t* d_frame_match,
@@ -473,9 +413,7 @@ int planar_update_local_map_dev(planar_local_map_ws* ws, const planar_local_map*
                                       lp_stride, d_ll_id && d_n_ll && d_ll_valid && d_ll_xw6 && d_ll_normal && d_ll_min_dist && d_ll_max_dist && d_ll_desc && d_ll_observed,
                                       d_ll_xw6, d_ll_normal, d_ll_desc, ll_stride, d_status)) return rc;
     planar_ctx* ctx = ws->ctx;
-    PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ws->buf.p)
-        if (int rc = ws->buf.alloc(localmap::ws_bytes((size_t)ws->max_batch, (size_t)ws->kf_stride, (size_t)ws->pt_stride, (size_t)ws->ml_stride))) return rc;
+    if (int rc = ensure_block(ctx, ws->buf, localmap::ws_bytes((size_t)ws->max_batch, (size_t)ws->kf_stride, (size_t)ws->pt_stride, (size_t)ws->ml_stride))) return rc;
     const size_t S = map->kf_stride, PS = map->pt_stride, LS = map->ml_stride, nb = (size_t)B;
     localmap::Args a{};
     a.m = *map; a.B = B; a.frame_stride = frame_stride; a.frame_line_stride = frame_line_stride; a.local_kf_stride = local_kf_stride; a.lp_stride = lp_stride;
@@ -518,19 +456,15 @@ int planar_update_local_map(planar_local_map_ws* ws, const planar_local_map* map
                                       lp_id && n_lp && lp_valid && lp_xw && lp_normal && lp_min_dist && lp_max_dist && lp_desc && lp_observed, lp_desc, lp_stride,
                                       ll_id && n_ll && ll_valid && ll_xw6 && ll_normal && ll_min_dist && ll_max_dist && ll_desc && ll_observed, ll_xw6, ll_normal, ll_desc,
                                       ll_stride, status)) return rc;
-    if (int rc = localmap::check_indices(map, B, map_of, n_frame, frame_match, frame_stride, n_frame_lines, frame_line_match, frame_line_stride, local_kf, n_local_kf,
-                                         local_kf_stride)) return rc;
+    if (int rc = check_map_indices(*map, NEEDS_LOCAL_MAP)) return rc;
+    if (int rc = localmap::check_frame_indices(map, B, map_of, n_frame, frame_match, frame_stride, n_frame_lines, frame_line_match, frame_line_stride, local_kf, n_local_kf,
+                                               local_kf_stride)) return rc;
     planar_ctx* ctx = ws->ctx;
     PLANAR_HIP_CHECK(hipSetDevice(ctx->device));
     Stager s;
     planar_local_map d = *map;
-    const size_t G = map->n_maps, k = G * map->kf_stride, p = G * map->pt_stride, l = G * map->ml_stride, nb = (size_t)B;
-    s.in_field(d.n_kf, G); s.in_field(d.kf_bad, k); s.in_field(d.kf_rank, k); s.in_field(d.covis, k * localmap::NCOVIS); s.in_field(d.parent, k);
-    s.in_field(d.child_off, G * (map->kf_stride + 1)); s.in_field(d.child, G * map->child_cap); s.in_field(d.n_slots, k); s.in_field(d.kf_pts, k * map->slot_stride);
-    s.in_field(d.n_line_slots, k); s.in_field(d.kf_lines, k * map->line_slot_stride); s.in_field(d.n_pts, G); s.in_field(d.pt_bad, p);
-    s.in_field(d.obs_off, G * (map->pt_stride + 1)); s.in_field(d.obs_kf, G * map->obs_cap); s.in_field(d.pt_xw, p * 3); s.in_field(d.pt_normal, p * 3);
-    s.in_field(d.pt_min_dist, p); s.in_field(d.pt_max_dist, p); s.in_field(d.pt_desc, p * 32); s.in_field(d.n_ml, G); s.in_field(d.ml_bad, l); s.in_field(d.ml_observed, l);
-    s.in_field(d.ml_xw6, l * 6); s.in_field(d.ml_normal, l * 3); s.in_field(d.ml_min_dist, l); s.in_field(d.ml_max_dist, l); s.in_field(d.ml_desc, l * 32);
+    stage_map(s, d, NEEDS_LOCAL_MAP);
+    const size_t nb = (size_t)B;
     const auto d_map_of = s.in(map_of, nb), d_nf = s.in(n_frame, nb), d_nfl = s.in(n_frame_lines, nb);
     const auto d_fm = s.inout(frame_match, nb * frame_stride), d_flm = s.inout(frame_line_match, nb * frame_line_stride);
     const auto d_lkf = s.inout(local_kf, nb * local_kf_stride), d_nlkf = s.inout(n_local_kf, nb);

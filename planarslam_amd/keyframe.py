@@ -10,9 +10,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import NEEDKF_NOUT, Context, KfFrames, MapEditView, check, lib
+from ._mapview import NCOVIS, _addr, _place, _Workspace
 from .localmap import LocalMap
 
-NCOVIS = 10
 ONLY_TRACKING, MAPPER_STOPPED, MAPPER_ACCEPTS, NEW_PLANE = 1, 2, 4, 8
 OUT_FIELDS = ("need", "interrupt_ba", "n_matches_inliers", "n_ref_matches", "n_map", "n_total", "n_non_tracked_close", "c1a", "c1b", "c1c", "c2", "status")
 PARAMS = np.dtype([("frame_id", np.uint64), ("last_reloc_frame_id", np.uint32), ("last_kf_frame_id", np.uint32), ("max_frames", np.int32), ("min_frames", np.int32),
@@ -26,19 +26,6 @@ _FRAME_FIELDS = (("map_of", np.int32), ("n_frame", np.int32), ("frame_match", np
                  ("xw", np.float32), ("normal", np.float32), ("min_dist", np.float32), ("max_dist", np.float32), ("desc", np.uint8), ("n_frame_lines", np.int32),
                  ("frame_line_match", np.int32), ("line_outlier", np.uint8), ("depth_line", np.float32), ("xw6", np.float64), ("line_normal", np.float64),
                  ("line_min_dist", np.float32), ("line_max_dist", np.float32), ("line_desc", np.uint8))
-
-
-def _place(a, dt, device):
-    """-> a C-contiguous numpy array, or a torch tensor on `device`"""
-    a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a, dt)
-    if device is None:
-        return a
-    import torch
-    return torch.from_numpy(a).to(device)
-
-
-def _addr(a):
-    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
 
 
 class MapEdit:
@@ -98,14 +85,12 @@ class Frames:
         return {k: (a.cpu().numpy() if hasattr(a, "cpu") else a.copy()) for k, a in self.arrays.items()}
 
 
-class Workspace:
+class Workspace(_Workspace):
     """planar_keyframe_ws: 4 * (1 + pt_stride + ml_stride + obs_cap + ml_obs_cap) bytes per map of max_maps"""
+    _NAME = "planar_keyframe_ws"
 
     def __init__(self, ctx: Context, max_batch: int, max_maps: int, pt_stride: int, ml_stride: int, obs_cap: int, ml_obs_cap: int):
-        self.ctx, self.L = ctx, lib()
-        h = C.c_void_p()
-        check(self.L.planar_keyframe_ws_create(ctx.h, int(max_batch), int(max_maps), int(pt_stride), int(ml_stride), int(obs_cap), int(ml_obs_cap), C.byref(h)))
-        self.h = h
+        super().__init__(ctx, max_batch, max_maps, pt_stride, ml_stride, obs_cap, ml_obs_cap)
 
     @classmethod
     def for_map(cls, ctx: Context, m: MapEdit, max_batch: int):
@@ -120,17 +105,6 @@ class Workspace:
         ms, calls = np.zeros(3), np.zeros(3, np.int64)
         check(self.L.planar_keyframe_ws_get_profile(self.h, ms.ctypes.data, calls.ctypes.data))
         return ms, calls
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.planar_keyframe_ws_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _dev_outputs(spec, device):

@@ -9,8 +9,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import Context, LocalMapView, check, lib
+from ._mapview import NCOVIS, _addr, _place, _Workspace
 
-NCOVIS = 10
 _FIELDS = (("n_kf", np.int32), ("kf_bad", np.uint8), ("kf_rank", np.int32), ("covis", np.int32), ("parent", np.int32), ("child_off", np.int32), ("child", np.int32),
            ("n_slots", np.int32), ("kf_pts", np.int32), ("n_line_slots", np.int32), ("kf_lines", np.int32), ("n_pts", np.int32), ("pt_bad", np.uint8),
            ("obs_off", np.int32), ("obs_kf", np.int32), ("pt_xw", np.float32), ("pt_normal", np.float32), ("pt_min_dist", np.float32), ("pt_max_dist", np.float32),
@@ -35,40 +35,21 @@ class LocalMap:
         v.obs_cap, v.child_cap = d["obs_kf"].shape[-1], d["child"].shape[-1]
         self.arrays = {}
         for name, dt in _FIELDS:
-            a = np.ascontiguousarray(d[name].cpu().numpy() if hasattr(d[name], "cpu") else d[name], dt)
-            if device is not None:
-                import torch
-                a = torch.from_numpy(a).to(device)
-                setattr(v, name, a.data_ptr())
-            else:
-                setattr(v, name, a.ctypes.data)
-            self.arrays[name] = a
+            self.arrays[name] = _place(d[name], dt, device)
+            setattr(v, name, _addr(self.arrays[name]))
         self.view, self.device = v, device
 
 
-class Workspace:
+class Workspace(_Workspace):
     """planar_local_map_ws: the marks and prefix counts of up to max_batch frames (12 * kf_stride + 5 * (pt_stride + ml_stride) + 32 bytes each)"""
+    _NAME = "planar_local_map_ws"
 
     def __init__(self, ctx: Context, max_batch: int, kf_stride: int, pt_stride: int, ml_stride: int):
-        self.ctx, self.L = ctx, lib()
-        h = C.c_void_p()
-        check(self.L.planar_local_map_ws_create(ctx.h, int(max_batch), int(kf_stride), int(pt_stride), int(ml_stride), C.byref(h)))
-        self.h = h
+        super().__init__(ctx, max_batch, kf_stride, pt_stride, ml_stride)
 
     @classmethod
     def for_map(cls, ctx: Context, m: LocalMap, max_batch: int):
         return cls(ctx, max_batch, m.view.kf_stride, m.view.pt_stride, m.view.ml_stride)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.planar_local_map_ws_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _outputs(B, lp_stride, ll_stride, make):
